@@ -13,19 +13,25 @@ collective - env instances never interact).  Steps are issued as fused rollout l
 `--chunk` steps each (default 64; state stays in registers inside a launch); `--chunk 1` gives one
 launch per step.  Inputs (state, seeds) are resident in HBM before the timed region.
 
-A pass = exactly `--steps` steps.  One pass of a short run (the driver's `--steps 20` is one ~65 us launch) is
-shorter than the two device synchronisations that bracket it, so the timed region holds `reps` passes issued back
-to back (state advancing; default: as many as reach ~65 536 steps = 0.2 s, the length from which the per-launch time
-stops falling - a region of a few ms is spent in the GPU's clock ramp; `--reps 1` for a single pass).  `value` and
-`ms_per_step` are per step of that region, whose length the line states: `timed_steps` = steps x reps and
-`timed_region_s`.  `single_pass_ms` / `single_pass_value` are what ONE individually bracketed pass gives (median of 9,
-sync overhead included).
+A plain run sets up, runs `--warmup` steps, times exactly `--steps` steps (one pass, bracketed by device
+synchronisations and one pair of HIP events), writes the outputs if `--dump-outputs DIR` is given, and prints the
+line.  `value` and `ms_per_step` are per step of the timed region, whose length the line states: `timed_steps` and
+`timed_region_s`.  `--reps R` times R passes of `--steps` steps back to back instead (state advancing; `--reps 0`: as
+many as reach ~65 536 steps = 0.2 s, the length from which the per-launch time stops falling - a region of a few ms
+is spent in the GPU's clock ramp).
 
-One GPU: the line also carries `configs_measured` - short sub-runs of BASELINE.json's other single-GPU configurations
-(configs[1..3]: Env_1 / Env_2 at 65 536 envs, Env_3 at 262 144 envs with the random and the learned policy in both
-product forms, the class-default noise) on the same clock, each with its kernel, launch time and roofline fraction.
-N GPUs: after the collective-free headline region a second region runs the rollout hand-off (BASELINE.json configs[4],
-`--exchange allgather|gather`: RCCL on a side stream, overlapped with the next rollout) and reports it under `exchange`.
+`--dump-outputs DIR`: after the timed region, what the last timed step handed its caller (the rollout buffers' last
+row: obs, mask, action, reward, done; `--policy mlp` also log-probability, value and the bootstrap value) is written
+as DIR/<name>.npy in float32, env-major; above 64 MB in all a fixed sample of env indices (seed 0) is written, with
+the indices as DIR/env_index.npy.  Inputs are fixed by the arguments: the same arguments give the same outputs.
+
+`--full` adds, after the headline region and the dump: `single_pass_ms` / `single_pass_value` (what ONE individually
+bracketed pass gives, median of 9, sync overhead included); one GPU: `configs_measured` - short sub-runs of
+BASELINE.json's other single-GPU configurations (configs[1..3]: Env_1 / Env_2 at 65 536 envs, Env_3 at 262 144 envs
+with the random and the learned policy in both product forms, the class-default noise) on the same clock, each with
+its kernel, launch time and roofline fraction - and `cpu_baseline`; N GPUs: a second region that runs the rollout
+hand-off (BASELINE.json configs[4], `--exchange allgather|gather`: RCCL on a side stream, overlapped with the next
+rollout), reported under `exchange`.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
 """
@@ -41,6 +47,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most 64 MB in all
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense f16 / bf16 matrix peak
 F32_MFMA_PEAK_TFLOPS = 157.3
@@ -155,6 +162,7 @@ class Workload:
             g = torch.Generator(device="cpu").manual_seed(1234 + rank)
             self.sort_mode = (torch.rand(n, generator=g) < 0.5).to(torch.int32).to(dev)
         self.collector = None
+        self.last = None  # (buffers, row of the last step in them, or None: per-env tensors) after run()
         if policy == "mlp":
             self.collector = M.FusedPolicyRollout(
                 self.env, M.MlpPolicy.random_init(self.env.obs_dim, self.env.num_actions, seed=7, device=dev, precision=precision), self.chunk)
@@ -164,9 +172,13 @@ class Workload:
 
     def run(self, n_steps):
         chunk = self.chunk
+        if n_steps <= 0:
+            return
         if self.mode == "step":
             for _ in range(n_steps):
-                self.env.step(self.env.sample_actions(policy_seed=2024), sort_mode=self.sort_mode)
+                actions = self.env.sample_actions(policy_seed=2024)
+                obs, reward, done, mask = self.env.step(actions, sort_mode=self.sort_mode)
+            self.last = (dict(actions=actions, obs=obs, reward=reward, done=done, mask=mask), None)
             return
         n_full, tail = n_steps // chunk, n_steps % chunk
         if self.collector is not None:
@@ -174,11 +186,47 @@ class Workload:
                 self.collector.collect(chunk)
             if tail > 0:
                 self.collector.collect(tail)
+            self.last = (self.collector.buffers, (tail or chunk) - 1)
             return
         for _ in range(n_full):
             self.env.rollout(chunk, policy_seed=2024, buffers=self.buf, sort_mode=self.sort_mode)
         if tail > 0:
             self.env.rollout(tail, policy_seed=2024, buffers=self.buf, sort_mode=self.sort_mode)
+        self.last = (self.buf, (tail or chunk) - 1)
+
+    def dump_outputs(self, out_dir):
+        """What the last step of run() handed its caller, as out_dir/<name>.npy in float32 (env-major); above
+        DUMP_LIMIT_BYTES a fixed sample of env indices (seed 0), written as out_dir/env_index.npy."""
+        import numpy as np
+
+        torch = self.torch
+        torch.cuda.synchronize(self.dev)
+        bufs, row = self.last
+        arrays = {}
+        for name, t in bufs.items():
+            if t is None:
+                continue
+            if row is not None and t.dim() >= 2:  # [K, N, ...] rollout buffers: the last step's row
+                t = t[row]
+            arrays[name] = t
+        total = sum(t.numel() * 4 for t in arrays.values())
+        index = None
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, self.n * (DUMP_LIMIT_BYTES - 8 * self.n) // total)
+            index = np.sort(np.random.default_rng(0).choice(self.n, size=keep, replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        if index is not None:
+            np.save(os.path.join(out_dir, "env_index.npy"), index.astype(np.float64))
+            sel = torch.from_numpy(index).to(self.dev)
+        written = {}
+        for name, t in arrays.items():
+            if index is not None:
+                t = t.index_select(0, sel)
+            a = t.to(torch.float32).cpu().numpy()
+            np.save(os.path.join(out_dir, f"{name}.npy"), a)
+            written[name] = list(a.shape)
+        return {"dir": out_dir, "arrays": written, "dtype": "float32",
+                "env_sample": None if index is None else f"{len(index)} of {self.n} envs (seed 0, env_index.npy)"}
 
     def fused_bytes(self, steps_per_launch):
         """bytes a fused launch must move per env-step: outputs + action every step, state once per launch"""
@@ -199,18 +247,22 @@ class Workload:
         self.buf = self.collector = None
 
 
-def timed_region(torch, dev, wl, steps, reps, barrier=lambda: None, singles=9):
-    """`reps` passes of `steps` steps issued back to back, bracketed by barrier + synchronize on both sides (wall clock)
-    and by ONE pair of HIP events on the launch stream (an event pair per pass would put two event records between
-    consecutive launches: ~10 us per 65 us launch at --steps 20).  Returns wall seconds, event ms, and the median of
-    individually bracketed single passes."""
+def single_passes(torch, dev, wl, steps, n):
+    """The median wall time of `n` individually bracketed passes of `steps` steps (sync overhead included), or None."""
     single = []
-    for _ in range(min(reps, singles)):
+    for _ in range(n):
         t1 = time.perf_counter()
         wl.run(steps)
         torch.cuda.synchronize(dev)
         single.append(time.perf_counter() - t1)
     single.sort()
+    return single[len(single) // 2] if single else None
+
+
+def timed_region(torch, dev, wl, steps, reps, barrier=lambda: None):
+    """`reps` passes of `steps` steps issued back to back, bracketed by barrier + synchronize on both sides (wall clock)
+    and by ONE pair of HIP events on the launch stream (an event pair per pass would put two event records between
+    consecutive launches: ~10 us per 65 us launch at --steps 20).  Returns wall seconds and event ms."""
     barrier()
     torch.cuda.synchronize(dev)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -223,7 +275,7 @@ def timed_region(torch, dev, wl, steps, reps, barrier=lambda: None, singles=9):
     barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
-    return elapsed, ev0.elapsed_time(ev1), (single[len(single) // 2] if single else None)
+    return elapsed, ev0.elapsed_time(ev1)
 
 
 def roofline_of(wl, steps, reps, event_ms):
@@ -280,7 +332,8 @@ def sub_run(M, torch, dev, spec, target_s=0.12):
         torch.cuda.synchronize(dev)
         per_launch = max(1e-6, (time.perf_counter() - t1) / 4)
         reps = max(8, int(target_s / per_launch))
-        elapsed, event_ms, single = timed_region(torch, dev, wl, K, reps, singles=3)
+        single = single_passes(torch, dev, wl, K, 3)
+        elapsed, event_ms = timed_region(torch, dev, wl, K, reps)
         r = roofline_of(wl, K, reps, event_ms)
         assert wl.env.error_count() == 0
         out = {"workload": wl.describe(), "value": wl.n * K * reps / elapsed, "unit": "env-steps/s",
@@ -389,20 +442,26 @@ def main():
                          "once with seed 1234: BASELINE.json configs[2]) or the reference's sorting_rules()")
     ap.add_argument("--pipeline", type=int, default=0, choices=[0, 1, 2, 3],
                     help="mse_config.rollout_pipeline: 0 by size (default), 1 two-role, 2 one lane per env, 3 three-role ring")
-    ap.add_argument("--reps", type=int, default=0,
-                    help="passes of --steps steps inside the timed region (0 = as many as reach ~65 536 steps)")
+    ap.add_argument("--reps", type=int, default=1,
+                    help="passes of --steps steps inside the timed region (default 1: exactly --steps timed steps; "
+                         "0 = as many as reach ~65 536 steps)")
     ap.add_argument("--policy", default="random", choices=["random", "mlp"],
                     help="random: the on-device masked-uniform policy (headline); mlp: the reference's actor-critic MLP "
                          "evaluated inside the rollout kernel (MaskablePPO-shaped collection, BASELINE.json configs[3])")
     ap.add_argument("--precision", default="auto", choices=["auto", "f32", "f16x3"],
                     help="--policy mlp: arithmetic of the policy's matrix products (include/mse.h mse_policy_set_precision)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure single passes, cpu_baseline and configs_measured (one GPU) or the exchange leg "
+                         "(N GPUs, or --force-collective)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
     ap.add_argument("--cpu-budget", type=float, default=8.0)
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs_measured sub-runs (one GPU only)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the configs_measured sub-runs (one GPU only)")
     ap.add_argument("--exchange", default="auto", choices=["auto", "none", "allgather", "gather"],
-                    help="rollout hand-off leg after the headline region: auto = gather to rank 0 when N > 1, none at N = 1")
+                    help="--full: rollout hand-off leg after the headline region: auto = gather to rank 0 when N > 1, none at N = 1")
     ap.add_argument("--force-collective", action="store_true",
-                    help="rehearsal: run the --exchange leg at N = 1 through a one-rank RCCL group")
+                    help="rehearsal (with --full): run the --exchange leg at N = 1 through a one-rank RCCL group")
     args = ap.parse_args()
 
     import torch
@@ -420,7 +479,7 @@ def main():
     rehearsal = world > 1 and n_dev < world
     torch.cuda.set_device(dev_index)
     exchange_mode = args.exchange if args.exchange != "auto" else ("gather" if world > 1 else "none")
-    forced = args.force_collective and world == 1 and exchange_mode != "none"
+    forced = args.full and args.force_collective and world == 1 and exchange_mode != "none"
     if world > 1 or forced:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29511")
@@ -447,12 +506,15 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # default: ~65 536 steps (0.2 s) in the timed region.  Shorter regions measure the clock ramp, not the kernel: at
-    # --steps 20 a 8 ms region gives 75-77 us per launch, 70 ms 69.7, 0.27 s 68.6, 1.1 s 68.3
+    # default: exactly --steps timed steps.  Short regions measure the clock ramp, not the kernel: at --steps 20 a 8 ms
+    # region gives 75-77 us per launch, 70 ms 69.7, 0.27 s 68.6, 1.1 s 68.3; --reps 0 sizes
+    # the region to ~65 536 steps (0.2 s)
     reps = args.reps if args.reps > 0 else max(1, -(-65536 // args.steps))
     wl.run(args.warmup)
     torch.cuda.synchronize(dev)
-    elapsed, event_ms, single = timed_region(torch, dev, wl, args.steps, reps, barrier)
+    elapsed, event_ms = timed_region(torch, dev, wl, args.steps, reps, barrier)
+    dumped = wl.dump_outputs(args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    single = single_passes(torch, dev, wl, args.steps, 9) if args.full else None
 
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
     if world > 1:
@@ -474,8 +536,8 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "reps": reps,
             "timed_steps": args.steps * reps, "timed_region_s": elapsed,
             "ms_per_step": elapsed * 1e3 / (args.steps * reps),
-            "single_pass_ms": None if single is None else single * 1e3,
-            "single_pass_value": None if single is None else n * world * args.steps / single,
+            **({"single_pass_ms": None if single is None else single * 1e3,
+                "single_pass_value": None if single is None else n * world * args.steps / single} if args.full else {}),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "int32+f64 (integer state/masks, fp64 rewards, f32 observations)",
             "data": "synthetic",
@@ -493,9 +555,11 @@ def main():
             },
             "roofline": roof,
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
 
     # ---- N GPUs (or a forced one-rank rehearsal): the hand-off leg, after and apart from the headline region ----------
-    if exchange_mode != "none" and (world > 1 or forced) and args.mode == "rollout" and args.policy == "random":
+    if args.full and exchange_mode != "none" and (world > 1 or forced) and args.mode == "rollout" and args.policy == "random":
         wl.close()
         torch.cuda.empty_cache()
         try:
@@ -506,11 +570,11 @@ def main():
             out["exchange"] = ex
             out["exchange"]["hardware"] = "measured on this run's GPUs" if world > 1 and not rehearsal else \
                 "rehearsal only (one rank / shared GPU): no xGMI transfer took place"
-    elif out is not None and world > 1:
+    elif out is not None and world > 1 and exchange_mode == "none":
         out["exchange"] = {"mode": "none"}
 
     # ---- one GPU: BASELINE.json's other single-GPU configurations on the same clock ----------------------------------
-    if rank == 0 and world == 1 and not args.no_configs and args.mode == "rollout":
+    if args.full and rank == 0 and world == 1 and not args.no_configs and args.mode == "rollout":
         wl.close()
         torch.cuda.empty_cache()
         K = min(wl.chunk, args.steps)
@@ -534,7 +598,7 @@ def main():
         out["configs_measured"] = measured
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.kind, args.max_steps, args.noise, 200, args.cpu_budget)
         print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -242,7 +242,7 @@ def main():
     print(f"total {total/1024:.1f} KiB")
 
 
-if __name__ == "__main__" and not any(a in sys.argv for a in ("--rule-based", "--model", "--trace", "--random-mode", "--agents",
+if __name__ == "__main__" and not any(a in sys.argv for a in ("--rule-based", "--model", "--trace", "--random-mode", "--agents", "--vs-reference",
                                                               "--overflow-info")):
     main()
 
@@ -588,3 +588,44 @@ if __name__ == "__main__" and "--agents" in sys.argv:
     gen_agents()
 if __name__ == "__main__" and "--overflow-info" in sys.argv:
     gen_overflow_info()
+
+
+def gen_vs_reference():
+    """The reference's side of tests/test_oracle_vs_reference.py and tests/test_oracle_config_fuzz.py: every test case is
+    run once against the live reference, wrapped in tests/recorded_reference.Recorder, and what the reference returned
+    is stored as tests/golden/recorded_reference_<module>.npz; the tests play it back."""
+    import inspect
+
+    import pytest
+
+    from tests import recorded_reference as rr
+    from tests import test_oracle_config_fuzz, test_oracle_vs_reference
+
+    rr.recording = {}
+    cwd = os.getcwd()
+    for mod in (test_oracle_vs_reference, test_oracle_config_fuzz):
+        for name, fn in inspect.getmembers(mod, inspect.isfunction):
+            if not name.startswith("test_"):
+                continue
+            cases = [{}]  # the cross product of the function's parametrize marks
+            for m in getattr(fn, "pytestmark", []):
+                if m.name == "parametrize":
+                    keys = [k.strip() for k in m.args[0].split(",")]
+                    cases = [dict(c, **dict(zip(keys, v if len(keys) > 1 else (v,)))) for c in cases for v in m.args[1]]
+            for kw in cases:
+                try:
+                    fn(**kw)
+                except pytest.skip.Exception:
+                    pass
+    os.chdir(cwd)  # ref_harness.load() enters the reference checkout (it reads config.yml from the CWD)
+    for module, recs in rr.recording.items():
+        out = {}
+        for case, rec in recs.items():
+            out.update(rec.arrays(case))
+        path = rr.FIXTURES[module]
+        np.savez_compressed(path, **out)
+        print(f"{os.path.basename(path):48s} cases={len(recs):3d}  {os.path.getsize(path)/1024:7.1f} KiB")
+
+
+if __name__ == "__main__" and "--vs-reference" in sys.argv:
+    gen_vs_reference()

@@ -1,6 +1,8 @@
-"""Oracle vs the imported reference under fuzzed config.yml's (build container only): pins the CPU restatement off the
-three hand-written configurations of tests/golden/.  Every row: observation bits, reward (1e-12), mask, integer state,
-accuracies and all five PCG64 streams (the generator's only where the batch size makes it observable)."""
+"""Oracle vs the reference under fuzzed config.yml's: pins the CPU restatement off the three hand-written
+configurations of tests/golden/.  Every row: observation bits, reward (1e-12), mask, integer state, accuracies and all
+five PCG64 streams (the generator's only where the batch size makes it observable).  The reference's side is the
+recording in tests/golden/recorded_reference_config_fuzz.npz (tests/recorded_reference.py; regenerated from the
+imported reference by `python -m oracle.gen_golden --vs-reference`)."""
 import numpy as np
 import pytest
 
@@ -8,21 +10,24 @@ from oracle import ref_harness
 from oracle.oracle import OracleEnv
 from tests import replay
 from tests.fuzz_configs import fuzz_overrides, meta_for
+from tests.recorded_reference import reference_env
 
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference checkout not present")
+
+def _construct(cls, seed, ctor, ov):
+    from oracle.gen_golden import _construct as construct  # the live reference env (recording only)
+
+    return construct(cls, seed, ctor, ov)
 
 
 @pytest.mark.parametrize("seed", range(30))
 def test_oracle_matches_reference_under_a_fuzzed_config(seed):
-    from oracle.gen_golden import _construct
-
     kind = ("mono", "press", "sort")[seed % 3]
     masking = seed % 4 != 3 or kind == "sort"
     check_overflow = seed % 5 == 4   # overflow terminates with the penalty (default off in the reference's callers)
     hoard = seed % 6 == 5            # mostly no-ops: containers far beyond their capacity
     meta = meta_for(kind, seed)
     ov, ctor = fuzz_overrides(seed)
-    ref = _construct(ref_harness.load()[kind], seed, ctor, ov)
+    ref = reference_env("config_fuzz", f"{kind}_s{seed}", lambda: _construct(ref_harness.load()[kind], seed, ctor, ov))
     agent = None
     if kind == "press":
         agent = ref_harness.ScriptedSortAgent()
@@ -49,7 +54,7 @@ def test_oracle_matches_reference_under_a_fuzzed_config(seed):
             o_orc, r_orc, term_orc = orc.step(a, sm, use_action_masking=masking, check_overflow=check_overflow)
             assert np.array_equal(np.asarray(o_ref, np.float32).view(np.uint32), o_orc.view(np.uint32)), (episode, t)
             assert abs(r_ref - r_orc) <= 1e-12 and term_ref == term_orc, (episode, t, r_ref, r_orc)
-            I, D, R = ref_harness.snapshot(ref)
+            I, D, R = ref.snapshot()
             Io, Do, Ro = orc.snapshot()
             Io[59] = Io[60] = I[59] = I[60] = 0
             assert np.array_equal(I, Io), (episode, t, np.flatnonzero(I != Io))
@@ -57,18 +62,17 @@ def test_oracle_matches_reference_under_a_fuzzed_config(seed):
             assert np.array_equal(D, Do) and np.array_equal(R[:n_words], Ro[:n_words]), (episode, t)
             if term_ref:
                 break
+    ref.finish()
 
 
 @pytest.mark.parametrize("seed", range(6))
 def test_oracle_model_mode_matches_reference_under_a_fuzzed_config(seed):
     """Env_3_Monolith.step(action=None, mode='model') without agents (env_monolith.py:186-221) under fuzzed configs:
     the env's own rng_sorting / rng_pressing draws, masked and unmasked."""
-    from oracle.gen_golden import _construct
-
     masking = seed % 2 == 0
     meta = meta_for("mono", 40 + seed)
     ov, ctor = fuzz_overrides(40 + seed)
-    ref = _construct(ref_harness.load()["mono"], seed, ctor, ov)
+    ref = reference_env("config_fuzz", f"model_mono_s{seed}", lambda: _construct(ref_harness.load()["mono"], seed, ctor, ov))
     orc = OracleEnv(kind="mono", seed=seed, cfg=replay.oracle_config(meta))
     o_ref, _ = ref.reset(seed=seed)
     assert np.array_equal(np.asarray(o_ref, np.float32).view(np.uint32), orc.reset(seed).view(np.uint32))
@@ -79,5 +83,6 @@ def test_oracle_model_mode_matches_reference_under_a_fuzzed_config(seed):
         o_orc, r_orc, term_orc = orc.step(a)
         assert np.array_equal(np.asarray(o_ref, np.float32).view(np.uint32), o_orc.view(np.uint32)), t
         assert abs(r_ref - r_orc) <= 1e-12 and term_ref == term_orc
-        R, Ro = ref_harness.snapshot(ref)[2], orc.snapshot()[2]
+        R, Ro = ref.snapshot()[2], orc.snapshot()[2]
         assert np.array_equal(R[:24], Ro[:24]), t
+    ref.finish()

@@ -1,12 +1,12 @@
-"""Live check of the oracle against the imported reference on fresh random scripts (build
-container only: skipped wherever the reference checkout is absent, e.g. on the GPU box)."""
+"""The oracle against the reference on random scripts, call by call.  The reference's side is the recording in
+tests/golden/recorded_reference_random_scripts.npz (tests/recorded_reference.py; regenerated from the imported
+reference by `python -m oracle.gen_golden --vs-reference`)."""
 import numpy as np
 import pytest
 
 from oracle import ref_harness
 from oracle.oracle import OracleEnv
-
-pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference checkout not present")
+from tests.recorded_reference import reference_env
 
 
 @pytest.mark.parametrize("kind", ["mono", "press", "sort"])
@@ -14,8 +14,8 @@ pytestmark = pytest.mark.skipif(not ref_harness.available(), reason="reference c
 def test_random_script(kind, seed, noise, masking):
     if kind == "sort" and not masking:
         pytest.skip("Env_1 ignores use_action_masking")
-    cls = ref_harness.load()[kind]
-    ref = cls(max_steps=60, seed=seed, noise_sorting=noise, balesize=180)
+    ref = reference_env("random_scripts", f"{kind}_s{seed}",
+                        lambda: ref_harness.load()[kind](max_steps=60, seed=seed, noise_sorting=noise, balesize=180))
     agent = None
     if kind == "press":
         agent = ref_harness.ScriptedSortAgent()
@@ -42,10 +42,11 @@ def test_random_script(kind, seed, noise, masking):
             assert np.array_equal(np.asarray(o_ref, np.float32).view(np.uint32), o_orc.view(np.uint32)), (episode, t)
             assert abs(r_ref - r_orc) <= 1e-12
             assert term_ref == term_orc
-            I, D, R = ref_harness.snapshot(ref)
+            I, D, R = ref.snapshot()
             Io, Do, Ro = orc.snapshot()
             Io[59] = Io[60] = I[59] = I[60] = 0
             assert np.array_equal(I, Io), (episode, t, np.flatnonzero(I != Io))
             # (the generator's private stream - words 24.. - is only followed when the batch size leaves a floor()
             # remainder: tests/golden/*_cfgB_*; with config.yml's 100 it is never observed)
             assert np.array_equal(D, Do) and np.array_equal(R[:24], Ro[:24])
+    ref.finish()

@@ -2,7 +2,7 @@
 set -o pipefail
 OUT=gpurun_out/prof_roles; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-B="--no-cpu-baseline --no-configs"
+B="--no-cpu-baseline --no-configs --reps 0"
 for pl in 0 2; do
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --output-format csv -d $OUT/sq_p$pl -- python3 bench.py $B --policy mlp --envs 65536 --chunk 16 --steps 128 --warmup 16 --reps 1 --pipeline $pl > $OUT/sq_p$pl.json 2> $OUT/sq_p$pl.err || { echo failed; tail -3 $OUT/sq_p$pl.err; }
 python3 - <<PY

@@ -5,7 +5,7 @@
 set -o pipefail
 OUT=gpurun_out/prof_r02; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-B="--no-cpu-baseline"
+B="--full --no-cpu-baseline --reps 0"
 run_trace() { # tag, bench args
   local tag=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$tag -- python3 bench.py $B "$@" > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; }
@@ -30,7 +30,7 @@ run_pmc sq_mlp_262144 "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_VALU_MFMA_M
 run_pmc fetch_mlp_262144 FETCH_SIZE --policy mlp --envs 262144 --chunk 16 --steps 128 --warmup 16 --reps 1
 run_pmc write_mlp_262144 WRITE_SIZE --policy mlp --envs 262144 --chunk 16 --steps 128 --warmup 16 --reps 1
 # free-running reference points (no profiler attached)
-python3 bench.py --steps 20 --warmup 5 > $OUT/free_driver_line.json 2> $OUT/free.err
+python3 bench.py --full --reps 0 --steps 20 --warmup 5 > $OUT/free_driver_line.json 2> $OUT/free.err
 python3 bench.py $B > $OUT/free_k64.json 2>> $OUT/free.err
 for n in 65536 262144; do python3 bench.py $B --policy mlp --envs $n --chunk 16 --steps 256 --warmup 32 > $OUT/free_mlp_$n.json 2>> $OUT/free.err; done
 python3 bench.py $B --policy mlp --envs 262144 --chunk 64 --steps 256 --warmup 64 > $OUT/free_mlp_262144_k64.json 2>> $OUT/free.err

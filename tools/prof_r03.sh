@@ -6,7 +6,7 @@
 set -o pipefail
 OUT=gpurun_out/prof_r03; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-B="--no-cpu-baseline --no-configs"
+B="--no-cpu-baseline --no-configs --reps 0"
 run_trace() { # tag, bench args
   local tag=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$tag -- python3 bench.py $B "$@" > $OUT/$tag.json 2> $OUT/$tag.err || { echo "$tag failed"; tail -3 $OUT/$tag.err; }
@@ -35,7 +35,7 @@ run_pmc sq_mlp_65536 "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYC
 run_pmc fetch_mlp_262144 FETCH_SIZE --policy mlp --envs 262144 --chunk 16 --steps 128 --warmup 16 --reps 1
 run_pmc write_mlp_262144 WRITE_SIZE --policy mlp --envs 262144 --chunk 16 --steps 128 --warmup 16 --reps 1
 # free-running reference points (no profiler attached): the driver's line with its sub-runs, and a 64-step collector
-python3 bench.py --steps 20 --warmup 5 > $OUT/free_driver_line.json 2> $OUT/free.err
+python3 bench.py --full --reps 0 --steps 20 --warmup 5 > $OUT/free_driver_line.json 2> $OUT/free.err
 python3 bench.py $B > $OUT/free_k64.json 2>> $OUT/free.err
 python3 tools/summarize_r03.py $OUT > $OUT/summary.json
 # keep the merge small: drop the raw per-dispatch traces, keep stats and counter CSVs
