@@ -68,8 +68,8 @@ class MlpPolicy:
 
     def set_precision(self, precision: str) -> str:
         """"f32": exact f32 matrix products; "f16x3": three f16 MFMAs per product on 22-bit operand splits (logits
-        within ~1e-6 of f32, 5x the matrix rate); "auto": f16x3 when the weights fit f16's range.  Returns the form
-        in effect."""
+        within ~1e-6 of f32 at SB3-scale weights, ~3e-5 of float64 with hidden pre-activations of ~40; 5x the matrix
+        rate); "auto": f16x3 when the weights fit f16's range.  Returns the form in effect."""
         check(self.L.mse_policy_set_precision(self._h, self.PRECISIONS[precision]))
         self.precision = "f16x3" if self.L.mse_policy_precision(self._h) == 2 else "f32"
         return self.precision

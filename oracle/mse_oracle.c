@@ -1105,3 +1105,112 @@ double orc_env_random_rollout(orc_env *e, int64_t n_steps, uint64_t policy_seed)
     }
     return acc;
 }
+
+/* ====================================================================================== *
+ *  batch of envs (tests): the scalar env N times, range by range
+ * ====================================================================================== */
+
+struct orc_batch {
+    orc_config cfg;
+    int64_t    n;
+    int        obs_dim, num_actions;
+    uint64_t  *seeds;
+    orc_env  **envs;
+};
+
+orc_batch *orc_batch_create(const orc_config *cfg, int64_t n, uint64_t base_seed, const uint64_t *seeds)
+{
+    if (n < 1) return NULL;
+    orc_batch *b = (orc_batch *)calloc(1, sizeof(orc_batch));
+    if (!b) return NULL;
+    b->cfg = *cfg;
+    b->n = n;
+    b->seeds = (uint64_t *)malloc((size_t)n * sizeof(uint64_t));
+    b->envs = (orc_env **)calloc((size_t)n, sizeof(orc_env *));
+    if (!b->seeds || !b->envs) {
+        orc_batch_destroy(b);
+        return NULL;
+    }
+    for (int64_t i = 0; i < n; ++i) b->seeds[i] = seeds ? seeds[i] : base_seed + (uint64_t)i;
+    orc_env probe; /* the dimensions depend on the config only */
+    memset(&probe, 0, sizeof(probe));
+    probe.cfg = *cfg;
+    b->obs_dim = orc_env_obs_dim(&probe);
+    b->num_actions = orc_env_num_actions(&probe);
+    return b;
+}
+
+int64_t orc_batch_init(orc_batch *b, int64_t lo, int64_t hi)
+{
+    for (int64_t i = lo; i < hi; ++i) {
+        if (!b->envs[i]) b->envs[i] = orc_env_create(&b->cfg, 1, b->seeds[i]);
+        if (!b->envs[i]) return 1 + i;
+    }
+    return 0;
+}
+
+void orc_batch_destroy(orc_batch *b)
+{
+    if (!b) return;
+    if (b->envs)
+        for (int64_t i = 0; i < b->n; ++i) orc_env_destroy(b->envs[i]);
+    free(b->envs);
+    free(b->seeds);
+    free(b);
+}
+
+int64_t orc_batch_size(const orc_batch *b) { return b->n; }
+
+orc_env *orc_batch_env(orc_batch *b, int64_t i) { return (i >= 0 && i < b->n) ? b->envs[i] : NULL; }
+
+void orc_batch_reset(orc_batch *b, int64_t lo, int64_t hi, const uint64_t *seeds, const uint8_t *which, float *obs_out)
+{
+    const int D = b->obs_dim;
+    for (int64_t i = lo; i < hi; ++i) {
+        if (!which || which[i]) orc_env_reset(b->envs[i], seeds != NULL, seeds ? seeds[i] : 0, NULL);
+        if (obs_out) orc_env_obs(b->envs[i], obs_out + i * D);
+    }
+}
+
+int64_t orc_batch_step(orc_batch *b, int64_t lo, int64_t hi, const int32_t *actions, const int32_t *sort_mode,
+                       uint32_t flags, float *obs_out, float *terminal_obs_out, uint8_t *mask_pre_out,
+                       uint8_t *mask_post_out, double *reward_out, uint8_t *term_out)
+{
+    const int D = b->obs_dim, A = b->num_actions;
+    float obs[32];
+    for (int64_t i = lo; i < hi; ++i) {
+        orc_env *e = b->envs[i];
+        double reward;
+        int32_t term;
+        if (mask_pre_out) orc_env_action_mask(e, mask_pre_out + i * A);
+        if (orc_env_step(e, actions[i], sort_mode ? sort_mode[i] : -1, flags, obs, &reward, &term) != 0) return 1 + i;
+        if (terminal_obs_out) memcpy(terminal_obs_out + i * D, obs, (size_t)D * sizeof(float));
+        if (term) orc_env_reset(e, 0, 0, obs);
+        if (obs_out) memcpy(obs_out + i * D, obs, (size_t)D * sizeof(float));
+        if (mask_post_out) orc_env_action_mask(e, mask_post_out + i * A);
+        if (reward_out) reward_out[i] = reward;
+        if (term_out) term_out[i] = (uint8_t)(term != 0);
+    }
+    return 0;
+}
+
+void orc_batch_obs(const orc_batch *b, int64_t lo, int64_t hi, float *obs_out)
+{
+    for (int64_t i = lo; i < hi; ++i) orc_env_obs(b->envs[i], obs_out + i * b->obs_dim);
+}
+
+void orc_batch_action_mask(const orc_batch *b, int64_t lo, int64_t hi, uint8_t *mask_out)
+{
+    for (int64_t i = lo; i < hi; ++i) orc_env_action_mask(b->envs[i], mask_out + i * b->num_actions);
+}
+
+void orc_batch_sort_agent_obs(const orc_batch *b, int64_t lo, int64_t hi, float *obs13_out)
+{
+    for (int64_t i = lo; i < hi; ++i) orc_env_sort_agent_obs(b->envs[i], obs13_out + i * 13);
+}
+
+void orc_batch_snapshot(const orc_batch *b, int64_t lo, int64_t hi, int64_t *ints, double *dbls, uint64_t *rng_words)
+{
+    for (int64_t i = lo; i < hi; ++i)
+        orc_env_snapshot(b->envs[i], ints + i * ORC_SNAP_INTS, dbls + i * ORC_SNAP_DBLS, rng_words + i * ORC_SNAP_RNG_WORDS);
+}

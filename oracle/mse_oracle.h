@@ -171,6 +171,36 @@ int32_t orc_env_bales(const orc_env *e, int m, int64_t *sizes, int32_t *qs, int3
  * used by bench.py's cpu_baseline leg.  Returns sum of rewards (to defeat dead-code elimination). */
 double orc_env_random_rollout(orc_env *e, int64_t n_steps, uint64_t policy_seed);
 
+/* ---- batch of envs (tests): N scalar envs behind one handle ------------------------------
+ * Every call works on the env index range [lo, hi) and reads / writes rows lo..hi-1 of arrays that hold one row per
+ * env of the whole batch, so disjoint ranges can run on different threads at once.  The step is orc_env_step itself;
+ * a terminated env is reset with the unseeded rule (reset(seed=None)), as a batched engine with auto-reset does. */
+typedef struct orc_batch orc_batch;
+
+/* env i gets seed seeds[i], or base_seed + i when seeds is NULL; the envs are created by orc_batch_init */
+orc_batch *orc_batch_create(const orc_config *cfg, int64_t n, uint64_t base_seed, const uint64_t *seeds);
+int64_t orc_batch_init(orc_batch *b, int64_t lo, int64_t hi); /* Env(seed=...) for each: returns 0, or 1 + a failing index */
+void orc_batch_destroy(orc_batch *b);
+int64_t orc_batch_size(const orc_batch *b);
+orc_env *orc_batch_env(orc_batch *b, int64_t i);
+
+/* reset(seed=seeds[i]) (seeds NULL: reset(seed=None)) for the envs with which[i] != 0 (which NULL: all); obs_out [N, D] */
+void orc_batch_reset(orc_batch *b, int64_t lo, int64_t hi, const uint64_t *seeds, const uint8_t *which, float *obs_out);
+
+/* one step of each env in the range.  actions [N]; sort_mode [N] or NULL (-1 for all: the rule); every output may be
+ * NULL: obs_out [N, D] after the auto-reset, terminal_obs_out [N, D] before it, mask_pre_out / mask_post_out [N, A]
+ * (the action mask the action was taken under, and the one after the step), reward_out [N], term_out [N].
+ * Returns 0, or 1 + the index of the first env whose step was refused (its outputs and later envs' are unwritten). */
+int64_t orc_batch_step(orc_batch *b, int64_t lo, int64_t hi, const int32_t *actions, const int32_t *sort_mode,
+                       uint32_t flags, float *obs_out, float *terminal_obs_out, uint8_t *mask_pre_out,
+                       uint8_t *mask_post_out, double *reward_out, uint8_t *term_out);
+
+void orc_batch_obs(const orc_batch *b, int64_t lo, int64_t hi, float *obs_out);              /* [N, D]  */
+void orc_batch_action_mask(const orc_batch *b, int64_t lo, int64_t hi, uint8_t *mask_out);   /* [N, A]  */
+void orc_batch_sort_agent_obs(const orc_batch *b, int64_t lo, int64_t hi, float *obs13_out); /* [N, 13] */
+/* orc_env_snapshot per env: ints [N, ORC_SNAP_INTS], dbls [N, ORC_SNAP_DBLS], rng_words [N, ORC_SNAP_RNG_WORDS] */
+void orc_batch_snapshot(const orc_batch *b, int64_t lo, int64_t hi, int64_t *ints, double *dbls, uint64_t *rng_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -124,6 +125,23 @@ def lib() -> C.CDLL:
         L.orc_env_bales.restype = i32
         L.orc_env_random_rollout.argtypes = [C.c_void_p, i64, u64]
         L.orc_env_random_rollout.restype = dbl
+        vp = C.c_void_p
+        L.orc_batch_create.argtypes = [P(Config), i64, u64, vp]
+        L.orc_batch_create.restype = vp
+        L.orc_batch_init.argtypes = [vp, i64, i64]
+        L.orc_batch_init.restype = i64
+        L.orc_batch_destroy.argtypes = [vp]
+        L.orc_batch_size.argtypes = [vp]
+        L.orc_batch_size.restype = i64
+        L.orc_batch_env.argtypes = [vp, i64]
+        L.orc_batch_env.restype = vp
+        L.orc_batch_reset.argtypes = [vp, i64, i64, vp, vp, vp]
+        L.orc_batch_step.argtypes = [vp, i64, i64, vp, vp, u32, vp, vp, vp, vp, vp, vp]
+        L.orc_batch_step.restype = i64
+        L.orc_batch_obs.argtypes = [vp, i64, i64, vp]
+        L.orc_batch_action_mask.argtypes = [vp, i64, i64, vp]
+        L.orc_batch_sort_agent_obs.argtypes = [vp, i64, i64, vp]
+        L.orc_batch_snapshot.argtypes = [vp, i64, i64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -241,3 +259,120 @@ class OracleEnv:
 
     def random_rollout(self, n_steps, policy_seed=2024):
         return self.L.orc_env_random_rollout(self._h, int(n_steps), int(policy_seed))
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data
+
+
+class OracleBatch:
+    """N scalar oracle envs stepped in C (orc_batch_*), the index range split over a thread pool.
+
+    Env i is `OracleEnv(seed=seeds[i])` (seeds: u64 array, default base_seed + i); step() steps every env once and
+    resets the ones that terminate with reset(seed=None), the rule a batched engine with auto-reset follows.  The
+    ctypes calls release the GIL, so the threads run the C loops in parallel."""
+
+    def __init__(self, kind="mono", num_envs=1, base_seed=0, seeds=None, max_steps=50, noise_sorting=0.05,
+                 balesize=200, cfg: Config | None = None, threads: int | None = None):
+        self.L = lib()
+        self.cfg = cfg if cfg is not None else default_config(kind, max_steps, noise_sorting, balesize)
+        self.num_envs = n = int(num_envs)
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+            if seeds.shape != (n,):
+                raise ValueError("seeds must have one entry per env")
+        self._h = self.L.orc_batch_create(C.byref(self.cfg), n, int(base_seed) % 2**64, _p(seeds))
+        if not self._h:
+            raise MemoryError("orc_batch_create failed")
+        probe = OracleEnv(cfg=self.cfg, seed=0)
+        self.obs_dim, self.num_actions = probe.obs_dim, probe.num_actions
+        probe.close()
+        # never size the pool by os.cpu_count(): a shared machine may grant this process a few of its CPUs
+        self.threads = max(1, int(threads) if threads is not None else min(16, len(os.sched_getaffinity(0))))
+        step = -(-n // self.threads)
+        self._ranges = [(lo, min(n, lo + step)) for lo in range(0, n, step)]
+        self._pool = ThreadPoolExecutor(self.threads) if len(self._ranges) > 1 else None
+        bad = [r for r in self._map(self.L.orc_batch_init) if r]
+        if bad:
+            raise MemoryError(f"orc_env_create failed for env {bad[0] - 1}")
+
+    def _map(self, fn, *args):
+        if self._pool is None:
+            return [fn(self._h, lo, hi, *args) for lo, hi in self._ranges]
+        return list(self._pool.map(lambda r: fn(self._h, r[0], r[1], *args), self._ranges))
+
+    def close(self):
+        if getattr(self, "_pool", None) is not None:
+            self._pool.shutdown()
+            self._pool = None
+        if getattr(self, "_h", None):
+            self.L.orc_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _rows(self, width, dtype):
+        return np.zeros((self.num_envs, width), dtype=dtype)
+
+    def reset(self, seeds=None, which=None):
+        """reset(seed=seeds[i]) (None: reset(seed=None)) of the envs with which[i] != 0 (None: all) -> obs [N, D]."""
+        if seeds is not None:
+            seeds = np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64))
+            assert seeds.shape == (self.num_envs,)
+        if which is not None:
+            which = np.ascontiguousarray(np.asarray(which, dtype=np.uint8))
+            assert which.shape == (self.num_envs,)
+        obs = self._rows(self.obs_dim, np.float32)
+        self._map(self.L.orc_batch_reset, _p(seeds), _p(which), _p(obs))
+        return obs
+
+    def step(self, actions, sort_mode=None, use_action_masking=True, check_overflow=False, sanitize_late=False,
+             want_terminal_obs=False):
+        """One step of every env -> dict: obs [N, D] f32 (after the auto-reset), mask_pre / mask [N, A] u8 (before /
+        after the step), reward [N] f64, term [N] u8 [, terminal_obs [N, D] f32 (before the auto-reset)]."""
+        n = self.num_envs
+        actions = np.ascontiguousarray(np.asarray(actions, dtype=np.int32))
+        assert actions.shape == (n,)
+        if sort_mode is not None:
+            sort_mode = np.ascontiguousarray(np.asarray(sort_mode, dtype=np.int32))
+            assert sort_mode.shape == (n,)
+        flags = (0 if use_action_masking else STEP_UNMASKED) | (STEP_CHECK_OVERFLOW if check_overflow else 0) | \
+                (STEP_SANITIZE_LATE if sanitize_late else 0)
+        out = {"obs": self._rows(self.obs_dim, np.float32), "mask_pre": self._rows(self.num_actions, np.uint8),
+               "mask": self._rows(self.num_actions, np.uint8), "reward": np.zeros(n, np.float64),
+               "term": np.zeros(n, np.uint8)}
+        if want_terminal_obs:
+            out["terminal_obs"] = self._rows(self.obs_dim, np.float32)
+        bad = [r for r in self._map(self.L.orc_batch_step, _p(actions), _p(sort_mode), flags, _p(out["obs"]),
+                                    _p(out.get("terminal_obs")), _p(out["mask_pre"]), _p(out["mask"]),
+                                    _p(out["reward"]), _p(out["term"])) if r]
+        if bad:
+            raise ValueError(f"orc_env_step refused env {bad[0] - 1}'s action {int(actions[bad[0] - 1])}")
+        return out
+
+    def obs(self):
+        o = self._rows(self.obs_dim, np.float32)
+        self._map(self.L.orc_batch_obs, _p(o))
+        return o
+
+    def action_masks(self):
+        m = self._rows(self.num_actions, np.uint8)
+        self._map(self.L.orc_batch_action_mask, _p(m))
+        return m
+
+    def sort_agent_obs(self):
+        """[N, 13]: what Env_2_Pressing.step would hand its sorting agent on the next step (env_2_press.py:101)."""
+        o = self._rows(13, np.float32)
+        self._map(self.L.orc_batch_sort_agent_obs, _p(o))
+        return o
+
+    def snapshot(self):
+        """orc_env_snapshot of every env: ints [N, SNAP_INTS], dbls [N, SNAP_DBLS], rng words [N, SNAP_RNG_WORDS]."""
+        ints, dbls = self._rows(SNAP_INTS, np.int64), self._rows(SNAP_DBLS, np.float64)
+        rng = self._rows(SNAP_RNG_WORDS, np.uint64)
+        self._map(self.L.orc_batch_snapshot, _p(ints), _p(dbls), _p(rng))
+        return ints, dbls, rng

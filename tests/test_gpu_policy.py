@@ -9,9 +9,14 @@ same op; the weights are random with SB3's state_dict names and shapes."""
 import numpy as np
 import pytest
 
+from tests import policy_stream as ps
+
 pytestmark = pytest.mark.gpu
 
 LOGIT_TOL, LOGP_TOL = 2e-5, 1e-4
+# the f16x3 form on the saturating weight set (pre-activations up to ~40): it carries 22-bit operand splits, not f32's
+# 24 bits; measured 2.7e-5 against float64 (the f32 form 1.8e-5, torch's own fp32 1.1e-5)
+SATURATING_F16X3_LOGIT_TOL = 4e-5
 
 
 def _weights(obs_dim, n_actions, seed):
@@ -42,52 +47,78 @@ def _torch_reference(w, obs, mask):
     return logits, torch.log_softmax(logits, dim=1), value
 
 
-def _fmix32(h):
-    M = 0xFFFFFFFF
-    h ^= h >> 16
-    h = (h * 0x85EBCA6B) & M
-    h ^= h >> 13
-    h = (h * 0xC2B2AE35) & M
-    h ^= h >> 16
-    return h
+def _saturating_weights(obs_dim, n_actions, seed):
+    """Hidden layers at 8x SB3's initial scale (pre-activations of several units: tanh saturates, the folded tanh's
+    exp2 overflows) and the action head at gain 3 (logits reach tens: a softmax dominated by one action)."""
+    import torch
 
+    from marl_sortingenv_amd.policy import SB3_KEYS, _shapes
 
-def _word(seed, g, t):
-    """mse_policy_word(mse_policy_key(seed, g), t) of csrc/mse_policy_stream.h on the host."""
-    M = 0xFFFFFFFF
-    s = _fmix32((seed & M) ^ _fmix32(((seed >> 32) + 0x9E3779B9) & M))
-    key = _fmix32((s + (g & M) * 0x9E3779B1 + (g >> 32) * 0xC2B2AE3D) & M)
-    c = ((t & M) * 0x85EBCA77 + (t >> 32) * 0x27D4EB2F) & M
-    return _fmix32(c ^ key)
+    g = torch.Generator().manual_seed(seed)
+    w = {}
+    for k, s in zip(SB3_KEYS, _shapes(obs_dim, n_actions)):
+        if len(s) == 1:
+            w[k] = (torch.randn(s, generator=g) * 0.1).float()
+        else:
+            gain = 3.0 if k == "action_net.weight" else (1.0 if k == "value_net.weight" else 8.0 * 2.0 ** 0.5)
+            w[k] = (torch.randn(s, generator=g) * gain / s[1] ** 0.5).float()
+    return w
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
 @pytest.mark.parametrize("obs_dim,n_actions,n", [(29, 22, 1000), (16, 11, 333), (13, 2, 64), (29, 22, 31)])
 def test_policy_forward_matches_torch_fp32(obs_dim, n_actions, n, precision):
+    _check_forward(obs_dim, n_actions, n, precision, "test")
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+@pytest.mark.parametrize("obs_dim,n_actions,n", [(29, 22, 1000), (16, 11, 333), (13, 2, 64), (29, 22, 31)])
+def test_policy_forward_with_saturating_weights_matches_float64(obs_dim, n_actions, n, precision):
+    """Saturated tanh units (the folded tanh's exp2 overflows to inf) and a softmax dominated by one action."""
+    _check_forward(obs_dim, n_actions, n, precision, "saturating")
+
+
+def _check_forward(obs_dim, n_actions, n, precision, weights):
     import torch
 
     import marl_sortingenv_amd as M
 
-    w = _weights(obs_dim, n_actions, seed=obs_dim * 100 + n_actions)
+    make = _weights if weights == "test" else _saturating_weights
+    w = make(obs_dim, n_actions, seed=obs_dim * 100 + n_actions)
+    # the saturating set is held to float64 (at its magnitudes fp32 itself is off by ~1e-5)
+    w_ref = w if weights == "test" else {k: v.double() for k, v in w.items()}
+    logit_tol = SATURATING_F16X3_LOGIT_TOL if (weights == "saturating" and precision == "f16x3") else LOGIT_TOL
     pol = M.MlpPolicy(obs_dim, n_actions, w, device=0, precision=precision)
     assert pol.precision == precision
     g = torch.Generator().manual_seed(5)
-    obs = torch.rand((n, obs_dim), generator=g)  # observations live in [0, 1] (clip in env_super.py:339-359)
+    # observations lie in [-1, 1]: the obs clip, and four sort-obs slots are purity - 0.9 (env_super.py:339-359)
+    obs = torch.rand((n, obs_dim), generator=g) * 2.0 - 1.0
     mask = torch.rand((n, n_actions), generator=g) < 0.6
     mask[:, 0] = True  # action 0 is always valid in the reference's masks
+    # fixed edge rows: all -1, all 0, all +1 under a mask with only action 0 valid (logp = 0) and an all-valid one
+    edge = torch.tensor([-1.0, 0.0, 1.0]).repeat_interleave(2).unsqueeze(1).expand(6, obs_dim)
+    only0 = torch.zeros((6, n_actions), dtype=torch.bool)
+    only0[:, 0] = True
+    only0[1::2] = True
+    obs, mask, n = torch.cat([obs, edge]), torch.cat([mask, only0]), n + 6
+    single = torch.zeros(n, dtype=torch.bool)
+    single[n - 6::2] = True
     for use_mask in (True, False):
         mk = mask if use_mask else None
-        ref_logits, ref_logsm, ref_value = _torch_reference(w, obs, mk)
+        ref_logits, ref_logsm, ref_value = _torch_reference(w_ref, obs.to(w_ref["action_net.bias"].dtype), mk)
+        rt = ref_logits.dtype
         out = pol.forward(obs.cuda(), None if mk is None else mk.cuda(), seed=77, t=3, want_logits=True)
         logits = out["logits"].cpu()
-        assert torch.allclose(logits, ref_logits, atol=LOGIT_TOL, rtol=1e-6), (logits - ref_logits).abs().max()
-        assert torch.allclose(out["value"].cpu(), ref_value, atol=LOGIT_TOL, rtol=1e-6)
+        assert torch.allclose(logits.to(rt), ref_logits, atol=logit_tol, rtol=1e-6), (logits.to(rt) - ref_logits).abs().max()
+        assert torch.allclose(out["value"].cpu().to(rt), ref_value, atol=LOGIT_TOL, rtol=1e-6)
         act = out["action"].cpu().long()
         assert bool(((act >= 0) & (act < n_actions)).all())
         if mk is not None:
             assert bool(mk.gather(1, act.unsqueeze(1)).all()), "a masked action was sampled"
         # log-probability of the sampled action
-        assert torch.allclose(out["logp"].cpu(), ref_logsm.gather(1, act.unsqueeze(1)).squeeze(1), atol=LOGP_TOL)
+        assert torch.allclose(out["logp"].cpu().to(rt), ref_logsm.gather(1, act.unsqueeze(1)).squeeze(1), atol=LOGP_TOL)
+        if mk is not None:  # a single valid action: taken with certainty
+            assert bool((act[single] == 0).all()) and float(out["logp"].cpu()[single].abs().max()) <= LOGP_TOL
         # the sample is the inverse cdf of the engine's stream over the softmax masses in REGISTER order (the MFMA
         # accumulator's rows of half 0, then half 1: csrc/mse_policy_device.h): recompute it in fp64 from the device's
         # own logits; a draw that lands within 1e-5 of a boundary may fall on either side
@@ -95,8 +126,9 @@ def test_policy_forward_matches_torch_fp32(obs_dim, n_actions, n, precision):
         assert sorted(order) == list(range(n_actions))
         p = torch.softmax(logits.double(), dim=1).numpy()[:, order]
         cdf = np.cumsum(p, axis=1)
+        u_all = ps.uniform24(ps.word(77, np.arange(n), 3))
         for i in range(n):
-            u = (_word(77, i, 3) >> 8) * 2.0 ** -24
+            u = float(u_all[i])
             k = int(np.searchsorted(cdf[i], u, side="right"))
             k = order[min(k, n_actions - 1)]
             if int(act[i]) != k:
