@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mse_exact.h"
 #include "mse_policy_stream.h"
 
 namespace mse {
@@ -77,6 +78,8 @@ struct Params {
     int press_time0, press_time1; // the same as two scalars: selected per lane with v_cndmask, never indexed
     float inv_balesize;           // 1.0f / bale_standard_size (quotient estimate, fixed up exactly)
     double max_state_reward;      // used every step: stays a kernel argument (SGPR pair)
+    double sr_den, sr_inv;        // 5 * capacity and its reciprocal (state_ratio)
+    int sr_exact_max;             // state_ratio's reciprocal form is proven for 0 <= total_level <= this
     // stage vectors are one of three words: id 0 = empty (after reset), 1 / 2 = seasonal pattern
     uint32_t pat_word[3];   // packed u8x4 counts A..D (load/store conversion)
     uint32_t pat_word1, pat_word2; // the same as two scalars: a per-lane choice between them is two v_cndmask on
@@ -1353,14 +1356,17 @@ __device__ __forceinline__ int sample_masked_press_action(Env &e, const Params &
     return select_kth_bit(bits, (int)(m >> 32));
 }
 
-// round(true/total, 2) in hundredths = rint(fl(fl(true/total) * 100)), the way numpy rounds
-// (env_super.py:754, 785-789).  The literal fp64 form is also the cheapest one here: at one wave per
-// SIMD a kernel pays ~5 cycles per instruction whatever it is, and the division sequence is ~14
-// instructions; an integer formulation (fp32 reciprocal, remainder fix-up, exact-tie table) was
-// measured 6 % slower end to end.
-__device__ __forceinline__ int purity_hundredths(int tru, int total)
+// round(true/total, 2) in hundredths = rint(fl(fl(true/total) * 100)), the way numpy rounds (env_super.py:754,
+// 785-789), or `empty` for total == 0.  The integer form of mse_exact.h (about 10 instructions, one of them a
+// transcendental, against the fp64 division's 16 with two) decides every case but an exact tie or a total beyond its
+// proven range; those lanes evaluate the literal expression.  (Round 1 measured an integer form with an exact-tie table
+// 6 % slower in the one-lane kernel: it had a remainder fix-up and a table lookup and saved no instructions.)
+__device__ __forceinline__ int purity_hundredths(int tru, int total, int empty)
 {
-    return (int)rint(((double)tru / (double)total) * 100.0);
+    bool tie;
+    int k = (int)purity_quotient((uint32_t)tru, (uint32_t)total, purity_rcp((uint32_t)total), tie);
+    if (__builtin_expect(total > 0 && (tie || (uint32_t)total > kPurityExactMax), 0)) k = purity_literal(tru, total);
+    return total > 0 ? k : empty;
 }
 
 // amount // S and amount % S for 0 <= amount < 2^24 without a division: fp32 estimate, exact fix-up
@@ -1375,6 +1381,16 @@ __device__ __forceinline__ void divmod_small(int amount, int S, float inv_S, int
         q += 1;
         r -= S;
     }
+}
+
+// total_level / (5 capacity) of calculate_press_reward (env_super.py:1029): a reciprocal multiply and one fma
+// correction, proven at mse_create equal to the literal division for every total up to P.sr_exact_max (-1 if the proof
+// failed); a lane beyond that divides
+__device__ __forceinline__ double state_ratio(int total_level, const Params &P)
+{
+    double v = ratio_by_reciprocal(total_level, P.sr_den, P.sr_inv);
+    if (__builtin_expect(total_level > P.sr_exact_max, 0)) v = (double)total_level / P.sr_den;
+    return v;
 }
 
 // int(q * 100) of press_bale (env_super.py:664): q100 minus a bit of qi_down (the 101 cases, found by the host with the
@@ -1575,8 +1591,7 @@ __device__ __forceinline__ void press_action_rules(Env &e, const Params &P, cons
     if (mat == 4) e.ce = 0;
     e.lps = 1;
     e.lpa = total;
-    int q = 0;
-    if (tru > 0) q = purity_hundredths(tru, total); // round(x, 2)
+    const int q = purity_hundredths(tru, total, 0); // round(x, 2); 0 for an empty container
     const int pt0 = P.press_time0, pt1 = P.press_time1;
     const int pt = p ? pt1 : pt0;
     if (p) {
@@ -1599,9 +1614,7 @@ __device__ __forceinline__ void container_purity_k(const Env &e, int k[4])
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         const int total = e.ct[m] + e.cf[m];
-        int v = 101;
-        if (total > 0) v = purity_hundredths(e.ct[m], total);
-        k[m] = v;
+        k[m] = purity_hundredths(e.ct[m], total, 101);
     }
 }
 
@@ -2011,10 +2024,10 @@ __device__ __forceinline__ StepResult env_observe(const Snap &sn, const Params &
         bonus_v = tb.bonus[nb > 3 ? 3 : nb];
     }
 
-    // ---- purity: four fp64 divisions (they also cover batch A's LDS latency) ----------------------
+    // ---- purity (it also covers batch A's LDS latency) ------------------------------------------------
     // env_super.py:771-791; round(true/total, 2) in hundredths, [101] = empty container
 #pragma unroll
-    for (int m = 0; m < 4; ++m) k[m] = lvl[m] > 0 ? purity_hundredths(sn.ct[m], lvl[m]) : 101;
+    for (int m = 0; m < 4; ++m) k[m] = purity_hundredths(sn.ct[m], lvl[m], 101);
 
     // ---- batch B: reads keyed by the purities -------------------------------------------------------
     float pdiff_f[4] = {0.f, 0.f, 0.f, 0.f};
@@ -2035,7 +2048,7 @@ __device__ __forceinline__ StepResult env_observe(const Snap &sn, const Params &
     if (KIND != 1) {
         const PenaltyClass pc = classify_levels(lvl, P);
         const int total_level = lvl[0] + lvl[1] + lvl[2] + lvl[3] + lvl[4];
-        const double state_reward = ((double)total_level / (double)(5 * P.capacity)) * P.max_state_reward;
+        const double state_reward = state_ratio(total_level, P) * P.max_state_reward;
         bool penalised = pc.any_cat;
         double penalty = 0.0;
         if (__builtin_expect(pc.any_cat || pc.any_sev || pc.any_mild, 0)) { // rare: constants fetched only here
@@ -2116,7 +2129,7 @@ __device__ __forceinline__ double env_reward(int s_sum, bool lps, int amount, in
     if (KIND != 2) tanh_v = tb.tanh_s[s_sum];
     double rp = 0.0;
     if (KIND != 1) {
-        const double state_reward = ((double)total_level / (double)(5 * P.capacity)) * P.max_state_reward;
+        const double state_reward = state_ratio(total_level, P) * P.max_state_reward;
         bool penalised = pc.any_cat;
         double penalty = 0.0;
         if (__builtin_expect(pc.any_cat || pc.any_sev || pc.any_mild, 0)) {

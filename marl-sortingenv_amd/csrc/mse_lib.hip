@@ -2646,6 +2646,12 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     }
     P.rem_thr_units = (int)std::floor((double)cfg->bale_standard_size * cfg->bale_remainder_threshold);
     P.max_state_reward = cfg->max_state_reward;
+    // state_ratio: the reciprocal form up to the first total level where it differs from the literal division, checked
+    // over every total a stepped env can hold (no container above capacity + one batch: the overflow ends the
+    // episode); a lane beyond that bound divides
+    P.sr_den = (double)(5 * P.capacity);
+    P.sr_inv = 1.0 / P.sr_den;
+    P.sr_exact_max = ratio_exact_upto(P.sr_den, P.sr_inv, 5 * (P.capacity + 255));
     std::vector<uint32_t> image;
     std::string why;
     int trc = build_tables(*cfg, P, image, why);
