@@ -218,6 +218,30 @@ int mse_set_state(mse_env *env, const int64_t *ints_in, const double *dbls_in, c
  * MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_NO_PRESS_DRAW (an assigned agent decides that part).  Env_3 handles only. */
 int mse_model_actions(mse_env *env, uint32_t flags, int32_t *action_out, void *stream);
 
+/* K fused steps of Env_3_Monolith.step(action=None, mode='model') (env_monolith.py:186-221), agents assigned or not:
+ * per step k and env i the sorting part is the argmax of sort_agent's actor (13 -> 2) on get_sort_obs() after the
+ * step's flow update (what mse_sort_agent_obs previews), or - sort_agent NULL - rng_sorting.choice([0, 1]); the press
+ * part the argmax of press_agent's actor (16 -> 11) on get_press_obs() after the flow update (mse_press_agent_obs),
+ * with MSE_MODEL_PRESS_AGENT_MASKED over press_action_masks() (illegal actions at logit -1e8, as mse_policy_forward),
+ * or - press_agent NULL - the draw of mse_model_actions (rng_pressing.choice(flatnonzero(press_action_masks())), or
+ * choice(11) with MSE_STEP_UNMASKED).  Argmax ties go to the first maximum (mse_policy_forward, deterministic=1).  The
+ * flat action mode * 11 + press is then stepped as mse_step steps it without MSE_STEP_UNMASKED (no sanitising,
+ * env_monolith.py:254-257), MSE_STEP_CHECK_OVERFLOW honoured, auto-reset on termination.  Bit-identical to K rounds of
+ * mse_sort_agent_obs / mse_press_agent_obs, mse_policy_forward(deterministic=1), mse_model_actions(MSE_MODEL_NO_*_DRAW
+ * for the agents' parts) and mse_step: rng_sorting / rng_pressing advance as there, the policy step counter by K.
+ * Outputs are step-major, any may be NULL: actions_out i32[K,N], obs_out f32[K,N,29] (after any auto-reset),
+ * reward_out f32[K,N], done_out u8[K,N], mask_out u8[K,N,22] (the post-step rows, as mse_rollout), and the agents'
+ * views before the decision, written whether or not that agent is present: sort_obs_out f32[K,N,13],
+ * press_obs_out f32[K,N,16].  flags: MSE_STEP_UNMASKED (use_action_masking=False: the fallback press draw),
+ * MSE_STEP_CHECK_OVERFLOW, MSE_MODEL_PRESS_AGENT_MASKED.  Env_3 handles with auto_reset=1; agents in the f16x3 form
+ * (mse_policy_set_precision) on the env's device; not with literal_choice or in general generator mode
+ * (MSE_ERR_UNSUPPORTED_CONFIG: alternate the calls above instead). */
+#define MSE_MODEL_PRESS_AGENT_MASKED 64u /* the press agent is maskable and masking is on: argmax over press_action_masks() */
+struct mse_policy; /* a packed policy: mse_policy_create below */
+int mse_rollout_model(mse_env *env, struct mse_policy *sort_agent, struct mse_policy *press_agent, int32_t k_steps, uint32_t flags,
+                      int32_t *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *mask_out,
+                      float *sort_obs_out, float *press_obs_out, void *stream);
+
 /* Opt-in trace of ONE env: what the reference appends per step to its Python ledgers - reward_data
  * (env_super.py:402-408, 928-946), press_actions_per_timestep (:631-637, 730-736; env_monolith.py:136;
  * env_2_press.py:131) and the press_bale calls behind bale_count (:661-687) - which the dashboard reads

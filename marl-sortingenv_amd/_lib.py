@@ -9,6 +9,7 @@ from .build import LIB_PATH
 MSE_ENV_SORT, MSE_ENV_PRESS, MSE_ENV_MONO = 1, 2, 3
 MSE_STEP_UNMASKED, MSE_STEP_CHECK_OVERFLOW, MSE_ROLLOUT_RULE_BASED, MSE_STEP_SANITIZE_LATE = 1, 2, 4, 8
 MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_NO_PRESS_DRAW = 16, 32
+MSE_MODEL_PRESS_AGENT_MASKED = 64
 MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
@@ -20,6 +21,7 @@ EXPORTS = [
     "mse_error_count", "mse_algorithmic_bytes_per_step", "mse_tie_window",
     "mse_sort_agent_obs", "mse_policy_num_weights", "mse_policy_create", "mse_policy_destroy", "mse_policy_forward",
     "mse_get_policy_step", "mse_set_policy_step", "mse_model_actions", "mse_trace_begin", "mse_trace_end", "mse_press_agent_obs", "mse_rollout_policy", "mse_policy_set_precision", "mse_policy_precision",
+    "mse_rollout_model",
 ]
 
 _other_libs: dict = {}
@@ -117,6 +119,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_policy_precision.argtypes = [vp]
     L.mse_policy_forward.argtypes = [vp, i64, i64, vp, vp, u64, u64, C.c_int, vp, vp, vp, vp, vp]
     L.mse_rollout_policy.argtypes = [vp, vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     if path is None:
         _lib = L
     else:

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import (MSE_MODEL_NO_PRESS_DRAW, MSE_MODEL_NO_SORT_DRAW, MSE_ROLLOUT_RULE_BASED, MSE_SNAP_INTS, MSE_SNAP_RNG_WORDS,
+from ._lib import (MSE_MODEL_NO_PRESS_DRAW, MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_PRESS_AGENT_MASKED, MSE_ROLLOUT_RULE_BASED, MSE_SNAP_INTS, MSE_SNAP_RNG_WORDS,
                    MSE_STEP_CHECK_OVERFLOW, MSE_STEP_SANITIZE_LATE, MSE_STEP_UNMASKED, MSE_TRACE_COLS, check, load_library)
 from .config import NUM_ACTIONS, OBS_DIM, SortingEnvConfig
 
@@ -201,21 +201,39 @@ class BatchedSortingEnv:
     def policy_step(self, t: int) -> None:
         check(self.L.mse_set_policy_step(self._h, int(t)))
 
-    def alloc_rollout(self, k_steps: int, obs=True, mask=True, actions=True, reward=True, done=True):
+    def alloc_rollout(self, k_steps: int, obs=True, mask=True, actions=True, reward=True, done=True,
+                      sort_obs=False, press_obs=False):
+        """Step-major rollout buffers.  sort_obs / press_obs (policy="model"): the agents' views of every step,
+        f32[K, N, 13] / f32[K, N, 16], under keys that are only there when asked for."""
         n, dev, K = self.num_envs, self.device, int(k_steps)
-        return {
+        buffers = {
             "actions": torch.empty((K, n), dtype=torch.int32, device=dev) if actions else None,
             "obs": torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev) if obs else None,
             "reward": torch.empty((K, n), dtype=torch.float32, device=dev) if reward else None,
             "done": torch.empty((K, n), dtype=torch.uint8, device=dev) if done else None,
             "mask": torch.empty((K, n, self.num_actions), dtype=torch.uint8, device=dev) if mask else None,
         }
+        if sort_obs:
+            buffers["sort_obs"] = torch.empty((K, n, 13), dtype=torch.float32, device=dev)
+        if press_obs:
+            buffers["press_obs"] = torch.empty((K, n, 16), dtype=torch.float32, device=dev)
+        return buffers
 
     def rollout(self, k_steps: int, policy_seed: int = 2024, buffers: Optional[dict] = None,
                 sort_mode: Optional[torch.Tensor] = None, use_action_masking: bool = True,
-                check_overflow: bool = False, policy: str = "random") -> dict:
-        """K fused steps in one kernel launch under an on-device policy: "random" (masked-uniform) or
-        "rule_based" (the reference's mode='rule_based')."""
+                check_overflow: bool = False, policy: str = "random", sort_agent=None, press_agent=None,
+                press_agent_maskable: bool = True) -> dict:
+        """K fused steps in one kernel launch under an on-device policy: "random" (masked-uniform),
+        "rule_based" (the reference's mode='rule_based') or, on Env_3, "model": Env_3_Monolith.step(action=None,
+        mode='model') (env_monolith.py:186-221) with an optional sorting agent (MlpPolicy 13 -> 2) and pressing agent
+        (MlpPolicy 16 -> 11) evaluated inside the kernel (argmax), the env's own rng_sorting / rng_pressing drawing
+        the part no agent decides (mse_rollout_model).  press_agent_maskable: the pressing agent is a MaskablePPO, so
+        with use_action_masking it is shown press_action_masks() (env_monolith.py:201-206)."""
+        if policy == "model":
+            if sort_mode is not None:
+                raise ValueError("policy='model' takes its sorting decisions from sort_agent or rng_sorting, not sort_mode")
+            return self._rollout_model(k_steps, buffers, use_action_masking, check_overflow, sort_agent, press_agent,
+                                       press_agent_maskable)
         if buffers is None:
             buffers = self.alloc_rollout(k_steps)
         if sort_mode is not None:
@@ -226,12 +244,31 @@ class BatchedSortingEnv:
         if policy == "rule_based":
             flags |= MSE_ROLLOUT_RULE_BASED
         elif policy != "random":
-            raise ValueError("policy must be 'random' or 'rule_based'")
+            raise ValueError("policy must be 'random', 'rule_based' or 'model'")
         with torch.cuda.device(self.device):
             check(self.L.mse_rollout(self._h, int(k_steps), int(policy_seed), _ptr(sort_mode), flags,
                                      _ptr(buffers.get("actions")), _ptr(buffers.get("obs")),
                                      _ptr(buffers.get("reward")), _ptr(buffers.get("done")),
                                      _ptr(buffers.get("mask")), self._stream()))
+        return buffers
+
+    def _rollout_model(self, k_steps, buffers, use_action_masking, check_overflow, sort_agent, press_agent,
+                       press_agent_maskable):
+        if buffers is None:
+            buffers = self.alloc_rollout(k_steps, sort_obs=True, press_obs=True)
+        for key, b in buffers.items():  # the kernel writes K full rows into every buffer it is given
+            if b is not None and (b.shape[0] < int(k_steps) or b.shape[1] != self.num_envs or not b.is_contiguous()):
+                raise ValueError(f"buffers[{key!r}] must be a contiguous [>= {int(k_steps)}, {self.num_envs}, ...] tensor")
+        flags = (0 if use_action_masking else MSE_STEP_UNMASKED) | (MSE_STEP_CHECK_OVERFLOW if check_overflow else 0)
+        if press_agent is not None and use_action_masking and press_agent_maskable:
+            flags |= MSE_MODEL_PRESS_AGENT_MASKED
+        with torch.cuda.device(self.device):
+            check(self.L.mse_rollout_model(self._h, None if sort_agent is None else sort_agent._h,
+                                           None if press_agent is None else press_agent._h, int(k_steps), flags,
+                                           _ptr(buffers.get("actions")), _ptr(buffers.get("obs")),
+                                           _ptr(buffers.get("reward")), _ptr(buffers.get("done")),
+                                           _ptr(buffers.get("mask")), _ptr(buffers.get("sort_obs")),
+                                           _ptr(buffers.get("press_obs")), self._stream()))
         return buffers
 
     # ---- state export / import (tests, checkpoint, dashboard trace) ---------------------------

@@ -11,6 +11,11 @@ agent.  Two launches per step.
 `FusedPolicyRollout` is the same collection in ONE launch per rollout (`mse_rollout_policy`): the policy forward runs
 inside the rollout kernel, the observation never leaves the wave's registers between the env transition and the
 policy's MFMA chain.  Its buffers are bit-identical to `PolicyRolloutCollector`'s for the same seed.
+
+`ModelRolloutCollector` is Env_3_Monolith.step(action=None, mode='model') (env_monolith.py:186-221) for N envs in
+several launches per step: the agents' previews, their forwards, the env's own fallback draws, the step.  It is what
+`BatchedSortingEnv.rollout(K, policy="model")` (`mse_rollout_model`, one launch per rollout) is held against, and it
+serves the handles that kernel refuses (literal_choice, general generator mode).
 """
 from __future__ import annotations
 
@@ -127,4 +132,53 @@ class FusedPolicyRollout:
                                            ptr(b["actions"]), ptr(b["log_probs"]), ptr(b["values"]), ptr(b["rewards"]),
                                            ptr(b["episode_starts"]), ptr(b["last_values"]), ptr(b["last_dones"]),
                                            env._stream()))
+        return b
+
+
+class ModelRolloutCollector:
+    """Env_3_Monolith.step(action=None, mode='model') for every env, one round of launches per step:
+    mse_sort_agent_obs, mse_press_agent_obs, up to two deterministic MlpPolicy forwards (sort_agent 13 -> 2, press_agent
+    16 -> 11), mse_model_actions drawing the parts no agent decides, mse_step.  press_agent_maskable: the pressing agent
+    is a MaskablePPO, so with use_action_masking it is shown press_action_masks() (env_monolith.py:201-206).
+    `collect` fills the buffers `BatchedSortingEnv.rollout(K, policy="model")` fills, with the same values."""
+
+    def __init__(self, env: BatchedSortingEnv, sort_agent: Optional[MlpPolicy] = None,
+                 press_agent: Optional[MlpPolicy] = None, press_agent_maskable: bool = True):
+        if env.kind != "mono":
+            raise ValueError("mode='model' exists on Env_3_Monolith only (env_monolith.py:186)")
+        if sort_agent is not None and (sort_agent.obs_dim != 13 or sort_agent.n_actions != 2):
+            raise ValueError("the sorting agent must be a 13 -> 2 policy")
+        if press_agent is not None and (press_agent.obs_dim != 16 or press_agent.n_actions != 11):
+            raise ValueError("the pressing agent must be a 16 -> 11 policy")
+        if not env.auto_reset:
+            raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+        self.env, self.sort_agent, self.press_agent = env, sort_agent, press_agent
+        self.press_agent_maskable = bool(press_agent_maskable)
+        self._sort_out = self._press_out = None
+
+    def collect(self, k_steps: int, use_action_masking: bool = True, check_overflow: bool = False,
+                buffers: Optional[dict] = None) -> dict:
+        env, K = self.env, int(k_steps)
+        b = env.alloc_rollout(K, sort_obs=True, press_obs=True) if buffers is None else buffers
+        masked_agent = self.press_agent is not None and use_action_masking and self.press_agent_maskable
+        env.refresh_outputs()  # env.mask = action_masks() of the current state, whatever ran on the handle before
+        for k in range(K):
+            sort_obs, press_obs = env.sort_agent_obs(), env.press_agent_obs()
+            if self.sort_agent is not None:
+                self._sort_out = self.sort_agent.forward(sort_obs, None, deterministic=True, out=self._sort_out)
+            if self.press_agent is not None:
+                mask = env.mask[:, :11] if masked_agent else None  # press_action_masks()
+                self._press_out = self.press_agent.forward(press_obs, mask, deterministic=True, out=self._press_out)
+            action = env.model_actions(use_action_masking, draw_sort=self.sort_agent is None,
+                                       draw_press=self.press_agent is None)
+            if self.sort_agent is not None:
+                action += 11 * self._sort_out["action"]
+            if self.press_agent is not None:
+                action += self._press_out["action"]
+            # applied without sanitising (env_monolith.py:254-257): masked step semantics whatever use_action_masking
+            obs, rew, done, mask = env.step(action, check_overflow=check_overflow)
+            for key, v in (("actions", action), ("obs", obs), ("reward", rew), ("done", done), ("mask", mask),
+                           ("sort_obs", sort_obs), ("press_obs", press_obs)):
+                if b.get(key) is not None:
+                    b[key][k].copy_(v)
         return b

@@ -1705,6 +1705,193 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
     }
 }
 
+// ==========================================================================================
+// Env_3 mode='model' rollout: the modular agents + the env's fallback draws + the transition, K steps per launch
+// (DESIGN.md "Model rollout")
+//
+// Env_3_Monolith.step(action=None, mode='model') (env_monolith.py:186-221): the sorting part is the sorting agent's
+// argmax on get_sort_obs() after the step's flow update, or rng_sorting.choice([0, 1]); the press part the pressing
+// agent's argmax on get_press_obs() after the flow update (press_action_masks() as its mask when it is maskable and
+// masking is on), or rng_pressing.choice(flatnonzero(press_action_masks())) / choice(11).  The flat action is applied
+// without sanitising (:254-257).  Shaped like k_rollout_policy: one wave owns 32 TILES envs for the whole launch, the
+// two agents' weight images and the tables are in LDS, the env state stays in registers.  Per step a copy of the env
+// takes the flow update for both previews (env_step takes the same step), the agents run their actors only (no
+// critic), the lane's own PCG64 streams draw what no agent decides (the code of k_model_actions), env_step applies
+// the action.  The streams' planes are only read and written by the instantiations that draw from them.
+// LDS: [sorting agent image][pressing agent image][tables][per wave: row tile | bale ledger]
+// ==========================================================================================
+template <bool NOISE, bool SORT_AG, bool PRESS_AG, int TILES>
+__global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restrict__ planes,
+                                                       const uint32_t *__restrict__ table_image,
+                                                       const float *__restrict__ sort_blob,
+                                                       const float *__restrict__ press_blob, int k_steps, uint32_t flags,
+                                                       int *__restrict__ actions_out, float *__restrict__ obs_out,
+                                                       float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
+                                                       uint8_t *__restrict__ mask_out, float *__restrict__ sort_obs_out,
+                                                       float *__restrict__ press_obs_out)
+{
+    using L = PolLayout<3, TILES>; // the row tile holds an observation row (29 floats) or a mask row
+    constexpr int D = L::D, A = L::A, ENVS = L::ENVS, NR = msep::regs_for_actions(11);
+    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
+    float *lw = reinterpret_cast<float *>(lds);
+    constexpr int kWeightBytes = L::weight_bytes * 2; // [sorting agent image][pressing agent image]
+    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
+    const int table_bytes = P.table_words * 4;
+    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
+    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
+    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
+    long long rem = P.n - wave_row0;
+    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
+    const bool wave_active = n_valid > 0;
+    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
+    // the batch's end its last env; mirrors store nothing
+    const int src_lane = TILES == 1 ? (lane & 31) : lane;
+    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
+    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
+
+    if (SORT_AG) msep_copy_image(lw, sort_blob, true, tid, blockDim.x);
+    if (PRESS_AG) msep_copy_image(lw + msep::kLdsFloats, press_blob, true, tid, blockDim.x);
+    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
+        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
+    const BaleRef bales{lbale + src_lane, ENVS};
+    if (P.track_bales && wave_active) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
+    }
+    Env e;
+    load_env<3, NOISE>(e, planes, P, i);
+    Rng32 srt, prs; // rng_sorting (seed+2), rng_pressing (seed+3): the fallback draws (k_model_actions)
+    if (!SORT_AG && wave_active) {
+        const uint4 a = planes[(long long)PL_SORTRNG_STATE * P.n_pad + i], b = planes[(long long)PL_SORTRNG_INC * P.n_pad + i];
+        const uint4 x = planes[(long long)PL_SORTRNG_AUX * P.n_pad + i];
+        srt.g.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
+        srt.g.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
+        srt.g.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
+        srt.g.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
+        srt.uinteger = x.x;
+        srt.has = (int)x.y;
+    }
+    if (!PRESS_AG && wave_active) { // the 32-bit buffer came with PL_MISC2 (load_env)
+        const uint4 a = planes[(long long)PL_PRESS_STATE * P.n_pad + i], b = planes[(long long)PL_PRESS_INC * P.n_pad + i];
+        prs.g.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
+        prs.g.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
+        prs.g.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
+        prs.g.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
+        prs.uinteger = e.press_uint;
+        prs.has = e.press_has;
+    }
+    __syncthreads();
+    if (!wave_active) return;
+    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
+    const Tables tb = tables_at(ltab, P);
+    const msep::lds_f4 wl_sort = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
+    const msep::lds_f4 wl_press = (msep::lds_f4)(__attribute__((address_space(3))) float *)(lw + msep::kLdsFloats);
+    const bool unmasked_draw = (flags & MSE_STEP_UNMASKED) != 0;
+    const bool agent_masked = (flags & MSE_MODEL_PRESS_AGENT_MASKED) != 0;
+    const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // mode='model' actions are applied unsanitised
+    const int h = lane >> 5;
+    int kcur[4]; // container purities of the current state (the sorting view needs them)
+    container_purity_k(e, kcur);
+
+    // press_action_masks() bits of env -> bit r: the action of accumulator register r of half h is legal
+    auto legal_of = [&](uint32_t env_bits) -> uint32_t {
+        const uint32_t t = env_bits >> (4 * h);
+        return (t & 0xFu) | ((t >> 4) & 0xF0u) | ((t >> 8) & 0xF00u) | ((t >> 12) & 0xF000u);
+    };
+    // swap(o[2q], o[2q+1]) = {tile 0's k-step q operand, tile 1's} (k_rollout_policy)
+    auto operands_of = [&](const float *ob, float (*x)[16]) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(ob[2 * q]), __float_as_uint(ob[2 * q + 1]), false, false);
+            x[0][q] = __uint_as_float(r[0]);
+            x[1][q] = __uint_as_float(r[1]);
+        }
+    };
+
+    float *ltile = reinterpret_cast<float *>(lwave);
+    const uint32_t lrow_obs = lds_row_address(ltile + src_lane * D);
+    const uint32_t lrow_sort = lds_row_address(ltile + src_lane * 13);
+    const uint32_t lrow_press = lds_row_address(ltile + src_lane * 16);
+    const uint32_t lrow_mask = lds_row_address(lwave + src_lane * A);
+    for (int s = 0; s < k_steps; ++s) {
+        const long long srow = (long long)s * P.n + wave_row0;
+        // ---- the agents' views: get_sort_obs() / get_press_obs() one flow update ahead (a copy takes the update)
+        float so[32], po[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) so[j] = po[j] = 0.0f;
+        {
+            Env ec = e;
+            update_environment<false>(ec, P);
+            sort_obs<false>(ec, P, tb, kcur, so);
+            press_obs<false>(ec, P, tb, po);
+        }
+        if (sort_obs_out != nullptr) wave_store_rows_f32<13, ENVS>(ltile, lrow_sort, so, sort_obs_out + srow * 13, n_valid, lane);
+        if (press_obs_out != nullptr) wave_store_rows_f32<16, ENVS>(ltile, lrow_press, po, press_obs_out + srow * 16, n_valid, lane);
+        // press_action_masks() of the state the decision is taken in (the flow update does not change it)
+        const uint32_t pbits = press_mask_bits(e, P);
+        // ---- sorting part
+        int sm;
+        if (SORT_AG) {
+            float sx[2][16];
+            operands_of(so, sx);
+            int sa[2];
+            msep::actor_argmax2_tiles<true, TILES>(wl_sort, lane, sx, sa);
+            sm = (TILES == 2 && h) ? sa[1] : sa[0];
+        } else {
+            sm = (int)srt.lemire(2u); // rng_sorting.choice([0, 1])
+        }
+        // ---- press part
+        int pa;
+        if (PRESS_AG) {
+            float px[2][16];
+            operands_of(po, px);
+            uint32_t pb0, pb1;
+            msep::both_halves_u32(agent_masked ? pbits : 0x7FFu, pb0, pb1);
+            const uint32_t legal[2] = {legal_of(pb0), legal_of(pb1)};
+            const uint32_t words[2] = {0u, 0u};
+            msep::TileOut p[2];
+            msep::actor_tiles<NR, true, TILES>(wl_press, lane, px, legal, true, words, p);
+            pa = (TILES == 2 && h) ? p[1].action : p[0].action;
+        } else if (unmasked_draw) {
+            pa = (int)prs.lemire(11u); // rng_pressing.choice(11)
+        } else {
+            pa = select_kth_bit(pbits, (int)prs.lemire((uint32_t)__popc(pbits))); // choice(flatnonzero(mask))
+        }
+        const int a = sm * 11 + pa;
+        // ---- the transition under that action, auto-reset on termination
+        float o[32];
+        StepResult r = env_step<3, NOISE, false>(e, P, tb, a, -1, step_flags, bales, kcur, o);
+        if (__builtin_expect(r.done != 0, 0)) {
+            auto_reset_env(e, P, tb, bales, kcur);
+            env_obs<3>(e, P, tb, kcur, o);
+        }
+        const uint32_t mbits = action_mask_bits<3>(e, P);
+        if (obs_out != nullptr) wave_store_rows_f32<D, ENVS>(ltile, lrow_obs, o, obs_out + srow * D, n_valid, lane);
+        if (mask_out != nullptr) wave_store_rows_mask<A, ENVS>(lwave, lrow_mask, mbits, mask_out + srow * A, n_valid, lane);
+        if (live) {
+            const long long at = (long long)s * P.n + i;
+            if (actions_out != nullptr) __builtin_nontemporal_store(a, &actions_out[at]);
+            if (reward_out != nullptr) __builtin_nontemporal_store((float)r.reward, &reward_out[at]);
+            if (done_out != nullptr) __builtin_nontemporal_store((uint8_t)r.done, &done_out[at]);
+        }
+    }
+    if (!PRESS_AG) {
+        e.press_uint = prs.uinteger; // store_env writes the 32-bit buffer with PL_MISC2
+        e.press_has = prs.has;
+    }
+    if (live) store_env<3, NOISE>(e, planes, P, i, false);
+    if (live && !SORT_AG) {
+        planes[(long long)PL_SORTRNG_STATE * P.n_pad + i] = pack_u64x2(srt.g.s_lo, srt.g.s_hi);
+        planes[(long long)PL_SORTRNG_AUX * P.n_pad + i] = make_uint4(srt.uinteger, (uint32_t)srt.has, 0, 0);
+    }
+    if (live && !PRESS_AG) planes[(long long)PL_PRESS_STATE * P.n_pad + i] = pack_u64x2(prs.g.s_lo, prs.g.s_hi);
+    if (P.track_bales && live) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
+    }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_reset(Params P, uint4 *__restrict__ planes,
                                                   const uint32_t *__restrict__ table_image,
@@ -2491,6 +2678,36 @@ static int launch_rollout_policy(mse_env *h, const mse_policy *pol, const mse_po
     return MSE_OK;
 }
 
+// mse_rollout_model's shape: k_rollout_policy's f16x3 one (eight waves per workgroup; a wave owns 32 envs while they
+// leave every CU at most one workgroup's worth, n <= 256 envs x CUs, else 64)
+static int launch_rollout_model(mse_env *h, const mse_policy *sort_ag, const mse_policy *press_ag, hipStream_t s,
+                                int k_steps, uint32_t flags, int32_t *actions, float *obs, float *rew, uint8_t *done,
+                                uint8_t *mask, float *sort_obs, float *press_obs)
+{
+    const int tiles = h->P.n <= (long long)256 * h->cus ? 1 : 2;
+    const int n_waves = 8;
+    const long long envs_per_wg = 32LL * tiles * n_waves;
+    const dim3 grid((unsigned)((h->P.n + envs_per_wg - 1) / envs_per_wg)), block((unsigned)(64 * n_waves));
+    const size_t wave_bytes = tiles == 1 ? PolLayout<3, 1>::wave_bytes : PolLayout<3, 2>::wave_bytes;
+    const size_t lds = (size_t)msep::kLdsFloats * 4u * 2u + (size_t)h->P.table_words * 4u + (size_t)n_waves * wave_bytes;
+    if (lds > (size_t)160 * 1024) return MSE_ERR_UNSUPPORTED_CONFIG;
+    const float *sort_blob = sort_ag != nullptr ? sort_ag->blob : nullptr;
+    const float *press_blob = press_ag != nullptr ? press_ag->blob : nullptr;
+#define MSE_LAUNCH_RM(NOISE, SA, PA, TILES)                                                                          \
+    hipLaunchKernelGGL((k_rollout_model<NOISE, SA, PA, TILES>), grid, block, lds, s, h->P, h->planes, h->tables,     \
+                       sort_blob, press_blob, k_steps, flags, actions, obs, rew, done, mask, sort_obs, press_obs)
+#define MSE_LAUNCH_RM_T(NOISE, SA, PA) do { if (tiles == 1) MSE_LAUNCH_RM(NOISE, SA, PA, 1); else MSE_LAUNCH_RM(NOISE, SA, PA, 2); } while (0)
+#define MSE_LAUNCH_RM_N(SA, PA) do { if (h->noise_on) MSE_LAUNCH_RM_T(true, SA, PA); else MSE_LAUNCH_RM_T(false, SA, PA); } while (0)
+    if (sort_ag != nullptr && press_ag != nullptr) MSE_LAUNCH_RM_N(true, true);
+    else if (sort_ag != nullptr) MSE_LAUNCH_RM_N(true, false);
+    else if (press_ag != nullptr) MSE_LAUNCH_RM_N(false, true);
+    else MSE_LAUNCH_RM_N(false, false);
+#undef MSE_LAUNCH_RM_N
+#undef MSE_LAUNCH_RM_T
+#undef MSE_LAUNCH_RM
+    return MSE_OK;
+}
+
 extern "C" {
 
 int mse_version(void) { return MSE_VERSION; }
@@ -2904,6 +3121,44 @@ int mse_rollout_policy(mse_env *h, mse_policy *pol, mse_policy *sort_pol, int32_
     default: rc = launch_rollout_policy<3>(h, pol, sort_pol, s, k_steps, seed, deterministic, sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out, reward_out, episode_start_out, last_value_out, last_done_out); break;
     }
     if (rc != MSE_OK) return fail(rc, "the policy rollout kernel's LDS image does not fit this config's tables");
+    MSE_CHECK_LAUNCH();
+    h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+int mse_rollout_model(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, int32_t k_steps, uint32_t flags,
+                      int32_t *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *mask_out,
+                      float *sort_obs_out, float *press_obs_out, void *stream)
+{
+    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "env is NULL");
+    if (h->P.env_kind != MSE_ENV_MONO)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mode='model' exists on Env_3_Monolith only (env_monolith.py:186)");
+    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_rollout_model before mse_reset(seeds)");
+    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
+    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_model needs auto_reset=1");
+    if (h->trace_rec != nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (flags & ~(MSE_STEP_UNMASKED | MSE_STEP_CHECK_OVERFLOW | MSE_MODEL_PRESS_AGENT_MASKED))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag");
+    if (sort_ag != nullptr && (sort_ag->d_in != 13 || sort_ag->n_act != 2))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "the sorting agent must be a 13 -> 2 policy");
+    if (press_ag != nullptr && (press_ag->d_in != 16 || press_ag->n_act != 11))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "the pressing agent must be a 16 -> 11 policy");
+    if ((sort_ag != nullptr && sort_ag->device != h->device) || (press_ag != nullptr && press_ag->device != h->device))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "agent and env live on different devices");
+    if ((obs_out && !aligned16(obs_out)) || (mask_out && !aligned16(mask_out)) || (sort_obs_out && !aligned16(sort_obs_out)) ||
+        (press_obs_out && !aligned16(press_obs_out)))
+        return fail(MSE_ERR_ALIGNMENT, "obs_out / mask_out / sort_obs_out / press_obs_out must be 16-byte aligned");
+    if ((sort_ag != nullptr && !sort_ag->use_f16()) || (press_ag != nullptr && !press_ag->use_f16()))
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the in-loop agents exist in the f16x3 form (mse_policy_set_precision)");
+    if (h->literal || h->P.gen_mode)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_model serves the integer draw path with a remainder-free batch "
+                                                "(literal_choice or general generator mode: alternate mse_sort_agent_obs / "
+                                                "mse_press_agent_obs, mse_policy_forward, mse_model_actions and mse_step, "
+                                                "as ModelRolloutCollector does)");
+    const int rc = launch_rollout_model(h, sort_ag, press_ag, static_cast<hipStream_t>(stream), k_steps, flags, actions_out,
+                                        obs_out, reward_out, done_out, mask_out, sort_obs_out, press_obs_out);
+    if (rc != MSE_OK) return fail(rc, "the model rollout kernel's LDS image does not fit this config's tables");
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
     return MSE_OK;

@@ -7,7 +7,17 @@ lane: one fused rollout per scenario (rule-based and masked-uniform policies run
 scenario steps with uniform actions over all 22).  Not a parity target (the reference's random mode draws from the
 global np.random); the rule-based run is, and tests/test_gpu_api.py checks it seed by seed against the reference.
 
-    python tools/benchmark_scenarios.py [--envs 65536]
+The scenarios with trained agents (utils/benchmark_models.py:152-172) run Env_3_Monolith.step(mode='model'): PPO Sort-Only
+(a sorting agent, the press part drawn from the env's rng_pressing), PPO Modular (sorting + pressing agent, with and
+without masking) - both as one fused rollout per 50 steps (BatchedSortingEnv.rollout(policy="model"), mse_rollout_model)
+- and PPO Monolith (FusedPolicyRollout, deterministic).  The agents are local `torch.save`d SB3 `policy.state_dict()`
+files (--sort-weights / --press-weights / --mono-weights); without one, random-init weights of the same architecture
+stand in, and the row says so: its number is not comparable to the paper.  "mode='model', no agents" is the env-stream
+random baseline.  --time prints env-steps/s of the fused model rollout against ModelRolloutCollector (one round of
+launches per step) for each agent combination at --envs envs and K = --k steps.
+
+    python tools/benchmark_scenarios.py [--envs 65536] [--sort-weights F] [--press-weights F] [--mono-weights F]
+    python tools/benchmark_scenarios.py --time [--envs 65536] [--k 200]
 """
 import argparse
 import os
@@ -21,6 +31,11 @@ import marl_sortingenv_amd as M  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=65536)
+ap.add_argument("--sort-weights", default=None, help="torch.save'd SB3 policy.state_dict() of the sorting agent (13 -> 2)")
+ap.add_argument("--press-weights", default=None, help="... of the pressing agent (16 -> 11)")
+ap.add_argument("--mono-weights", default=None, help="... of the monolithic agent (29 -> 22)")
+ap.add_argument("--time", action="store_true", help="env-steps/s of the fused model rollout vs ModelRolloutCollector")
+ap.add_argument("--k", type=int, default=200, help="steps per rollout for --time")
 args = ap.parse_args()
 n, T = args.envs, 200
 
@@ -47,6 +62,63 @@ def total_reward(env, policy, masked=True):
     return tot
 
 
+
+
+def agent(path, obs_dim, n_actions, seed):
+    """(MlpPolicy, label suffix): the state dict at `path`, else random-init weights with a fixed seed."""
+    if path:
+        return M.MlpPolicy.from_state_dict(torch.load(path, map_location="cpu"), device=0), ""
+    return M.MlpPolicy.random_init(obs_dim, n_actions, seed=seed), "  [random-init weights, not comparable to the paper]"
+
+
+def model_reward(env, sort_agent, press_agent, masked, maskable=True):
+    tot = torch.zeros((n,), dtype=torch.float64, device="cuda")
+    K = 50
+    buf = env.alloc_rollout(K, obs=False, mask=False)
+    for _ in range(T // K):
+        env.rollout(K, buffers=buf, policy="model", sort_agent=sort_agent, press_agent=press_agent,
+                    press_agent_maskable=maskable, use_action_masking=masked)
+        tot += buf["reward"].double().sum(dim=0)
+    return tot
+
+
+def mono_reward(env, policy, masked):
+    tot = torch.zeros((n,), dtype=torch.float64, device="cuda")
+    K = 50
+    coll = M.FusedPolicyRollout(env, policy, K)
+    for _ in range(T // K):
+        tot += coll.collect(deterministic=True, use_action_masking=masked)["rewards"].double().sum(dim=0)
+    return tot
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e-3
+
+
+if args.time:
+    K = args.k
+    sort_ag, _ = agent(args.sort_weights, 13, 2, 1)
+    press_ag, _ = agent(args.press_weights, 16, 11, 2)
+    for label, s_ag, p_ag in (("no agents", None, None), ("sorting agent", sort_ag, None),
+                              ("pressing agent (maskable)", None, press_ag), ("both agents (maskable)", sort_ag, press_ag)):
+        env = make()
+        buf = env.alloc_rollout(K, sort_obs=True, press_obs=True)
+        env.rollout(K, buffers=buf, policy="model", sort_agent=s_ag, press_agent=p_ag)  # warm-up
+        t_fused = timed(lambda: env.rollout(K, buffers=buf, policy="model", sort_agent=s_ag, press_agent=p_ag))
+        coll = M.ModelRolloutCollector(env, sort_agent=s_ag, press_agent=p_ag)
+        coll.collect(2, buffers=buf)  # warm-up
+        t_multi = timed(lambda: coll.collect(K, buffers=buf))
+        print(f"{label:28s} {n} envs, K={K}: fused {n * K / t_fused / 1e9:7.3f} G env-steps/s   "
+              f"ModelRolloutCollector {n * K / t_multi / 1e9:7.3f} G env-steps/s   ({t_multi / t_fused:6.1f}x)")
+        env.close()
+        del buf
+    sys.exit(0)
+
 for label, policy, masked, quoted in (
         ("Random, masking", "random", True, "-84.28 +- 22.29"),
         ("Rule-Based, masking", "rule_based", True, "44.03 +- 1.10"),
@@ -56,3 +128,17 @@ for label, policy, masked, quoted in (
           f"(reference, 10 seeds: {quoted})")
 print("Rule-Based, no masking   = the masked run: mode='rule_based' executes its action without validation whatever "
       "use_action_masking is (env_monolith.py:166-184, 262-264); the reference quotes 43.20 +- 1.07 for its second sample")
+
+r = model_reward(make(), None, None, True)
+print(f"{'mode=model, no agents':24s} {n} seeds: cumulative reward {float(r.mean()):8.2f} +- {float(r.std()):6.2f}   "
+      f"(rng_sorting / rng_pressing draws, masking)")
+sort_ag, sort_note = agent(args.sort_weights, 13, 2, 1)
+press_ag, press_note = agent(args.press_weights, 16, 11, 2)
+mono_ag, mono_note = agent(args.mono_weights, 29, 22, 3)
+for label, run, note in (
+        ("PPO Sort-Only", lambda: model_reward(make(), sort_ag, None, True), sort_note),
+        ("PPO Modular, masking", lambda: model_reward(make(), sort_ag, press_ag, True), sort_note or press_note),
+        ("PPO Modular, no masking", lambda: model_reward(make(), sort_ag, press_ag, False), sort_note or press_note),
+        ("PPO Monolith, masking", lambda: mono_reward(make(), mono_ag, True), mono_note)):
+    r = run()
+    print(f"{label:24s} {n} seeds: cumulative reward {float(r.mean()):8.2f} +- {float(r.std()):6.2f}{note}")
