@@ -4,6 +4,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared -Iinclude \
 //         marl-sortingenv_amd/csrc/mse_lib.hip -o marl-sortingenv_amd/libmse_hip.so
 #include "mse_device.h"
+#include "mse_plan.h"
 #include "mse_policy_device.h"
 
 #include "mse.h"
@@ -12,8 +13,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace mse;
@@ -2238,9 +2241,7 @@ struct mse_env {
     bool seeded;
     bool noise_on;
     bool literal;                // evaluate every Generator.choice draw in literal fp64
-    bool pipelined;              // mse_rollout uses the dynamics/observer kernel (k_rollout_po)
-    bool ring;                   // ... with RNG waves feeding an LDS ring (k_rollout_ring)
-    bool ring_ok;                // the config allows an LDS ring at all (draws per step, integer draw path, build)
+    RolloutKernel rollout;       // mse_rollout's kernel (plan_rollout, at create)
     uint64_t policy_t;
     // opt-in trace of one env (mse_trace_begin): records_dev f64[capacity][MSE_TRACE_COLS], caller-owned
     double *trace_rec;
@@ -2478,42 +2479,55 @@ static size_t lds_bytes_rollout(const mse_env *h)
     return (size_t)(h->noise_on ? RolloutLayout<KIND, true>::table_offset : RolloutLayout<KIND, false>::table_offset) +
            (size_t)(h->P.gen_mode ? h->P.table_words : h->P.off_jump) * 4u;
 }
+// the multi-role kernels' LDS: their layout's fixed part, then the whole table image
+template <class Layout>
+static size_t lds_with_tables(const Params &P)
+{
+    return (size_t)Layout::table_offset + (size_t)P.table_words * 4u;
+}
+template <int KIND>
+static PolicyLds policy_lds(const Params &P)
+{
+    return {lds_with_tables<PolRolesLayout<KIND, true>>(P), lds_with_tables<PolRolesLayout<KIND, false>>(P),
+            (size_t)msep::kLdsFloats * 4u, (size_t)P.table_words * 4u,
+            {PolLayout<KIND, 1>::wave_bytes, PolLayout<KIND, 2>::wave_bytes}};
+}
 
 static inline dim3 grid_of(const mse_env *h) { return dim3((unsigned)(h->P.n_pad / kBlock)); }
+
+// Runtime values as template arguments: with_kind(kind, f) calls f(Int<kind>{}) and with_flags(f, b...) calls
+// f(std::bool_constant<b>{}...), so that a launch names its kernel once.  Every combination is instantiated unless the
+// launch leaves it out with `if constexpr`.
+template <int V> using Int = std::integral_constant<int, V>;
+
+template <class F>
+static auto with_kind(int kind, F &&f)
+{
+    if (kind == MSE_ENV_SORT) return f(Int<1>{});
+    if (kind == MSE_ENV_PRESS) return f(Int<2>{});
+    return f(Int<3>{});
+}
+template <class F>
+static void with_flags(F &&f) { f(); }
+template <class F, class... B>
+static void with_flags(F &&f, bool b, B... rest)
+{
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 template <int KIND>
 static void launch_step(mse_env *h, hipStream_t s, const int32_t *action, const int32_t *sort_mode, uint32_t flags,
                         float *obs, float *rew, double *rew64, uint8_t *done, uint8_t *mask, float *tobs)
 {
-    const bool lit = h->literal;
-    const size_t lds = lds_bytes_step<KIND>(h);
-    if (h->trace_rec != nullptr) { // the traced variant: one more record for env trace_env
-        double *rec = h->trace_rec + h->trace_count * MSE_TRACE_COLS;
-#define MSE_LAUNCH_STEP_T(NOISE, LIT, GEN)                                                               \
-    hipLaunchKernelGGL((k_step<KIND, NOISE, LIT, true, GEN>), grid_of(h), dim3(kBlock), lds, s, h->P, h->planes, h->tables, \
-                       action, sort_mode, flags, obs, rew, rew64, done, mask, tobs, h->err_count, rec, (long long)h->trace_env)
-#define MSE_LAUNCH_STEP_TG(NOISE, LIT) do { if (h->P.gen_mode) MSE_LAUNCH_STEP_T(NOISE, LIT, true); else MSE_LAUNCH_STEP_T(NOISE, LIT, false); } while (0)
-        if (h->noise_on) {
-            if (lit) MSE_LAUNCH_STEP_TG(true, true); else MSE_LAUNCH_STEP_TG(true, false);
-        } else {
-            if (lit) MSE_LAUNCH_STEP_TG(false, true); else MSE_LAUNCH_STEP_TG(false, false);
-        }
-#undef MSE_LAUNCH_STEP_TG
-#undef MSE_LAUNCH_STEP_T
-        h->trace_count += 1;
-        return;
-    }
-#define MSE_LAUNCH_STEP(NOISE, LIT, GEN)                                                                 \
-    hipLaunchKernelGGL((k_step<KIND, NOISE, LIT, false, GEN>), grid_of(h), dim3(kBlock), lds, s, h->P, h->planes, h->tables, \
-                       action, sort_mode, flags, obs, rew, rew64, done, mask, tobs, h->err_count, (double *)nullptr, -1LL)
-#define MSE_LAUNCH_STEP_G(NOISE, LIT) do { if (h->P.gen_mode) MSE_LAUNCH_STEP(NOISE, LIT, true); else MSE_LAUNCH_STEP(NOISE, LIT, false); } while (0)
-    if (h->noise_on) {
-        if (lit) MSE_LAUNCH_STEP_G(true, true); else MSE_LAUNCH_STEP_G(true, false);
-    } else {
-        if (lit) MSE_LAUNCH_STEP_G(false, true); else MSE_LAUNCH_STEP_G(false, false);
-    }
-#undef MSE_LAUNCH_STEP_G
-#undef MSE_LAUNCH_STEP
+    const bool traced = h->trace_rec != nullptr; // the traced variant: one more record for env trace_env
+    double *rec = traced ? h->trace_rec + h->trace_count * MSE_TRACE_COLS : nullptr;
+    with_flags([&](auto NOISE, auto LIT, auto TRACE, auto GEN) {
+        hipLaunchKernelGGL((k_step<KIND, NOISE, LIT, TRACE, GEN>), grid_of(h), dim3(kBlock), lds_bytes_step<KIND>(h), s,
+                           h->P, h->planes, h->tables, action, sort_mode, flags, obs, rew, rew64, done, mask, tobs,
+                           h->err_count, rec, traced ? (long long)h->trace_env : -1LL);
+    }, h->noise_on, h->literal, traced, h->P.gen_mode != 0);
+    if (traced) h->trace_count += 1;
 }
 
 // RngRing::load masks an output's row into the lane's LDS address, which needs the ring on a 64 KiB LDS boundary:
@@ -2522,22 +2536,22 @@ static void launch_step(mse_env *h, hipStream_t s, const int32_t *action, const 
 // in the kernel.
 static bool ring_kernels_static_lds_free()
 {
-    static int cached = -1;
-    if (cached < 0) {
+    static const bool lds_free = [] {
         const void *fns[] = {(const void *)k_rollout_ring<1, false>, (const void *)k_rollout_ring<1, true>,
                              (const void *)k_rollout_ring<2, false>, (const void *)k_rollout_ring<2, true>,
                              (const void *)k_rollout_ring<3, false>, (const void *)k_rollout_ring<3, true>,
                              (const void *)k_rollout_policy_roles<1, false, true>, (const void *)k_rollout_policy_roles<1, true, true>,
                              (const void *)k_rollout_policy_roles<2, false, true>, (const void *)k_rollout_policy_roles<2, true, true>,
                              (const void *)k_rollout_policy_roles<3, false, true>, (const void *)k_rollout_policy_roles<3, true, true>};
-        cached = 1;
         for (const void *f : fns) {
             hipFuncAttributes a{};
-            if (hipFuncGetAttributes(&a, f) != hipSuccess || a.sharedSizeBytes != 0) cached = 0;
+            if (hipFuncGetAttributes(&a, f) != hipSuccess || a.sharedSizeBytes != 0) return false;
         }
-    }
-    return cached == 1;
+        return true;
+    }();
+    return lds_free;
 }
+static_assert(kPlanRingMaxPerStep == kRingMaxPerStep && kRoundEnvs == kPoEnvs, "mse_plan.h restates these");
 
 // Params::ring_fwd: s_{n+d} = M^d s_n + (1 + M + ... + M^{d-1}) inc for d = ring_worst, the distance between the two
 // halves of the ring's priming (k_rollout_ring)
@@ -2560,51 +2574,28 @@ template <int KIND>
 static void launch_rollout(mse_env *h, hipStream_t s, int k_steps, uint64_t policy_seed, const int32_t *sort_mode,
                            uint32_t flags, int32_t *actions, float *obs, float *rew, uint8_t *done, uint8_t *mask)
 {
-    const bool lit = h->literal;
-    if (h->ring) {
-        const dim3 grid((unsigned)(h->P.n_pad / kPoEnvs));
-        const size_t table_bytes = (size_t)h->P.table_words * 4u;
-        const size_t lds_n = (size_t)RingLayout<KIND, true>::table_offset + table_bytes;
-        const size_t lds_p = (size_t)RingLayout<KIND, false>::table_offset + table_bytes;
-        if (h->noise_on)
-            hipLaunchKernelGGL((k_rollout_ring<KIND, true>), grid, dim3(kRingThreads), lds_n, s, h->P, h->planes,
+    const dim3 grid_wg((unsigned)(h->P.n_pad / kPoEnvs)); // the multi-role kernels: one workgroup per 256 envs
+    if (h->rollout == RolloutKernel::Ring) {
+        with_flags([&](auto NOISE) {
+            const size_t lds = lds_with_tables<RingLayout<KIND, NOISE>>(h->P);
+            hipLaunchKernelGGL((k_rollout_ring<KIND, NOISE>), grid_wg, dim3(kRingThreads), lds, s, h->P, h->planes,
                                h->tables, k_steps, policy_seed, h->policy_t, sort_mode, flags, actions, obs, rew, done,
                                mask);
-        else
-            hipLaunchKernelGGL((k_rollout_ring<KIND, false>), grid, dim3(kRingThreads), lds_p, s, h->P, h->planes,
+        }, h->noise_on);
+    } else if (h->rollout == RolloutKernel::TwoRole) {
+        with_flags([&](auto NOISE, auto LIT) {
+            const size_t lds = lds_with_tables<PoLayout<KIND, NOISE>>(h->P);
+            hipLaunchKernelGGL((k_rollout_po<KIND, NOISE, LIT>), grid_wg, dim3(kPoThreads), lds, s, h->P, h->planes,
                                h->tables, k_steps, policy_seed, h->policy_t, sort_mode, flags, actions, obs, rew, done,
                                mask);
-        return;
-    }
-    if (h->pipelined) {
-        const dim3 grid((unsigned)(h->P.n_pad / kPoEnvs));
-        const size_t table_bytes = (size_t)h->P.table_words * 4u;
-        const size_t lds_noise = (size_t)PoLayout<KIND, true>::table_offset + table_bytes;
-        const size_t lds_plain = (size_t)PoLayout<KIND, false>::table_offset + table_bytes;
-#define MSE_LAUNCH_PO(NOISE, LIT)                                                                        \
-    hipLaunchKernelGGL((k_rollout_po<KIND, NOISE, LIT>), grid, dim3(kPoThreads), (NOISE ? lds_noise : lds_plain), s, \
-                       h->P, h->planes, h->tables, k_steps, policy_seed, h->policy_t, sort_mode, flags, actions, obs, \
-                       rew, done, mask)
-        if (h->noise_on) {
-            if (lit) MSE_LAUNCH_PO(true, true); else MSE_LAUNCH_PO(true, false);
-        } else {
-            if (lit) MSE_LAUNCH_PO(false, true); else MSE_LAUNCH_PO(false, false);
-        }
-#undef MSE_LAUNCH_PO
-        return;
-    }
-    const size_t lds = lds_bytes_rollout<KIND>(h);
-#define MSE_LAUNCH_ROLLOUT(NOISE, LIT, GEN)                                                              \
-    hipLaunchKernelGGL((k_rollout<KIND, NOISE, LIT, GEN>), grid_of(h), dim3(kBlock), lds, s, h->P, h->planes, h->tables, \
-                       k_steps, policy_seed, h->policy_t, sort_mode, flags, actions, obs, rew, done, mask)
-#define MSE_LAUNCH_ROLLOUT_G(NOISE, LIT) do { if (h->P.gen_mode) MSE_LAUNCH_ROLLOUT(NOISE, LIT, true); else MSE_LAUNCH_ROLLOUT(NOISE, LIT, false); } while (0)
-    if (h->noise_on) {
-        if (lit) MSE_LAUNCH_ROLLOUT_G(true, true); else MSE_LAUNCH_ROLLOUT_G(true, false);
+        }, h->noise_on, h->literal);
     } else {
-        if (lit) MSE_LAUNCH_ROLLOUT_G(false, true); else MSE_LAUNCH_ROLLOUT_G(false, false);
+        with_flags([&](auto NOISE, auto LIT, auto GEN) {
+            hipLaunchKernelGGL((k_rollout<KIND, NOISE, LIT, GEN>), grid_of(h), dim3(kBlock), lds_bytes_rollout<KIND>(h), s,
+                               h->P, h->planes, h->tables, k_steps, policy_seed, h->policy_t, sort_mode, flags, actions,
+                               obs, rew, done, mask);
+        }, h->noise_on, h->literal, h->P.gen_mode != 0);
     }
-#undef MSE_LAUNCH_ROLLOUT_G
-#undef MSE_LAUNCH_ROLLOUT
 }
 
 template <int KIND>
@@ -2613,98 +2604,59 @@ static int launch_rollout_policy(mse_env *h, const mse_policy *pol, const mse_po
                                  int32_t *actions, float *logp, float *value, float *rew, uint8_t *start,
                                  float *last_value, uint8_t *last_done)
 {
-    // Shape: eight waves per workgroup, two per SIMD.  While 32-env waves leave every CU at most one workgroup's worth
-    // (n <= 256 envs x CUs) a wave owns 32 envs - at that size 64-env waves would run one per SIMD, at a vector
-    // instruction per ~5 cycles; beyond, 64 envs.  The exact-f32 form only exists in the 64-env shape.
-    const int cus = h->cus; // queried once at create: hipGetDeviceProperties is far too slow for a launch path
-    const bool f16 = pol->use_f16();
-    // Batches that leave a SIMD 64 envs (n <= 256 envs x CUs), f16x3 form, no in-loop sorting policy: the two-role
-    // kernel in roles (one workgroup of four actor / critic[ / RNG] wave sets per 256 envs).  rollout_pipeline = 2 ("one
-    // lane per env, no roles") keeps the plain kernel and 1 ("two roles") the form without the RNG waves, which is how the
-    // tests hold the three against each other.
-    if (f16 && sort_pol == nullptr && h->P.n <= (long long)256 * cus && h->cfg.rollout_pipeline != 2) {
-        const size_t table_bytes = (size_t)h->P.table_words * 4u;
-        const size_t lds_ring = (size_t)PolRolesLayout<KIND, true>::table_offset + table_bytes;
-        const size_t lds_pair = (size_t)PolRolesLayout<KIND, false>::table_offset + table_bytes;
-        const bool with_ring = h->ring_ok && lds_ring <= (size_t)160 * 1024 && h->cfg.rollout_pipeline != 1;
-        if (with_ring || lds_pair <= (size_t)160 * 1024) {
-            const dim3 grid_r((unsigned)((h->P.n + kPoEnvs - 1) / kPoEnvs));
-#define MSE_LAUNCH_RPR(NOISE, RING)                                                                                  \
-    hipLaunchKernelGGL((k_rollout_policy_roles<KIND, NOISE, RING>), grid_r, dim3((unsigned)PolRolesLayout<KIND, RING>::kThreads), \
-                       (RING ? lds_ring : lds_pair), s, h->P, h->planes, h->tables, pol->blob, k_steps, seed, h->policy_t,   \
-                       deterministic, sort_mode, flags, obs, mask, actions, logp, value, rew, start, last_value, last_done)
-            if (with_ring) {
-                if (h->noise_on) MSE_LAUNCH_RPR(true, true); else MSE_LAUNCH_RPR(false, true);
-            } else {
-                if (h->noise_on) MSE_LAUNCH_RPR(true, false); else MSE_LAUNCH_RPR(false, false);
-            }
-#undef MSE_LAUNCH_RPR
-            return MSE_OK;
-        }
-    }
-    const int tiles = (f16 && h->P.n <= (long long)256 * cus) ? 1 : 2;
-    // (the exact-f32 form below that size: four 64-env waves per workgroup, so that every CU gets one)
-    const int n_waves = (!f16 && h->P.n <= (long long)256 * cus) ? 4 : 8;
-    const long long envs_per_wg = 32LL * tiles * n_waves;
-    const dim3 grid((unsigned)((h->P.n + envs_per_wg - 1) / envs_per_wg)), block((unsigned)(64 * n_waves));
-    const size_t wave_bytes = tiles == 1 ? PolLayout<KIND, 1>::wave_bytes : PolLayout<KIND, 2>::wave_bytes;
-    const size_t lds = (size_t)msep::kLdsFloats * 4u * (sort_pol ? 2u : 1u) + (size_t)h->P.table_words * 4u + (size_t)n_waves * wave_bytes;
-    if (lds > (size_t)160 * 1024) return MSE_ERR_UNSUPPORTED_CONFIG;
-    if (KIND == 2 && sort_pol != nullptr) { // Env_2 with its sorting agent in the loop (f16x3 form of both networks)
-#define MSE_LAUNCH_RPS(NOISE, TILES)                                                                                 \
-    hipLaunchKernelGGL((k_rollout_policy<2, NOISE, TILES, true, true>), grid, block, lds, s, h->P, h->planes, h->tables, \
-                       pol->blob, sort_pol->blob, k_steps, seed, h->policy_t, deterministic, sort_mode, flags, obs, mask, \
-                       actions, logp, value, rew, start, last_value, last_done)
-        if (tiles == 1) {
-            if (h->noise_on) MSE_LAUNCH_RPS(true, 1); else MSE_LAUNCH_RPS(false, 1);
-        } else {
-            if (h->noise_on) MSE_LAUNCH_RPS(true, 2); else MSE_LAUNCH_RPS(false, 2);
-        }
-#undef MSE_LAUNCH_RPS
+    // h->cus: queried once at create (hipGetDeviceProperties is far too slow for a launch path)
+    const PolicyPlan plan = plan_rollout_policy(h->cfg.rollout_pipeline, h->P.n, h->cus, pol->use_f16(), sort_pol != nullptr,
+                                                h->P.ring_worst, h->literal, h->P.gen_mode != 0,
+                                                ring_kernels_static_lds_free(), policy_lds<KIND>(h->P));
+    if (plan.status != MSE_OK) return plan.status;
+    const dim3 grid((unsigned)plan.workgroups);
+    if (plan.kernel != PolicyKernel::Plain) {
+        with_flags([&](auto NOISE, auto RING) {
+            hipLaunchKernelGGL((k_rollout_policy_roles<KIND, NOISE, RING>), grid, dim3((unsigned)PolRolesLayout<KIND, RING>::kThreads),
+                               plan.lds_bytes, s, h->P, h->planes, h->tables, pol->blob, k_steps, seed, h->policy_t,
+                               deterministic, sort_mode, flags, obs, mask, actions, logp, value, rew, start, last_value,
+                               last_done);
+        }, h->noise_on, plan.kernel == PolicyKernel::RolesRing);
         return MSE_OK;
     }
-#define MSE_LAUNCH_RP(NOISE, TILES, F16)                                                                             \
-    hipLaunchKernelGGL((k_rollout_policy<KIND, NOISE, TILES, F16>), grid, block, lds, s, h->P, h->planes, h->tables, \
-                       pol->blob, (const float *)nullptr, k_steps, seed, h->policy_t, deterministic, sort_mode, flags, obs, \
-                       mask, actions, logp, value, rew, start, last_value, last_done)
-    if (!f16) {
-        if (h->noise_on) MSE_LAUNCH_RP(true, 2, false); else MSE_LAUNCH_RP(false, 2, false);
-    } else if (tiles == 1) {
-        if (h->noise_on) MSE_LAUNCH_RP(true, 1, true); else MSE_LAUNCH_RP(false, 1, true);
-    } else {
-        if (h->noise_on) MSE_LAUNCH_RP(true, 2, true); else MSE_LAUNCH_RP(false, 2, true);
-    }
-#undef MSE_LAUNCH_RP
+    const float *sort_blob = sort_pol != nullptr ? sort_pol->blob : nullptr;
+    with_flags([&](auto NOISE, auto ONE_TILE, auto F16, auto SORTPOL) {
+        // the forms the plan gives: exact f32 in two tiles only, an in-loop sorting policy (f16x3) on Env_2 only
+        if constexpr ((F16 || !ONE_TILE) && (!SORTPOL || (F16 && KIND == 2)))
+            hipLaunchKernelGGL((k_rollout_policy<KIND, NOISE, ONE_TILE ? 1 : 2, F16, SORTPOL>), grid,
+                               dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables,
+                               pol->blob, sort_blob, k_steps, seed, h->policy_t, deterministic, sort_mode, flags, obs,
+                               mask, actions, logp, value, rew, start, last_value, last_done);
+    }, h->noise_on, plan.tiles == 1, pol->use_f16(), sort_pol != nullptr);
     return MSE_OK;
 }
 
-// mse_rollout_model's shape: k_rollout_policy's f16x3 one (eight waves per workgroup; a wave owns 32 envs while they
-// leave every CU at most one workgroup's worth, n <= 256 envs x CUs, else 64)
+// mse_rollout_model's shape: k_rollout_policy's f16x3 one with two networks (plan_policy_plain)
 static int launch_rollout_model(mse_env *h, const mse_policy *sort_ag, const mse_policy *press_ag, hipStream_t s,
                                 int k_steps, uint32_t flags, int32_t *actions, float *obs, float *rew, uint8_t *done,
                                 uint8_t *mask, float *sort_obs, float *press_obs)
 {
-    const int tiles = h->P.n <= (long long)256 * h->cus ? 1 : 2;
-    const int n_waves = 8;
-    const long long envs_per_wg = 32LL * tiles * n_waves;
-    const dim3 grid((unsigned)((h->P.n + envs_per_wg - 1) / envs_per_wg)), block((unsigned)(64 * n_waves));
-    const size_t wave_bytes = tiles == 1 ? PolLayout<3, 1>::wave_bytes : PolLayout<3, 2>::wave_bytes;
-    const size_t lds = (size_t)msep::kLdsFloats * 4u * 2u + (size_t)h->P.table_words * 4u + (size_t)n_waves * wave_bytes;
-    if (lds > (size_t)160 * 1024) return MSE_ERR_UNSUPPORTED_CONFIG;
+    const PolicyPlan plan = plan_policy_plain(h->P.n, h->cus, true, 2, policy_lds<3>(h->P));
+    if (plan.status != MSE_OK) return plan.status;
     const float *sort_blob = sort_ag != nullptr ? sort_ag->blob : nullptr;
     const float *press_blob = press_ag != nullptr ? press_ag->blob : nullptr;
-#define MSE_LAUNCH_RM(NOISE, SA, PA, TILES)                                                                          \
-    hipLaunchKernelGGL((k_rollout_model<NOISE, SA, PA, TILES>), grid, block, lds, s, h->P, h->planes, h->tables,     \
-                       sort_blob, press_blob, k_steps, flags, actions, obs, rew, done, mask, sort_obs, press_obs)
-#define MSE_LAUNCH_RM_T(NOISE, SA, PA) do { if (tiles == 1) MSE_LAUNCH_RM(NOISE, SA, PA, 1); else MSE_LAUNCH_RM(NOISE, SA, PA, 2); } while (0)
-#define MSE_LAUNCH_RM_N(SA, PA) do { if (h->noise_on) MSE_LAUNCH_RM_T(true, SA, PA); else MSE_LAUNCH_RM_T(false, SA, PA); } while (0)
-    if (sort_ag != nullptr && press_ag != nullptr) MSE_LAUNCH_RM_N(true, true);
-    else if (sort_ag != nullptr) MSE_LAUNCH_RM_N(true, false);
-    else if (press_ag != nullptr) MSE_LAUNCH_RM_N(false, true);
-    else MSE_LAUNCH_RM_N(false, false);
-#undef MSE_LAUNCH_RM_N
-#undef MSE_LAUNCH_RM_T
-#undef MSE_LAUNCH_RM
+    with_flags([&](auto NOISE, auto SA, auto PA, auto ONE_TILE) {
+        hipLaunchKernelGGL((k_rollout_model<NOISE, SA, PA, ONE_TILE ? 1 : 2>), dim3((unsigned)plan.workgroups),
+                           dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables, sort_blob,
+                           press_blob, k_steps, flags, actions, obs, rew, done, mask, sort_obs, press_obs);
+    }, h->noise_on, sort_ag != nullptr, press_ag != nullptr, plan.tiles == 1);
+    return MSE_OK;
+}
+
+// the checks the three rollout entry points share (`fn` names the entry point in the messages)
+static int rollout_checks(const mse_env *h, int32_t k_steps, const char *fn)
+{
+    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "env is NULL");
+    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, std::string(fn) + " before mse_reset(seeds)");
+    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
+    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, std::string(fn) + " needs auto_reset=1");
+    if (h->trace_rec != nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
     return MSE_OK;
 }
 
@@ -2828,15 +2780,12 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     if (device_id < 0 || device_id >= n_dev) return fail(MSE_ERR_NO_DEVICE, "device_id out of range");
     MSE_HIP(hipSetDevice(device_id));
 
-    mse_env *h = new (std::nothrow) mse_env(); // value-initialised: device pointers start out null
+    // value-initialised: device pointers start out null, and an early return frees what exists
+    std::unique_ptr<mse_env, int (*)(mse_env *)> h(new (std::nothrow) mse_env(), mse_destroy);
     if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "out of host memory");
     h->cfg = *cfg;
     h->device = device_id;
-    h->seeded = false;
-    h->policy_t = 0;
-    h->trace_rec = nullptr;
     h->trace_env = -1;
-    h->trace_capacity = h->trace_count = 0;
     h->noise_on = cfg->noise != 0.0;
     Params &P = h->P;
     std::memset(&P, 0, sizeof(P));
@@ -2854,7 +2803,6 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     P.press_time[0] = P.press_time0 = cfg->press_time[0];
     P.press_time[1] = P.press_time1 = cfg->press_time[1];
     P.inv_balesize = 1.0f / (float)cfg->bale_standard_size;
-    for (int w = 0; w < 4; ++w) P.qi_down[w] = 0;
     for (int q = 0; q <= 100; ++q) { // env_super.py:664-666 with the literal expressions
         const double qd = (double)q / 100.0;
         const int qi = (int)(qd * 100.0);
@@ -2872,16 +2820,9 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     std::vector<uint32_t> image;
     std::string why;
     int trc = build_tables(*cfg, P, image, why);
-    if (trc != MSE_OK) {
-        delete h;
-        return fail(trc, why);
-    }
+    if (trc != MSE_OK) return fail(trc, why);
     // the byte-packed integer draw needs every prefix sum below 128; larger batches draw in literal fp64
     h->literal = cfg->literal_choice != 0 || cfg->input_batch_size > 127;
-    // rollout kernel: the multi-role kernels serve 256 envs per workgroup, one workgroup per CU (their LDS image is
-    // the whole CU's), so they pay off exactly while the batch fits the chip in one round: n <= 256 x CUs (65 536 on
-    // an MI355X).  Beyond that a one-lane-per-env grid already gives every SIMD several waves and wins (measured at
-    // 131 072 envs: 16.5 G env-steps/s against 15.9).  0 = decide by size, 1 / 3 = always, 2 = never
     int cus = 256;
     {
         hipDeviceProp_t prop;
@@ -2889,93 +2830,34 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
             cus = prop.multiProcessorCount;
     }
     h->cus = cus;
-    // ... and again while it fills most of a SECOND round: same-box at 64 steps per launch, three-role kernel against
-    // one lane per env: 98 304 envs 17.5 G against 15.5, 131 072 envs 22.9 against 20.5 (two full rounds run at the
-    // one-round rate; the one-lane grid has only two waves per SIMD there), 196 608 envs 23.1 against 23.8
-    const int64_t n_wg = (n_envs + kPoEnvs - 1) / kPoEnvs;
-    const bool by_size = n_wg <= cus || (n_wg > cus + cus / 4 && n_wg <= 2 * (int64_t)cus);
-    h->pipelined = cfg->rollout_pipeline == 1 || cfg->rollout_pipeline == 3 || (cfg->rollout_pipeline == 0 && by_size);
-    if (P.gen_mode) { // general generator mode: the multi-role kernels carry stage ids, not counts
-        if (cfg->rollout_pipeline == 1 || cfg->rollout_pipeline == 3) {
-            delete h;
-            return fail(MSE_ERR_UNSUPPORTED_CONFIG, "rollout_pipeline 1 / 3 need a remainder-free input_batch_size (the "
-                                                    "one-lane kernels serve the general generator)");
-        }
-        h->pipelined = false;
+    for (int m = 0; m < 4; ++m) { // the lowest accuracy each belt can have: clip(baseline [+ boost] - noise)
+        const double lo = cfg->baseline_accuracy[m] - cfg->noise, hi = cfg->baseline_accuracy[m] + cfg->boost - cfg->noise;
+        const double lo_c = lo < 0.0 ? 0.0 : (lo > 1.0 ? 1.0 : lo), hi_c = hi < 0.0 ? 0.0 : (hi > 1.0 ? 1.0 : hi);
+        P.acc_floor[m] = lo_c < hi_c ? lo_c : hi_c;
     }
-    {
-        // draws per step are bounded by the mis-sorted units of the two stations a mode leaves unboosted at the
-        // lowest accuracy the noise allows; the ring kernel needs that bound <= kRingMaxPerStep
-        // false_m = target - rint(target * acc) grows with target (<= the pattern's count) and falls with acc
-        // (>= clip(baseline [+ boost] - noise)); modes other than 0 / 1 (no boost) exist only for Env_2's
-        // externally supplied sorting decision
-        int worst = 0;
-        for (int m = 0; m < 4; ++m) {
-            const double lo = cfg->baseline_accuracy[m] - cfg->noise, hi = cfg->baseline_accuracy[m] + cfg->boost - cfg->noise;
-            const double lo_c = lo < 0.0 ? 0.0 : (lo > 1.0 ? 1.0 : lo), hi_c = hi < 0.0 ? 0.0 : (hi > 1.0 ? 1.0 : hi);
-            P.acc_floor[m] = lo_c < hi_c ? lo_c : hi_c;
-        }
-        const int n_modes = cfg->env_kind == MSE_ENV_PRESS ? 3 : 2;
-        for (int k = 1; k <= 2; ++k) {
-            for (int mode = 0; mode < n_modes; ++mode) {
-                int sum = 0;
-                for (int m = 0; m < 4; ++m) {
-                    const bool boosted = mode == 0 ? (m == 0 || m == 2) : (mode == 1 ? (m == 1 || m == 3) : false);
-                    double acc = cfg->baseline_accuracy[m] + (boosted ? cfg->boost : 0.0) - cfg->noise;
-                    acc = acc < 0.0 ? 0.0 : (acc > 1.0 ? 1.0 : acc);
-                    const int cnt = (int)((P.pat_word[k] >> (8 * m)) & 0xFFu);
-                    sum += cnt - (int)std::nearbyint((double)cnt * acc);
-                }
-                worst = sum > worst ? sum : worst;
-            }
-        }
-        // ... and its LDS image (ring, obs tile, two snapshots, bale ledger, tables) within the CU's 160 KiB
-        size_t ring_lds = (size_t)P.table_words * 4u;
-        const bool nz = h->noise_on;
-        if (cfg->env_kind == MSE_ENV_SORT) ring_lds += nz ? RingLayout<1, true>::table_offset : RingLayout<1, false>::table_offset;
-        else if (cfg->env_kind == MSE_ENV_PRESS) ring_lds += nz ? RingLayout<2, true>::table_offset : RingLayout<2, false>::table_offset;
-        else ring_lds += nz ? RingLayout<3, true>::table_offset : RingLayout<3, false>::table_offset;
-        P.ring_worst = worst;
-        set_ring_forward_jump(P);
-        h->ring_ok = worst <= kRingMaxPerStep && !h->literal && !P.gen_mode && ring_kernels_static_lds_free();
-        const bool fits = worst <= kRingMaxPerStep && !h->literal && ring_lds <= (size_t)160 * 1024 && ring_kernels_static_lds_free();
-        // (the second-round rule above was measured with the three-role kernel only)
-        if (cfg->rollout_pipeline == 0 && n_wg > cus && !fits) h->pipelined = false;
-        h->ring = h->pipelined && fits && cfg->rollout_pipeline != 1;
-        if (cfg->rollout_pipeline == 3 && !fits) {
-            delete h; // nothing is allocated on the device yet
-            return fail(MSE_ERR_UNSUPPORTED_CONFIG, "rollout_pipeline=3 (ring kernel) needs at most 31 draws per step, "
-                                                    "the integer draw path and an LDS image within 160 KiB");
-        }
-    }
+    P.ring_worst = max_draws_per_step(cfg->baseline_accuracy, cfg->boost, cfg->noise, P.pat_word, cfg->env_kind);
+    set_ring_forward_jump(P);
+    const size_t ring_lds = with_kind(P.env_kind, [&](auto KIND) {
+        return h->noise_on ? lds_with_tables<RingLayout<KIND, true>>(P) : lds_with_tables<RingLayout<KIND, false>>(P);
+    });
+    const RolloutPlan plan = plan_rollout(cfg->rollout_pipeline, n_envs, cus, h->literal, P.gen_mode != 0, P.ring_worst,
+                                          ring_lds, ring_kernels_static_lds_free());
+    if (plan.status != MSE_OK) return fail(plan.status, plan.why); // nothing is allocated on the device yet
+    h->rollout = plan.kernel;
 
     size_t bytes = (size_t)PL_COUNT * (size_t)P.n_pad * sizeof(uint4);
     hipError_t e1 = hipMalloc(reinterpret_cast<void **>(&h->planes), bytes);
-    if (e1 != hipSuccess) {
-        delete h;
-        return fail(MSE_ERR_HIP, std::string("hipMalloc(state planes): ") + hipGetErrorString(e1));
-    }
+    if (e1 != hipSuccess) return fail(MSE_ERR_HIP, std::string("hipMalloc(state planes): ") + hipGetErrorString(e1));
     hipError_t e2 = hipMalloc(reinterpret_cast<void **>(&h->err_count), sizeof(unsigned long long));
-    if (e2 != hipSuccess) {
-        (void)hipFree(h->planes);
-        delete h;
-        return fail(MSE_ERR_HIP, std::string("hipMalloc(err_count): ") + hipGetErrorString(e2));
-    }
+    if (e2 != hipSuccess) return fail(MSE_ERR_HIP, std::string("hipMalloc(err_count): ") + hipGetErrorString(e2));
     hipError_t e3 = hipMalloc(reinterpret_cast<void **>(&h->tables), image.size() * sizeof(uint32_t));
-    if (e3 != hipSuccess) {
-        (void)hipFree(h->planes);
-        (void)hipFree(h->err_count);
-        delete h;
-        return fail(MSE_ERR_HIP, std::string("hipMalloc(tables): ") + hipGetErrorString(e3));
-    }
+    if (e3 != hipSuccess) return fail(MSE_ERR_HIP, std::string("hipMalloc(tables): ") + hipGetErrorString(e3));
     hipError_t e4 = hipMemcpy(h->tables, image.data(), image.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
     if (e4 == hipSuccess) e4 = hipMemset(h->planes, 0, bytes);
     if (e4 == hipSuccess) e4 = hipMemset(h->err_count, 0, sizeof(unsigned long long));
-    if (e4 != hipSuccess) {
-        (void)mse_destroy(h);
+    if (e4 != hipSuccess)
         return fail(MSE_ERR_HIP, std::string("initialising the state planes / tables: ") + hipGetErrorString(e4));
-    }
-    *out = h;
+    *out = h.release();
     return MSE_OK;
 }
 
@@ -3020,12 +2902,10 @@ int mse_reset(mse_env *h, const uint64_t *seeds, const uint8_t *which, float *ob
         return fail(MSE_ERR_NOT_RESET, "the first mse_reset must carry seeds (the streams are not seeded yet)");
     if (seeds && which && !h->seeded)
         return fail(MSE_ERR_NOT_RESET, "the first mse_reset must seed every env (which_dev must be NULL)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (h->P.env_kind) {
-    case 1: hipLaunchKernelGGL(k_reset<1>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, seeds, which, obs_out, mask_out); break;
-    case 2: hipLaunchKernelGGL(k_reset<2>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, seeds, which, obs_out, mask_out); break;
-    default: hipLaunchKernelGGL(k_reset<3>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, seeds, which, obs_out, mask_out); break;
-    }
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        hipLaunchKernelGGL(k_reset<KIND>, grid_of(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->P, h->planes,
+                           h->tables, seeds, which, obs_out, mask_out);
+    });
     MSE_CHECK_LAUNCH();
     if (seeds) h->seeded = true;
     return MSE_OK;
@@ -3047,12 +2927,10 @@ int mse_step(mse_env *h, const int32_t *action, const int32_t *sort_mode, uint32
         return fail(MSE_ERR_ALIGNMENT, "obs_out / mask_out must be 16-byte aligned");
     if (h->trace_rec != nullptr && h->trace_count >= h->trace_capacity)
         return fail(MSE_ERR_INVALID_ARGUMENT, "the trace buffer is full: mse_trace_end, or begin a trace with more capacity");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (h->P.env_kind) {
-    case 1: launch_step<1>(h, s, action, sort_mode, flags, obs_out, reward_out, reward64_out, done_out, mask_out, terminal_obs_out); break;
-    case 2: launch_step<2>(h, s, action, sort_mode, flags, obs_out, reward_out, reward64_out, done_out, mask_out, terminal_obs_out); break;
-    default: launch_step<3>(h, s, action, sort_mode, flags, obs_out, reward_out, reward64_out, done_out, mask_out, terminal_obs_out); break;
-    }
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        launch_step<KIND>(h, static_cast<hipStream_t>(stream), action, sort_mode, flags, obs_out, reward_out, reward64_out,
+                          done_out, mask_out, terminal_obs_out);
+    });
     MSE_CHECK_LAUNCH();
     h->policy_t += 1;
     return MSE_OK;
@@ -3063,22 +2941,15 @@ int mse_rollout(mse_env *h, int32_t k_steps, uint64_t policy_seed, const int32_t
                 int32_t *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *mask_out,
                 void *stream)
 {
-    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "env is NULL");
-    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_rollout before mse_reset(seeds)");
-    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
-    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout needs auto_reset=1");
-    if (h->trace_rec != nullptr)
-        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (const int rc = rollout_checks(h, k_steps, "mse_rollout")) return rc;
     if (flags & ~(MSE_STEP_UNMASKED | MSE_STEP_CHECK_OVERFLOW | MSE_ROLLOUT_RULE_BASED | MSE_STEP_SANITIZE_LATE))
         return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag");
     if ((flags & MSE_STEP_SANITIZE_LATE) && (h->P.env_kind != MSE_ENV_MONO || !(flags & MSE_STEP_UNMASKED)))
         return fail(MSE_ERR_INVALID_ARGUMENT, "MSE_STEP_SANITIZE_LATE applies to Env_3 with MSE_STEP_UNMASKED only");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (h->P.env_kind) {
-    case 1: launch_rollout<1>(h, s, k_steps, policy_seed, sort_mode, flags, actions_out, obs_out, reward_out, done_out, mask_out); break;
-    case 2: launch_rollout<2>(h, s, k_steps, policy_seed, sort_mode, flags, actions_out, obs_out, reward_out, done_out, mask_out); break;
-    default: launch_rollout<3>(h, s, k_steps, policy_seed, sort_mode, flags, actions_out, obs_out, reward_out, done_out, mask_out); break;
-    }
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        launch_rollout<KIND>(h, static_cast<hipStream_t>(stream), k_steps, policy_seed, sort_mode, flags, actions_out,
+                             obs_out, reward_out, done_out, mask_out);
+    });
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
     return MSE_OK;
@@ -3090,11 +2961,7 @@ int mse_rollout_policy(mse_env *h, mse_policy *pol, mse_policy *sort_pol, int32_
                        float *last_value_out, uint8_t *last_done_out, void *stream)
 {
     if (!h || !pol) return fail(MSE_ERR_INVALID_ARGUMENT, "env/policy is NULL");
-    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_rollout_policy before mse_reset(seeds)");
-    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
-    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_policy needs auto_reset=1");
-    if (h->trace_rec != nullptr)
-        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (const int rc = rollout_checks(h, k_steps, "mse_rollout_policy")) return rc;
     if (flags & ~(MSE_STEP_UNMASKED | MSE_STEP_CHECK_OVERFLOW))
         return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag");
     if (pol->d_in != mse_obs_dim(h) || pol->n_act != mse_num_actions(h))
@@ -3113,13 +2980,11 @@ int mse_rollout_policy(mse_env *h, mse_policy *pol, mse_policy *sort_pol, int32_
         return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_policy serves the integer draw path with a remainder-free batch "
                                                 "(literal_choice, input_batch_size > 127 or with a floor() remainder: "
                                                 "alternate mse_policy_forward and mse_step)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc;
-    switch (h->P.env_kind) {
-    case 1: rc = launch_rollout_policy<1>(h, pol, sort_pol, s, k_steps, seed, deterministic, sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out, reward_out, episode_start_out, last_value_out, last_done_out); break;
-    case 2: rc = launch_rollout_policy<2>(h, pol, sort_pol, s, k_steps, seed, deterministic, sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out, reward_out, episode_start_out, last_value_out, last_done_out); break;
-    default: rc = launch_rollout_policy<3>(h, pol, sort_pol, s, k_steps, seed, deterministic, sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out, reward_out, episode_start_out, last_value_out, last_done_out); break;
-    }
+    const int rc = with_kind(h->P.env_kind, [&](auto KIND) {
+        return launch_rollout_policy<KIND>(h, pol, sort_pol, static_cast<hipStream_t>(stream), k_steps, seed, deterministic,
+                                           sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out,
+                                           reward_out, episode_start_out, last_value_out, last_done_out);
+    });
     if (rc != MSE_OK) return fail(rc, "the policy rollout kernel's LDS image does not fit this config's tables");
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
@@ -3130,14 +2995,9 @@ int mse_rollout_model(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, int
                       int32_t *actions_out, float *obs_out, float *reward_out, uint8_t *done_out, uint8_t *mask_out,
                       float *sort_obs_out, float *press_obs_out, void *stream)
 {
-    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "env is NULL");
-    if (h->P.env_kind != MSE_ENV_MONO)
+    if (h != nullptr && h->P.env_kind != MSE_ENV_MONO)
         return fail(MSE_ERR_INVALID_ARGUMENT, "mode='model' exists on Env_3_Monolith only (env_monolith.py:186)");
-    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_rollout_model before mse_reset(seeds)");
-    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
-    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_model needs auto_reset=1");
-    if (h->trace_rec != nullptr)
-        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (const int rc = rollout_checks(h, k_steps, "mse_rollout_model")) return rc;
     if (flags & ~(MSE_STEP_UNMASKED | MSE_STEP_CHECK_OVERFLOW | MSE_MODEL_PRESS_AGENT_MASKED))
         return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag");
     if (sort_ag != nullptr && (sort_ag->d_in != 13 || sort_ag->n_act != 2))
@@ -3168,12 +3028,10 @@ static int sample_actions_impl(mse_env *h, uint32_t pflags, uint64_t policy_seed
 {
     if (!h || !action_out) return fail(MSE_ERR_INVALID_ARGUMENT, "env/action_out is NULL");
     if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "policy sampling before mse_reset(seeds)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (h->P.env_kind) {
-    case 1: hipLaunchKernelGGL(k_sample<1>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, pflags, policy_seed, h->policy_t, action_out); break;
-    case 2: hipLaunchKernelGGL(k_sample<2>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, pflags, policy_seed, h->policy_t, action_out); break;
-    default: hipLaunchKernelGGL(k_sample<3>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, h->tables, pflags, policy_seed, h->policy_t, action_out); break;
-    }
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        hipLaunchKernelGGL(k_sample<KIND>, grid_of(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->P, h->planes,
+                           h->tables, pflags, policy_seed, h->policy_t, action_out);
+    });
     MSE_CHECK_LAUNCH();
     return MSE_OK;
 }
@@ -3227,12 +3085,10 @@ int mse_trace_end(mse_env *h, int64_t *n_records_out)
 int mse_action_masks(mse_env *h, uint8_t *mask_out, void *stream)
 {
     if (!h || !mask_out) return fail(MSE_ERR_INVALID_ARGUMENT, "env/mask_out is NULL");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    switch (h->P.env_kind) {
-    case 1: hipLaunchKernelGGL(k_masks<1>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, mask_out); break;
-    case 2: hipLaunchKernelGGL(k_masks<2>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, mask_out); break;
-    default: hipLaunchKernelGGL(k_masks<3>, grid_of(h), dim3(kBlock), 0, s, h->P, h->planes, mask_out); break;
-    }
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        hipLaunchKernelGGL(k_masks<KIND>, grid_of(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->P, h->planes,
+                           mask_out);
+    });
     MSE_CHECK_LAUNCH();
     return MSE_OK;
 }

@@ -1,0 +1,304 @@
+"""The rollout kernel selection (marl-sortingenv_amd/csrc/mse_plan.h) pinned on the CPU.  The header is compiled on the
+host as it is and its plans are compared with a restatement of the rules the library applied before the selection
+moved into one header (mse_create's pipelined / ring flags, launch_rollout_policy's roles test and shape,
+launch_rollout_model's shape), across the sizes, pipeline settings and LDS budgets where the choice changes.  The
+plans must also name the kernel bench.py reports for the workloads it runs."""
+import ctypes as C
+import itertools
+import math
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "marl-sortingenv_amd", "csrc")
+INCLUDE = os.path.join(ROOT, "include")
+
+SHIM = r"""
+#include "mse_plan.h"
+#include <string.h>
+using namespace mse;
+extern "C" {
+unsigned long long lds_limit() { return kLdsLimitBytes; }
+int draws(const double *baseline, double boost, double noise, const unsigned *pat_word, int kind)
+{
+    return max_draws_per_step(baseline, boost, noise, pat_word, kind);
+}
+int rollout(int rp, long long n, int cus, int literal, int gen, int worst, unsigned long long ring_lds, int static_free,
+            int *status, char *why, int why_len)
+{
+    const RolloutPlan p = plan_rollout(rp, n, cus, literal != 0, gen != 0, worst, ring_lds, static_free != 0);
+    *status = p.status;
+    why[0] = 0;
+    if (p.why != nullptr) strncpy(why, p.why, why_len - 1);
+    return (int)p.kernel;
+}
+static int out(const PolicyPlan &p, int *status, long long *shape)
+{
+    *status = p.status;
+    shape[0] = (long long)p.lds_bytes;
+    shape[1] = p.tiles;
+    shape[2] = p.n_waves;
+    shape[3] = p.workgroups;
+    return (int)p.kernel;
+}
+static PolicyLds lds_of(const unsigned long long *l) { return {l[0], l[1], l[2], l[3], {l[4], l[5]}}; }
+int policy(int rp, long long n, int cus, int f16, int sort_pol, int worst, int literal, int gen, int static_free,
+           const unsigned long long *lds, int *status, long long *shape)
+{
+    return out(plan_rollout_policy(rp, n, cus, f16 != 0, sort_pol != 0, worst, literal != 0, gen != 0,
+                                   static_free != 0, lds_of(lds)), status, shape);
+}
+int model(long long n, int cus, const unsigned long long *lds, int *status, long long *shape)
+{
+    return out(plan_policy_plain(n, cus, true, 2, lds_of(lds)), status, shape);
+}
+}
+"""
+
+ONE_LANE, TWO_ROLE, RING = 0, 1, 2            # RolloutKernel
+ROLES_RING, ROLES, PLAIN = 0, 1, 2            # PolicyKernel
+ROLLOUT_NAMES = {ONE_LANE: "k_rollout", TWO_ROLE: "k_rollout_po", RING: "k_rollout_ring"}
+POLICY_NAMES = {ROLES_RING: "k_rollout_policy_roles", ROLES: "k_rollout_policy_roles", PLAIN: "k_rollout_policy"}
+LIMIT = 160 * 1024
+
+
+def _status(name):
+    text = open(os.path.join(INCLUDE, "mse.h")).read()
+    return int(re.search(r"\b" + name + r"\s*=\s*(-?\d+)", text).group(1))
+
+
+OK, UNSUPPORTED = _status("MSE_OK"), _status("MSE_ERR_UNSUPPORTED_CONFIG")
+MSG_GEN = ("rollout_pipeline 1 / 3 need a remainder-free input_batch_size (the one-lane kernels serve the general "
+           "generator)")
+MSG_RING = ("rollout_pipeline=3 (ring kernel) needs at most 31 draws per step, the integer draw path and an LDS image "
+            "within 160 KiB")
+
+
+@pytest.fixture(scope="module")
+def lib(tmp_path_factory):
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler to build the mse_plan.h shim")
+    d = tmp_path_factory.mktemp("plan")
+    src, so = d / "shim.cpp", d / "shim.so"
+    src.write_text(SHIM)
+    subprocess.run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-I", CSRC,
+                    "-I", INCLUDE, str(src), "-o", str(so)], check=True)
+    L = C.CDLL(str(so))
+    L.lds_limit.restype = C.c_ulonglong
+    L.draws.argtypes = [C.POINTER(C.c_double), C.c_double, C.c_double, C.POINTER(C.c_uint), C.c_int]
+    L.rollout.argtypes = [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int,
+                          C.POINTER(C.c_int), C.c_char_p, C.c_int]
+    L.policy.argtypes = [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                         C.POINTER(C.c_ulonglong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    L.model.argtypes = [C.c_longlong, C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_int), C.POINTER(C.c_longlong)]
+    return L
+
+
+def plan_rollout(L, rp, n, cus, literal, gen, worst, ring_lds, static_free):
+    st, why = C.c_int(), C.create_string_buffer(512)
+    k = L.rollout(rp, n, cus, literal, gen, worst, ring_lds, static_free, C.byref(st), why, 512)
+    return (k, OK, None) if st.value == OK else (None, st.value, why.value.decode())
+
+
+def _lds_arr(lds):
+    return (C.c_ulonglong * 6)(*lds)
+
+
+def plan_policy(L, rp, n, cus, f16, sort_pol, worst, literal, gen, static_free, lds):
+    st, shape = C.c_int(), (C.c_longlong * 4)()
+    k = L.policy(rp, n, cus, f16, sort_pol, worst, literal, gen, static_free, _lds_arr(lds), C.byref(st), shape)
+    return (k, st.value, tuple(shape)) if st.value == OK else (None, st.value, None)
+
+
+def plan_model(L, n, cus, lds):
+    st, shape = C.c_int(), (C.c_longlong * 4)()
+    k = L.model(n, cus, _lds_arr(lds), C.byref(st), shape)
+    return (k, st.value, tuple(shape)) if st.value == OK else (None, st.value, None)
+
+
+# ---- the rules as the library applied them before mse_plan.h ---------------------------------------------------------
+def old_rollout(rp, n, cus, literal, gen, worst, ring_lds, static_free):
+    """mse_create: h->pipelined, h->ring and the two refusals"""
+    n_wg = (n + 255) // 256
+    by_size = n_wg <= cus or (cus + cus // 4 < n_wg <= 2 * cus)
+    pipelined = rp in (1, 3) or (rp == 0 and by_size)
+    if gen:
+        if rp in (1, 3):
+            return None, UNSUPPORTED, MSG_GEN
+        pipelined = False
+    fits = worst <= 31 and not literal and ring_lds <= LIMIT and static_free
+    if rp == 0 and n_wg > cus and not fits:
+        pipelined = False
+    ring = pipelined and fits and rp != 1
+    if rp == 3 and not fits:
+        return None, UNSUPPORTED, MSG_RING
+    return (RING if ring else TWO_ROLE if pipelined else ONE_LANE), OK, None
+
+
+def _old_plain(n, cus, f16, n_nets, lds):
+    small = n <= 256 * cus
+    tiles = 1 if f16 and small else 2
+    n_waves = 4 if not f16 and small else 8
+    total = lds[2] * n_nets + lds[3] + n_waves * (lds[4] if tiles == 1 else lds[5])
+    if total > LIMIT:
+        return None, UNSUPPORTED, None
+    epw = 32 * tiles * n_waves
+    return PLAIN, OK, (total, tiles, n_waves, (n + epw - 1) // epw)
+
+
+def old_policy(rp, n, cus, f16, sort_pol, worst, literal, gen, static_free, lds):
+    """launch_rollout_policy with mse_create's h->ring_ok"""
+    ring_ok = worst <= 31 and not literal and not gen and static_free
+    if f16 and not sort_pol and n <= 256 * cus and rp != 2:
+        with_ring = ring_ok and lds[0] <= LIMIT and rp != 1
+        if with_ring or lds[1] <= LIMIT:
+            return (ROLES_RING if with_ring else ROLES), OK, (lds[0] if with_ring else lds[1], 0, 0, (n + 255) // 256)
+    return _old_plain(n, cus, f16, 2 if sort_pol else 1, lds)
+
+
+def old_model(n, cus, lds):
+    """launch_rollout_model: f16x3 shape, two networks"""
+    tiles = 1 if n <= 256 * cus else 2
+    total = lds[2] * 2 + lds[3] + 8 * (lds[4] if tiles == 1 else lds[5])
+    if total > LIMIT:
+        return None, UNSUPPORTED, None
+    return PLAIN, OK, (total, tiles, 8, (n + 256 * tiles - 1) // (256 * tiles))
+
+
+def old_draws(baseline, boost, noise, pat_word, kind):
+    worst = 0
+    for k in (1, 2):
+        for mode in range(3 if kind == 2 else 2):
+            s = 0
+            for m in range(4):
+                boosted = (m in (0, 2)) if mode == 0 else ((m in (1, 3)) if mode == 1 else False)
+                acc = min(1.0, max(0.0, baseline[m] + (boost if boosted else 0.0) - noise))
+                cnt = (pat_word[k] >> (8 * m)) & 0xFF
+                s += cnt - int(round(cnt * acc))
+            worst = max(worst, s)
+    return worst
+
+
+# ---- sweeps -----------------------------------------------------------------------------------------------------------
+CUS = (80, 256, 304)
+
+
+def sizes(cus):
+    """1, 2^20, and each side of the size rules' edges: 256, 320 and 512 envs x CUs"""
+    return sorted({1, 1 << 20} | {m * cus + d for m in (256, 320, 512) for d in (-256, -1, 0, 1, 256)})
+
+
+def test_lds_limit(lib):
+    assert lib.lds_limit() == LIMIT
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_rollout_plan_matches_the_old_rule(lib, cus):
+    n_checked = 0
+    for rp, n, literal, gen, worst, ring_lds, static_free in itertools.product(
+            range(4), sizes(cus), (0, 1), (0, 1), (19, 31, 32), (LIMIT, LIMIT + 1), (1, 0)):
+        got = plan_rollout(lib, rp, n, cus, literal, gen, worst, ring_lds, static_free)
+        want = old_rollout(rp, n, cus, bool(literal), bool(gen), worst, ring_lds, bool(static_free))
+        assert got == want, (rp, n, cus, literal, gen, worst, ring_lds, static_free)
+        n_checked += 1
+    assert n_checked > 3000
+
+
+def _policy_lds_cases():
+    """(roles_ring, roles_pair, network, tables, wave[1 tile], wave[2 tiles]) around the 160 KiB limit"""
+    net, w1, w2 = 21264, 6144, 10240
+    cases = []
+    for ring, pair in itertools.product((LIMIT, LIMIT + 1), (LIMIT - 65536, LIMIT, LIMIT + 1)):
+        cases.append((ring, pair, net, 4096, w1, w2))
+    # the plain form's sum just under, at and just over the limit for each shape it can take
+    for n_nets, n_waves, wave in ((1, 8, w1), (1, 8, w2), (1, 4, w2), (2, 8, w1), (2, 8, w2)):
+        edge = LIMIT - net * n_nets - n_waves * wave
+        for d in (-1, 0, 1):
+            cases.append((LIMIT + 1, LIMIT + 1, net, edge + d, w1, w2))
+    return cases
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_policy_plan_matches_the_old_rule(lib, cus):
+    n_checked = 0
+    for rp, n, f16, sort_pol, worst, literal, gen, static_free, lds in itertools.product(
+            range(4), sizes(cus), (1, 0), (0, 1), (19, 31, 32), (0, 1), (0, 1), (1, 0), _policy_lds_cases()):
+        if sort_pol and not f16:
+            continue  # mse_rollout_policy refuses an in-loop sorting policy outside the f16x3 form
+        got = plan_policy(lib, rp, n, cus, f16, sort_pol, worst, literal, gen, static_free, lds)
+        want = old_policy(rp, n, cus, bool(f16), bool(sort_pol), worst, bool(literal), bool(gen), bool(static_free), lds)
+        assert got == want, (rp, n, cus, f16, sort_pol, worst, literal, gen, static_free, lds)
+        n_checked += 1
+    assert n_checked > 10000
+
+
+@pytest.mark.parametrize("cus", CUS)
+def test_model_plan_matches_the_old_rule(lib, cus):
+    for n, lds in itertools.product(sizes(cus), _policy_lds_cases()):
+        assert plan_model(lib, n, cus, lds) == old_model(n, cus, lds), (n, cus, lds)
+
+
+def _pat_words(ratio, batch):
+    """Params::pat_word as build_tables packs it: floor(ratio * batch) per material, one byte each"""
+    words = [0]
+    for r in ratio:
+        w = 0
+        for m in range(4):
+            w |= math.floor(r[m] * batch) << (8 * m)
+        words.append(w)
+    return words
+
+
+REF_RATIO = ((0.40, 0.15, 0.35, 0.10), (0.15, 0.40, 0.10, 0.35))  # mse_config_default
+
+
+def _draws(lib, baseline, boost, noise, words, kind):
+    return lib.draws((C.c_double * 4)(*baseline), boost, noise, (C.c_uint * 3)(*words), kind)
+
+
+def test_max_draws_per_step(lib):
+    words = _pat_words(REF_RATIO, 100)
+    # the reference's config without noise
+    for kind in (1, 3):
+        assert _draws(lib, (0.75,) * 4, 0.5, 0.0, words, kind) == 19
+    for kind, batch, base, boost, noise in itertools.product(
+            (1, 2, 3), (20, 100, 127, 255), (0.5, 0.75, 0.9), (0.0, 0.25, 0.5), (0.0, 0.05, 0.3, 1.5)):
+        baseline = (base, base - 0.1, base + 0.05, base)
+        w = _pat_words(REF_RATIO, batch)
+        assert _draws(lib, baseline, boost, noise, w, kind) == old_draws(baseline, boost, noise, w, kind)
+
+
+# what bench.py runs: its headline and configs_measured entries, and its --pipeline choices
+BENCH = [dict(kind="mono", n=65536), dict(kind="sort", n=65536), dict(kind="press", n=65536),
+         dict(kind="mono", n=262144), dict(kind="mono", n=131072), dict(kind="mono", n=65536, noise=0.05)] + \
+        [dict(kind="mono", n=65536, pipeline=p) for p in (1, 2, 3)] + \
+        [dict(kind="mono", n=n, policy="mlp", precision=pr) for n in (65536, 262144) for pr in ("f16x3", "f32")]
+
+
+def test_plans_name_the_kernel_bench_reports(lib):
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    cus, kinds = 256, {"sort": 1, "press": 2, "mono": 3}
+    words = _pat_words(REF_RATIO, 100)
+    fitting = (LIMIT - 1024, LIMIT - 65536, 21264, 4096, 6144, 10240)
+    for w in BENCH:
+        kind, n, pipeline = kinds[w["kind"]], w["n"], w.get("pipeline", 0)
+        worst = _draws(lib, (0.75,) * 4, 0.5, w.get("noise", 0.0), words, kind)
+        policy, precision = w.get("policy", "random"), w.get("precision", "f16x3")
+        if policy == "mlp":
+            k, st, _ = plan_policy(lib, pipeline, n, cus, precision == "f16x3", 0, worst, 0, 0, 1, fitting)
+            got = POLICY_NAMES[k]
+        else:
+            k, st, _ = plan_rollout(lib, pipeline, n, cus, 0, 0, worst, LIMIT - 1024, 1)
+            got = ROLLOUT_NAMES[k]
+        assert st == OK
+        assert got == bench.kernel_name(w["kind"], n, policy, pipeline, "rollout", cus=cus, precision=precision), w
