@@ -342,6 +342,60 @@ int mse_rollout_policy(mse_env *env, mse_policy *policy, mse_policy *sort_policy
                        int32_t *actions_out, float *logp_out, float *value_out, float *reward_out,
                        uint8_t *episode_start_out, float *last_value_out, uint8_t *last_done_out, void *stream);
 
+/* Replaces the device image of `policy` with new weights (same flat order as mse_policy_create), repacked by the same
+ * host routine, including the f16 range check: a policy in the "auto" form moves to f32 when a folded weight leaves
+ * f16's range and back when all fit again; one pinned to f16x3 refuses such weights (MSE_ERR_UNSUPPORTED_CONFIG, image
+ * unchanged).  A BLOCKING host-to-device copy.  Ordering rule: no launch that reads this policy may be in flight on
+ * any stream when it is called; launches enqueued afterwards see the new weights. */
+int mse_policy_set_weights(mse_policy *policy, const float *weights_host);
+
+/* ---- The learner's half of PPO (SB3's model.learn -> MaskablePPO.train, src/training.py:191) ---------------------------
+ * All buffers are caller-owned device memory, all work goes to `stream`, nothing allocates or synchronises, and the
+ * arguments are checked before any device call.
+ *
+ * RolloutBuffer.compute_returns_and_advantage over step-major [K, N] arrays (the reference never truncates an episode,
+ * so there is no terminal-value bootstrap):  backwards over k,  nnt = 1 - episode_starts[k + 1]  (1 - last_dones at
+ * k = K - 1),  delta = r + gamma * next_v * nnt - v,  gae = delta + gamma * lambda * nnt * gae,  returns = advantages +
+ * values.  float32 with every operation rounded separately in exactly that order (gamma and gamma * lambda rounded to
+ * f32 once): bit-identical to numpy's evaluation of SB3's loop. */
+int mse_gae(int32_t k_steps, int64_t n, const float *rewards, const float *values, const uint8_t *episode_starts,
+            const float *last_values, const uint8_t *last_dones, double gamma, double gae_lambda, float *advantages_out,
+            float *returns_out, void *stream);
+
+/* What MaskablePPO.train computes for one minibatch (`rollout_data`), and the gradient of its loss.
+ *   weights_dev  f32[W], W = mse_policy_num_weights(D, A), in the FLAT order documented above (not the packed image)
+ *   rows_dev     i64[batch] or NULL: the minibatch's rows out of the n_rows = K * N flattened rollout rows
+ *                (NULL = rows 0 .. batch - 1; an index outside [0, n_rows) is clamped)
+ *   obs f32[n_rows, D], mask u8[n_rows, A] or NULL, actions i32[n_rows], old_logp / advantages / returns f32[n_rows]
+ * Per minibatch: advantages normalised as (a - mean) / (std + 1e-8) with the unbiased std (normalize_advantage != 0 and
+ * batch > 1); both 2 x 32 tanh MLPs forward, illegal actions at logit -1e8; ratio = exp(logp - old_logp);
+ * policy_loss = -mean(min(adv ratio, adv clamp(ratio, 1 - clip, 1 + clip))); value_loss = mean((returns - value)^2);
+ * entropy_loss = -mean(entropy over the legal actions); loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss.
+ *   grad_out     f32[W]: d loss / d weights, flat order
+ *   stats_out    f32[8]: loss, policy_loss, value_loss, entropy_loss, approx_kl = mean((ratio - 1) - log ratio),
+ *                clip_fraction, and the advantage mean and std that were used (0 and 1 when not normalised)
+ *   workspace    mse_ppo_workspace_bytes(D, A) bytes, 16-byte aligned; contents need not survive between calls
+ * Three launches; sums are formed in a fixed order without atomics, so equal inputs give bit-equal outputs. */
+typedef struct mse_ppo_params {
+    uint32_t struct_size; /* = sizeof(mse_ppo_params) */
+    float    clip_range;
+    float    ent_coef;
+    float    vf_coef;
+    int32_t  normalize_advantage;
+} mse_ppo_params;
+int64_t mse_ppo_workspace_bytes(int obs_dim, int n_actions); /* 0 for dimensions outside 1..32; needs no device */
+int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,
+                      const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                      const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                      float *stats_out, void *workspace, void *stream);
+
+/* torch.nn.utils.clip_grad_norm_ (coef = min(1, max_grad_norm / (norm + 1e-6)); max_grad_norm <= 0: no clipping) followed
+ * by torch.optim.Adam without weight decay or amsgrad, in place on weights / m / v (f32[n_weights], zero m and v before
+ * the first step); `step` counts from 1.  grad is not modified.  grad_norm_out f32[1] or NULL: the norm before clipping.
+ * One workgroup (a policy has at most 4 791 weights). */
+int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
+                      double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ EXPORTS = [
     "mse_sort_agent_obs", "mse_policy_num_weights", "mse_policy_create", "mse_policy_destroy", "mse_policy_forward",
     "mse_get_policy_step", "mse_set_policy_step", "mse_model_actions", "mse_trace_begin", "mse_trace_end", "mse_press_agent_obs", "mse_rollout_policy", "mse_policy_set_precision", "mse_policy_precision",
     "mse_rollout_model",
+    "mse_policy_set_weights", "mse_gae", "mse_ppo_workspace_bytes", "mse_ppo_loss_grad", "mse_ppo_adam_step",
 ]
 
 _other_libs: dict = {}
@@ -51,6 +52,12 @@ class MseConfigStruct(C.Structure):
         ("pattern_ratio", (C.c_double * 4) * 2),
         ("rollout_pipeline", C.c_int32), ("reserved0", C.c_int32),
     ]
+
+
+class MsePpoParams(C.Structure):
+    """struct mse_ppo_params (include/mse.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("clip_range", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float),
+                ("normalize_advantage", C.c_int32)]
 
 
 _lib = None
@@ -120,6 +127,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_policy_forward.argtypes = [vp, i64, i64, vp, vp, u64, u64, C.c_int, vp, vp, vp, vp, vp]
     L.mse_rollout_policy.argtypes = [vp, vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
+    L.mse_gae.argtypes = [i32, i64, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
+    L.mse_ppo_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.mse_ppo_workspace_bytes.restype = i64
+    L.mse_ppo_loss_grad.argtypes = [C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, vp]
+    L.mse_ppo_adam_step.argtypes = [i64, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     if path is None:
         _lib = L
     else:

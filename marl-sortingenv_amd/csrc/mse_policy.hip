@@ -210,6 +210,21 @@ int mse_policy_create(mse_policy **out, int obs_dim, int n_actions, const float 
     return MSE_OK;
 }
 
+int mse_policy_set_weights(mse_policy *p, const float *weights_host)
+{
+    if (p == nullptr || weights_host == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_set_weights: null argument");
+    bool f16_ok = false;
+    const std::vector<float> packed = pack_weights(weights_host, p->d_in, p->n_act, f16_ok);
+    if (p->precision == 2 && !f16_ok)
+        return mse_internal_fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_policy_set_weights: a folded weight exceeds f16's range (65 504) and the f16x3 form was asked for");
+    // blocking copy from pageable memory: hipMemcpy returns once the device image is written.  The caller keeps the
+    // ordering rule of mse.h (no launch that reads this policy in flight on another stream).
+    if (hipMemcpy(p->blob, packed.data(), p->blob_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        return mse_internal_fail(MSE_ERR_HIP, "mse_policy_set_weights: device copy failed");
+    p->f16_ok = f16_ok ? 1 : 0;
+    return MSE_OK;
+}
+
 int mse_policy_set_precision(mse_policy *p, int mode)
 {
     if (p == nullptr || mode < 0 || mode > 2) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_set_precision: bad argument");

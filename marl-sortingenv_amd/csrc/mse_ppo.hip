@@ -1,0 +1,523 @@
+// The second half of PPO on the device: returns and advantages (mse_gae), the clipped-surrogate loss of one minibatch
+// with its gradient w.r.t. all weights (mse_ppo_loss_grad) and clip_grad_norm_ + Adam (mse_ppo_adam_step).  The
+// per-row arithmetic lives in mse_ppo_math.h (host + device); this file holds the kernels and the C ABI.  gfx950 only.
+//
+// Gradient kernel (k_ppo_grad), DESIGN.md 4.12.  A workgroup is four waves: wave w works on the actor (w & 1 == 0) or
+// the critic (w & 1 == 1) of tile slot w >> 1; a tile is 64 minibatch rows, one row per lane.  Per tile a wave
+//   1. runs its network forward and backward for its row with plain fmaf chains, weights broadcast from LDS (padded
+//      image, 16-byte reads), activations and deltas in registers;
+//   2. per layer stages (delta, input activation) of 32 rows at a time in its own LDS strip and accumulates the weight
+//      gradient  delta^T x activation  as a register-tiled product: lane (ob, ib) owns outputs 4 ob .. 4 ob + 3 times
+//      inputs 4 ib .. 4 ib + 3 of every layer (16 accumulators + 4 bias sums per layer), rows are the k dimension.
+// Accumulators stay in registers across all tiles of the wave.  At the end the two waves of a network are added in a
+// fixed order through LDS and the workgroup stores ONE slab of W floats (+ 8 loss sums) into the workspace; k_ppo_reduce
+// sums the slabs in slab order in double.  No atomics anywhere: same inputs, same bits.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "mse.h"
+#include "mse_ppo_math.h"
+
+int mse_internal_fail(int status, const char *msg); // mse_lib.hip: sets mse_last_error()
+
+namespace {
+
+using namespace mseppo;
+
+constexpr int kMaxSlabs = 512;       // workgroups of k_ppo_grad at most (two per CU on 256 CUs)
+constexpr int kMaxAdvPartials = 256; // workgroups of k_ppo_adv_partial at most
+constexpr int kStatFloats = 8;       // per slab: surrogate, squared error, entropy, kl, clipped sums
+constexpr int kStageStride = 68;     // floats per staged row: 32 deltas + 32 activations + 4 (16-byte rows, spread banks)
+constexpr int kStageFloats = 32 * kStageStride;
+constexpr int kMiscFloats = 20;        // advantage mean / std, the waves' loss sums
+
+__host__ __device__ constexpr long long slab_stride(long long w) { return (w + kStatFloats + 3) / 4 * 4; }
+
+// ---- GAE ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_gae(int k_steps, long long n, const float *__restrict__ rewards,
+                                             const float *__restrict__ values, const uint8_t *__restrict__ episode_starts,
+                                             const float *__restrict__ last_values, const uint8_t *__restrict__ last_dones,
+                                             float g, float gl, float *__restrict__ adv_out, float *__restrict__ ret_out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) gae_column(k_steps, n, i, rewards, values, episode_starts, last_values, last_dones, g, gl, adv_out, ret_out);
+}
+
+// ---- advantage mean / std: partial sums of d = a - pivot and d^2 in double, one pair per workgroup -------------------
+__device__ __forceinline__ long long row_at(const long long *rows, long long b, long long n_rows)
+{
+    long long r = rows == nullptr ? b : rows[b];
+    r = r < 0 ? 0 : r;
+    return r >= n_rows ? n_rows - 1 : r; // an index outside the rollout is clamped, never followed
+}
+
+__global__ __launch_bounds__(256) void k_ppo_adv_partial(long long batch, long long n_rows, const long long *__restrict__ rows,
+                                                         const float *__restrict__ adv, double *__restrict__ partial)
+{
+    __shared__ double sh[2][256];
+    const double pivot = (double)adv[row_at(rows, 0, n_rows)];
+    double s = 0.0, q = 0.0;
+    for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < batch; b += (long long)gridDim.x * 256) {
+        const double d = (double)adv[row_at(rows, b, n_rows)] - pivot;
+        s += d;
+        q += d * d;
+    }
+    sh[0][threadIdx.x] = s;
+    sh[1][threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { // fixed tree
+        if ((int)threadIdx.x < w) {
+            sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
+            sh[1][threadIdx.x] += sh[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = sh[0][0];
+        partial[2 * blockIdx.x + 1] = sh[1][0];
+    }
+}
+
+// mean and unbiased std from the partials, summed in index order (every caller gets the same bits)
+__device__ __forceinline__ void adv_mean_std(const double *partial, int n_partial, double pivot, long long batch, float &mean, float &std)
+{
+    double s = 0.0, q = 0.0;
+    for (int g = 0; g < n_partial; ++g) {
+        s += partial[2 * g];
+        q += partial[2 * g + 1];
+    }
+    const double var = (q - s * s / (double)batch) / (double)(batch - 1);
+    mean = (float)(pivot + s / (double)batch);
+    std = (float)sqrt(var > 0.0 ? var : 0.0);
+}
+
+// ---- the gradient kernel ------------------------------------------------------------------------------------------------
+struct GradArgs {
+    int D, A;
+    long long n_rows, batch;
+    int n_adv_partial; // 0: advantages are used as they are
+    Params P;
+};
+
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+template <int N>
+__device__ __forceinline__ float padded_at(const float (&v)[N], int i) // i is a compile-time constant after unrolling
+{
+    return i < N ? v[i < N ? i : 0] : 0.0f;
+}
+
+// acc[4 p + q] += sum over the wave's 64 rows of delta[4 ob + p] * act[4 ib + q];  db[p] += sum of delta[4 ob + p].
+// Rows go through the wave's LDS strip 32 at a time: [row][0..31] deltas, [row][32..63] activations.
+template <int ND, int NA>
+__device__ __forceinline__ void accumulate_layer(float *strip, int lane, const float (&delta)[ND], const float (&act)[NA],
+                                                 float (&acc)[16], float (&db)[4])
+{
+    const int ob = lane >> 3, ib = lane & 7;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        if ((lane >> 5) == half) {
+            float4 *dst = reinterpret_cast<float4 *>(strip + (lane & 31) * kStageStride);
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                dst[c] = make_float4(padded_at(delta, 4 * c), padded_at(delta, 4 * c + 1), padded_at(delta, 4 * c + 2), padded_at(delta, 4 * c + 3));
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                dst[8 + c] = make_float4(padded_at(act, 4 * c), padded_at(act, 4 * c + 1), padded_at(act, 4 * c + 2), padded_at(act, 4 * c + 3));
+        }
+        wave_lds_sync();
+#pragma unroll 4
+        for (int r = 0; r < 32; ++r) {
+            const float4 d = *reinterpret_cast<const float4 *>(strip + r * kStageStride + 4 * ob);
+            const float4 a = *reinterpret_cast<const float4 *>(strip + r * kStageStride + 32 + 4 * ib);
+            const float dv[4] = {d.x, d.y, d.z, d.w}, av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[4 * p + q] = fmaf(dv[p], av[q], acc[4 * p + q]);
+                db[p] += dv[p];
+            }
+        }
+        wave_lds_sync();
+    }
+}
+
+struct LayerAcc {
+    float w[16], b[4];
+};
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64); // fixed butterfly
+    return v;
+}
+
+// one layer's accumulators -> the flat gradient: out[w_off + o * ld + i] (o < n_out, i < n_in), out[b_off + o]
+__device__ __forceinline__ void store_layer(float *out, const LayerAcc &L, int lane, int w_off, int b_off, int n_out, int n_in, int ld)
+{
+    const int ob = lane >> 3, ib = lane & 7;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int o = 4 * ob + p;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = 4 * ib + q;
+            if (o < n_out && i < n_in) out[w_off + o * ld + i] = L.w[4 * p + q];
+        }
+        if (ib == 0 && o < n_out) out[b_off + o] = L.b[p];
+    }
+}
+
+template <int DP, int AP>
+__global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__restrict__ weights, const long long *__restrict__ rows,
+                                                  const float *__restrict__ obs, const uint8_t *__restrict__ mask,
+                                                  const int *__restrict__ actions, const float *__restrict__ old_logp,
+                                                  const float *__restrict__ adv, const float *__restrict__ ret,
+                                                  const double *__restrict__ adv_partial, float *__restrict__ slabs)
+{
+    typedef Padded<DP, AP> PW;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *wl0 = lds;                     // PW::total floats: the padded weights
+    float *strips = lds + PW::total;      // 4 x kStageFloats: one staging strip per wave
+    // (no static __shared__: it would shift the dynamic base off its 16-byte alignment)
+    float *sh_mean_std = strips + 4 * kStageFloats;                       // [2]
+    float(*sh_stats)[4] = reinterpret_cast<float(*)[4]>(sh_mean_std + 4); // [4 waves][4]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int D = G.D, A = G.A;
+    const Flat F = flat_layout(D, A);
+    for (int i = tid; i < PW::total; i += 256) wl0[i] = 0.0f;
+    __syncthreads();
+    for (int f = tid; f < F.total; f += 256) wl0[padded_index<DP, AP>(f, D, A)] = weights[f];
+    if (wave == 0) { // every lane sums the same partials in the same order
+        float mean = 0.0f, std = 1.0f;
+        if (G.n_adv_partial > 0) adv_mean_std(adv_partial, G.n_adv_partial, (double)adv[row_at(rows, 0, G.n_rows)], G.batch, mean, std);
+        if (lane == 0) {
+            sh_mean_std[0] = mean;
+            sh_mean_std[1] = std;
+        }
+    }
+    __syncthreads();
+    const bool normalize = G.n_adv_partial > 0;
+    const float mean = sh_mean_std[0], std = sh_mean_std[1];
+    const float inv_b_all = 1.0f / (float)G.batch;
+    const bool critic = (wave & 1) != 0;
+    float *strip = strips + wave * kStageFloats;
+    LayerAcc L1 = {}, L2 = {}, L3 = {}; // first, second hidden layer, head
+    float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f;
+    const long long n_tiles = (G.batch + 63) / 64;
+    for (long long tile = (long long)blockIdx.x * 2 + (wave >> 1); tile < n_tiles; tile += (long long)gridDim.x * 2) {
+        // the weights are re-read from LDS every tile: an offset the compiler cannot see through keeps it from hoisting
+        // ~5 000 wave-uniform values out of the loop into (spilled) scalar registers
+        unsigned opaque = 0;
+        asm volatile("" : "+v"(opaque));
+        const float *wl = static_cast<const float *>(__builtin_assume_aligned(wl0 + 4 * opaque, 16));
+        const long long b = tile * 64 + lane;
+        const bool valid = b < G.batch;
+        const long long row = row_at(rows, valid ? b : 0, G.n_rows);
+        const float inv_b = valid ? inv_b_all : 0.0f; // a padding lane contributes zero deltas
+        float x[DP];
+#pragma unroll
+        for (int i = 0; i < DP; ++i) {
+            const float v = obs[row * D + (i < D ? i : 0)];
+            x[i] = i < D ? v : 0.0f;
+        }
+        float h1[kH], h2[kH], dz[kH];
+        if (!critic) {
+            uint32_t legal = 0;
+#pragma unroll
+            for (int a = 0; a < AP; ++a) {
+                const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
+                legal |= (ok ? 1u : 0u) << a;
+            }
+            int action = actions[row];
+            action = action < 0 ? 0 : (action >= A ? A - 1 : action);
+            const float a_raw = adv[row];
+            const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
+            hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
+            float dl[AP];
+            head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
+            const PolicyTerms t = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
+            if (valid) {
+                st0 += t.surrogate;
+                st1 += t.entropy;
+                st2 += t.kl;
+                st3 += t.clipped;
+            }
+            accumulate_layer(strip, lane, dl, h2, L3.w, L3.b);
+            backprop<AP>(wl + PW::act_w, dl, h2, dz);
+        } else {
+            hidden_forward<DP>(wl + PW::vf_w1, wl + PW::vf_b1, wl + PW::vf_w2, wl + PW::vf_b2, x, h1, h2);
+            float v[1];
+            head_forward<1>(wl + PW::val_w, wl + PW::val_b, h2, v);
+            float dv[1];
+            const float sq = value_head_terms(v[0], ret[row], G.P, inv_b, dv[0]);
+            if (valid) st0 += sq;
+            accumulate_layer(strip, lane, dv, h2, L3.w, L3.b);
+            backprop<1>(wl + PW::val_w, dv, h2, dz);
+        }
+        const float *w2 = wl + (critic ? PW::vf_w2 : PW::pi_w2);
+        accumulate_layer(strip, lane, dz, h1, L2.w, L2.b);
+        float dz1[kH];
+        backprop<kH>(w2, dz, h1, dz1);
+        accumulate_layer(strip, lane, dz1, x, L1.w, L1.b);
+    }
+    // ---- the two waves of a network: slot 1 hands its sums to slot 0 through LDS; fixed order (slot 0 + slot 1) ----
+    st0 = wave_sum(st0);
+    st1 = wave_sum(st1);
+    st2 = wave_sum(st2);
+    st3 = wave_sum(st3);
+    __syncthreads(); // every wave is done with its strip
+    float *xch = strips + (wave & 1) * (60 * 64);
+    if (wave >= 2) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            xch[(k)*64 + lane] = L1.w[k];
+            xch[(16 + k) * 64 + lane] = L2.w[k];
+            xch[(32 + k) * 64 + lane] = L3.w[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            xch[(48 + k) * 64 + lane] = L1.b[k];
+            xch[(52 + k) * 64 + lane] = L2.b[k];
+            xch[(56 + k) * 64 + lane] = L3.b[k];
+        }
+    }
+    if (lane == 0) {
+        sh_stats[wave][0] = st0;
+        sh_stats[wave][1] = st1;
+        sh_stats[wave][2] = st2;
+        sh_stats[wave][3] = st3;
+    }
+    __syncthreads();
+    float *slab = slabs + (long long)blockIdx.x * slab_stride(F.total);
+    if (wave < 2) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            L1.w[k] += xch[(k)*64 + lane];
+            L2.w[k] += xch[(16 + k) * 64 + lane];
+            L3.w[k] += xch[(32 + k) * 64 + lane];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            L1.b[k] += xch[(48 + k) * 64 + lane];
+            L2.b[k] += xch[(52 + k) * 64 + lane];
+            L3.b[k] += xch[(56 + k) * 64 + lane];
+        }
+        if (!critic) {
+            store_layer(slab, L1, lane, F.pi_w1, F.pi_b1, kH, D, D);
+            store_layer(slab, L2, lane, F.pi_w2, F.pi_b2, kH, kH, kH);
+            store_layer(slab, L3, lane, F.act_w, F.act_b, A, kH, kH);
+        } else {
+            store_layer(slab, L1, lane, F.vf_w1, F.vf_b1, kH, D, D);
+            store_layer(slab, L2, lane, F.vf_w2, F.vf_b2, kH, kH, kH);
+            store_layer(slab, L3, lane, F.val_w, F.val_b, 1, kH, kH);
+        }
+    }
+    if (tid == 0) {
+        float *s = slab + F.total;
+        s[0] = sh_stats[0][0] + sh_stats[2][0]; // surrogate
+        s[1] = sh_stats[1][0] + sh_stats[3][0]; // squared value error
+        s[2] = sh_stats[0][1] + sh_stats[2][1]; // entropy
+        s[3] = sh_stats[0][2] + sh_stats[2][2]; // kl
+        s[4] = sh_stats[0][3] + sh_stats[2][3]; // clipped
+        s[5] = s[6] = s[7] = 0.0f;
+    }
+}
+
+// grad_out[i] = sum over slabs, in slab order, in double; the last workgroup turns the loss sums into stats_out
+__global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int w_total, const float *__restrict__ slabs,
+                                                    const long long *__restrict__ rows, const float *__restrict__ adv,
+                                                    const double *__restrict__ adv_partial, float *__restrict__ grad_out,
+                                                    float *__restrict__ stats_out)
+{
+    const long long stride = slab_stride(w_total);
+    if (blockIdx.x + 1 < gridDim.x) {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i >= w_total) return;
+        double s = 0.0;
+#pragma unroll 8
+        for (int g = 0; g < n_slabs; ++g) s += (double)slabs[(long long)g * stride + i];
+        grad_out[i] = (float)s;
+        return;
+    }
+    __shared__ double sums[kStatFloats];
+    if (threadIdx.x < 5) {
+        double s = 0.0;
+#pragma unroll 8
+        for (int g = 0; g < n_slabs; ++g) s += (double)slabs[(long long)g * stride + w_total + threadIdx.x];
+        sums[threadIdx.x] = s / (double)G.batch;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float mean = 0.0f, std = 1.0f;
+        if (G.n_adv_partial > 0) adv_mean_std(adv_partial, G.n_adv_partial, (double)adv[row_at(rows, 0, G.n_rows)], G.batch, mean, std);
+        const double policy_loss = sums[0], value_loss = sums[1], entropy_loss = -sums[2];
+        stats_out[0] = (float)(policy_loss + (double)G.P.ent_coef * entropy_loss + (double)G.P.vf_coef * value_loss);
+        stats_out[1] = (float)policy_loss;
+        stats_out[2] = (float)value_loss;
+        stats_out[3] = (float)entropy_loss;
+        stats_out[4] = (float)sums[3];
+        stats_out[5] = (float)sums[4];
+        stats_out[6] = mean;
+        stats_out[7] = std;
+    }
+}
+
+// ---- clip_grad_norm_ + Adam, one workgroup ----------------------------------------------------------------------------
+struct AdamArgs {
+    int n;
+    float lr_over_bc1, inv_sqrt_bc2, beta1, beta2, eps, max_norm;
+};
+
+__global__ __launch_bounds__(1024) void k_ppo_adam(AdamArgs a, float *__restrict__ w, const float *__restrict__ grad,
+                                                   float *__restrict__ m, float *__restrict__ v, float *__restrict__ norm_out)
+{
+    __shared__ double sh[1024];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < a.n; i += 1024) s += (double)grad[i] * (double)grad[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 512; k > 0; k >>= 1) { // fixed tree
+        if ((int)threadIdx.x < k) sh[threadIdx.x] += sh[threadIdx.x + k];
+        __syncthreads();
+    }
+    const float norm = (float)sqrt(sh[0]);
+    float coef = 1.0f;
+    if (a.max_norm > 0.0f) coef = fminf(1.0f, a.max_norm / (norm + 1e-6f));
+    if (threadIdx.x == 0 && norm_out != nullptr) norm_out[0] = norm;
+    for (int i = threadIdx.x; i < a.n; i += 1024) {
+        const float g = grad[i] * coef;
+        const float mi = a.beta1 * m[i] + (1.0f - a.beta1) * g;
+        const float vi = a.beta2 * v[i] + (1.0f - a.beta2) * g * g;
+        m[i] = mi;
+        v[i] = vi;
+        const float denom = sqrtf(vi) * a.inv_sqrt_bc2 + a.eps;
+        w[i] = w[i] - a.lr_over_bc1 * (mi / denom);
+    }
+}
+
+int cu_count()
+{
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return cus;
+}
+
+template <int DP, int AP>
+int launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
+                const double *adv_partial, float *slabs)
+{
+    const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
+    hipLaunchKernelGGL((k_ppo_grad<DP, AP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                       old_logp, adv, ret, adv_partial, slabs);
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int mse_gae(int32_t k_steps, int64_t n, const float *rewards, const float *values, const uint8_t *episode_starts,
+            const float *last_values, const uint8_t *last_dones, double gamma, double gae_lambda, float *advantages_out,
+            float *returns_out, void *stream)
+{
+    if (rewards == nullptr || values == nullptr || episode_starts == nullptr || last_values == nullptr || last_dones == nullptr ||
+        advantages_out == nullptr || returns_out == nullptr)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_gae: null argument");
+    if (k_steps < 1 || n < 1) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_gae: k_steps and n must be positive");
+    if (!(gamma >= 0.0 && gamma <= 1.0) || !(gae_lambda >= 0.0 && gae_lambda <= 1.0))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_gae: gamma and gae_lambda must lie in [0, 1]");
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_gae, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), (int)k_steps, (long long)n,
+                       rewards, values, episode_starts, last_values, last_dones, (float)gamma, (float)(gamma * gae_lambda),
+                       advantages_out, returns_out);
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_gae: kernel launch failed");
+    return MSE_OK;
+}
+
+int64_t mse_ppo_workspace_bytes(int obs_dim, int n_actions)
+{
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32) return 0;
+    const long long w = flat_layout(obs_dim, n_actions).total;
+    return (int64_t)(kMaxAdvPartials * 2 * sizeof(double) + (size_t)kMaxSlabs * slab_stride(w) * sizeof(float));
+}
+
+int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,
+                      const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                      const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                      float *stats_out, void *workspace, void *stream)
+{
+    if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
+        returns == nullptr || params == nullptr || grad_out == nullptr || stats_out == nullptr || workspace == nullptr)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: obs_dim and n_actions must be in 1..32");
+    if (params->struct_size != sizeof(mse_ppo_params))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: mse_ppo_params.struct_size mismatch");
+    if (n_rows < 1 || batch < 1 || (rows_dev == nullptr && batch > n_rows))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: need 1 <= batch (<= n_rows without rows_dev)");
+    if (!(params->clip_range >= 0.0f) || !std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: bad clip_range / ent_coef / vf_coef");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
+        return mse_internal_fail(MSE_ERR_ALIGNMENT, "mse_ppo_loss_grad: workspace must be 16-byte aligned");
+    const int cus = cu_count();
+    if (cus <= 0) return mse_internal_fail(MSE_ERR_NO_DEVICE, "mse_ppo_loss_grad: no HIP device (there is no CPU path)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *adv_partial = static_cast<double *>(workspace);
+    float *slabs = reinterpret_cast<float *>(adv_partial + 2 * kMaxAdvPartials);
+    const long long *rows = reinterpret_cast<const long long *>(rows_dev);
+    GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch, 0,
+               Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage}};
+    if (params->normalize_advantage != 0 && batch > 1) {
+        long long g1 = (batch + 1023) / 1024;
+        G.n_adv_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
+        hipLaunchKernelGGL(k_ppo_adv_partial, dim3((unsigned)G.n_adv_partial), dim3(256), 0, s, (long long)batch, (long long)n_rows, rows,
+                           advantages, adv_partial);
+    }
+    const long long tiles = (batch + 63) / 64;
+    long long n_slabs = (tiles + 1) / 2;
+    const long long cap = 2LL * cus < kMaxSlabs ? 2LL * cus : kMaxSlabs;
+    if (n_slabs > cap) n_slabs = cap;
+    // four shapes: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
+#define MSE_PPO_LAUNCH(DP, AP) \
+    launch_grad<DP, AP>(G, (int)n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs)
+    if (obs_dim <= 16 && n_actions <= 4) MSE_PPO_LAUNCH(16, 4);
+    else if (obs_dim <= 16 && n_actions <= 12) MSE_PPO_LAUNCH(16, 12);
+    else if (n_actions <= 24) MSE_PPO_LAUNCH(32, 24);
+    else MSE_PPO_LAUNCH(32, 32);
+#undef MSE_PPO_LAUNCH
+    const int w_total = flat_layout(obs_dim, n_actions).total;
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)n_slabs, w_total, slabs, rows,
+                       advantages, adv_partial, grad_out, stats_out);
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_loss_grad: kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
+                      double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream)
+{
+    if (weights == nullptr || grad == nullptr || m == nullptr || v == nullptr)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: null argument");
+    if (n_weights < 1 || n_weights > (1 << 24) || step < 1)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: need 1 <= n_weights <= 2^24 and step >= 1");
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: bad lr / beta / eps");
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    AdamArgs a{(int)n_weights, (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2)), (float)beta1, (float)beta2, (float)eps,
+               (float)max_grad_norm};
+    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, weights, grad, m, v, grad_norm_out);
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_adam_step: kernel launch failed");
+    return MSE_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,274 @@
+// mse_ppo_math.h -- the per-row arithmetic of the on-device PPO learner (mse_ppo.hip), in plain C++ that compiles for
+// the host and for the device alike (as mse_exact.h and mse_plan.h do), so tests/test_ppo_math_cpu.py can hold it
+// against float64 autograd without a GPU.
+//
+// What it restates (stable-baselines3 / sb3-contrib, which src/training.py:115-131,191 of the reference drives):
+//   gae_column          RolloutBuffer.compute_returns_and_advantage, one env, every operation separately rounded
+//   policy_head_terms   MaskableCategorical (illegal logits at -1e8), log-prob / entropy, the clipped surrogate of
+//                       MaskablePPO.train and the gradient of  policy_loss + ent_coef * entropy_loss  w.r.t. the logits
+//   value_head_terms    F.mse_loss(returns, values) and its gradient
+//   hidden_forward / head_forward / backprop            the 2 x 32 tanh MLP and the deltas of its layers
+// The weights are read from a PADDED image (Padded<DP, AP>: rows of the first layer padded to DP inputs, the action
+// head to AP rows, zeros in the padding, every block 16-byte aligned) so that all loops have compile-time bounds and
+// every array lives in registers on the device.  padded_index() maps the flat order of include/mse.h to it.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MSE_PPO_HD __host__ __device__ __forceinline__
+#else
+#define MSE_PPO_HD inline
+#endif
+
+namespace mseppo {
+
+constexpr int kH = 32;
+constexpr float kMaskedLogit = -1e8f; // sb3_contrib MaskableCategorical / mse_policy_forward
+
+struct Params {
+    float clip_range, ent_coef, vf_coef;
+    int normalize_advantage;
+};
+
+// ---- GAE ------------------------------------------------------------------------------------------------------------
+// SB3's loop for env column `i` of step-major [K, N] arrays (stride n).  g = float(gamma), gl = float(gamma * lambda)
+// (SB3 multiplies the two Python floats first).  Operation order is SB3's:
+//   delta = r + g * next_v * nnt - v            ((r + ((g * next_v) * nnt)) - v)
+//   gae   = delta + gl * nnt * gae              (delta + ((gl * nnt) * gae))
+// Compiled with -ffp-contract=off, so nothing here fuses and the result equals numpy's float32 evaluation bit for bit.
+MSE_PPO_HD void gae_column(int k_steps, long long n, long long i, const float *rewards, const float *values,
+                           const uint8_t *episode_starts, const float *last_values, const uint8_t *last_dones, float g,
+                           float gl, float *adv_out, float *ret_out)
+{
+    float gae = 0.0f;
+    float next_v = last_values[i];
+    float nnt = 1.0f - (float)(last_dones[i] != 0 ? 1 : 0);
+    for (int k = k_steps - 1; k >= 0; --k) {
+        const long long at = (long long)k * n + i;
+        const float v = values[at];
+        const float t1 = g * next_v;
+        const float t2 = t1 * nnt;
+        const float t3 = rewards[at] + t2;
+        const float delta = t3 - v;
+        const float u1 = gl * nnt;
+        const float u2 = u1 * gae;
+        gae = delta + u2;
+        adv_out[at] = gae;
+        ret_out[at] = gae + v;
+        next_v = v;
+        nnt = 1.0f - (float)(episode_starts[at] != 0 ? 1 : 0);
+    }
+}
+
+// ---- weight layouts -------------------------------------------------------------------------------------------------
+// flat order of include/mse.h (= SB3's state_dict order)
+struct Flat {
+    int pi_w1, pi_b1, pi_w2, pi_b2, act_w, act_b, vf_w1, vf_b1, vf_w2, vf_b2, val_w, val_b, total;
+};
+MSE_PPO_HD Flat flat_layout(int D, int A)
+{
+    Flat f;
+    f.pi_w1 = 0;
+    f.pi_b1 = f.pi_w1 + kH * D;
+    f.pi_w2 = f.pi_b1 + kH;
+    f.pi_b2 = f.pi_w2 + kH * kH;
+    f.act_w = f.pi_b2 + kH;
+    f.act_b = f.act_w + A * kH;
+    f.vf_w1 = f.act_b + A;
+    f.vf_b1 = f.vf_w1 + kH * D;
+    f.vf_w2 = f.vf_b1 + kH;
+    f.vf_b2 = f.vf_w2 + kH * kH;
+    f.val_w = f.vf_b2 + kH;
+    f.val_b = f.val_w + kH;
+    f.total = f.val_b + 1;
+    return f;
+}
+
+template <int DP, int AP>
+struct Padded {
+    static_assert(DP % 4 == 0 && AP % 4 == 0 && DP <= 32 && AP <= 32, "padded sizes are multiples of 4, at most 32");
+    static constexpr int pi_w1 = 0;
+    static constexpr int pi_b1 = pi_w1 + kH * DP;
+    static constexpr int pi_w2 = pi_b1 + kH;
+    static constexpr int pi_b2 = pi_w2 + kH * kH;
+    static constexpr int act_w = pi_b2 + kH;
+    static constexpr int act_b = act_w + AP * kH;
+    static constexpr int vf_w1 = act_b + AP;
+    static constexpr int vf_b1 = vf_w1 + kH * DP;
+    static constexpr int vf_w2 = vf_b1 + kH;
+    static constexpr int vf_b2 = vf_w2 + kH * kH;
+    static constexpr int val_w = vf_b2 + kH;
+    static constexpr int val_b = val_w + kH;
+    static constexpr int total = val_b + 4;
+};
+
+// flat index (0 <= f < flat_layout(D, A).total) -> index in the padded image
+template <int DP, int AP>
+MSE_PPO_HD int padded_index(int f, int D, int A)
+{
+    typedef Padded<DP, AP> P;
+    const Flat F = flat_layout(D, A);
+    if (f < F.pi_b1) return P::pi_w1 + (f / D) * DP + f % D;
+    if (f < F.act_w) return P::pi_b1 + (f - F.pi_b1); // pi_b1, pi_w2, pi_b2 are contiguous in both
+    if (f < F.act_b) return P::act_w + (f - F.act_w);
+    if (f < F.vf_w1) return P::act_b + (f - F.act_b);
+    if (f < F.vf_b1) return P::vf_w1 + ((f - F.vf_w1) / D) * DP + (f - F.vf_w1) % D;
+    return P::vf_b1 + (f - F.vf_b1); // vf_b1 .. val_b are contiguous in both
+}
+
+// tanh without branches (a lane-divergent libm call would run every path).  Below 0.625: x (1 + u P(u)), u = x^2, P a
+// degree-5 least-squares fit of (tanh(x) / x - 1) / u on Chebyshev nodes (error < 1e-10 in exact arithmetic, 4e-8 as
+// evaluated in float32).  Above: 1 - 2 q with q = 1 / (e^(2|x|) + 1) <= 0.223, so q's few ulp of relative error stay
+// below 1e-7 absolute (6e-8 measured on the host).  The device uses the hardware exp2 and reciprocal (1 ulp each).
+MSE_PPO_HD float ppo_tanh(float x)
+{
+    const float ax = fabsf(x);
+    const float u = x * x;
+    float poly = fmaf(u, 0.002142803743481636f, -0.008177093230187893f);
+    poly = fmaf(u, poly, 0.021700501441955566f);
+    poly = fmaf(u, poly, -0.05394670367240906f);
+    poly = fmaf(u, poly, 0.1333320587873459f);
+    poly = fmaf(u, poly, -0.3333333134651184f);
+    poly = fmaf(u * ax, poly, ax);
+    // z = 2 log2(e) |x| as z + zl: the product's rounding error (up to 2^-24 z) would otherwise reach e^(2|x|) whole
+    const float c_hi = 2.8853900432586670f, c_lo = 3.851925e-8f; // 2 log2(e) = c_hi + c_lo
+    const float ac = fminf(ax, 20.0f);                           // tanh(20) rounds to 1
+    const float z = ac * c_hi;
+    const float zl = fmaf(ac, c_lo, fmaf(ac, c_hi, -z)) * 0.6931471805599453f;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float e = __builtin_amdgcn_exp2f(z);
+    const float q = __builtin_amdgcn_rcpf(fmaf(e, zl, e) + 1.0f);
+#else
+    const float e = exp2f(z);
+    const float q = 1.0f / (fmaf(e, zl, e) + 1.0f);
+#endif
+    const float big = fmaf(-2.0f, q, 1.0f);
+    return copysignf(ax < 0.625f ? poly : big, x);
+}
+
+// ---- the 2 x 32 tanh MLP ------------------------------------------------------------------------------------------------
+template <int DP>
+MSE_PPO_HD void hidden_forward(const float *w1, const float *b1, const float *w2, const float *b2, const float (&x)[DP],
+                               float (&h1)[kH], float (&h2)[kH])
+{
+#pragma unroll
+    for (int o = 0; o < kH; ++o) {
+        float acc = b1[o];
+#pragma unroll
+        for (int i = 0; i < DP; ++i) acc = fmaf(w1[o * DP + i], x[i], acc);
+        h1[o] = ppo_tanh(acc);
+    }
+#pragma unroll
+    for (int o = 0; o < kH; ++o) {
+        float acc = b2[o];
+#pragma unroll
+        for (int i = 0; i < kH; ++i) acc = fmaf(w2[o * kH + i], h1[i], acc);
+        h2[o] = ppo_tanh(acc);
+    }
+}
+
+template <int NP>
+MSE_PPO_HD void head_forward(const float *w, const float *b, const float (&h2)[kH], float (&out)[NP])
+{
+#pragma unroll
+    for (int a = 0; a < NP; ++a) {
+        float acc = b[a];
+#pragma unroll
+        for (int i = 0; i < kH; ++i) acc = fmaf(w[a * kH + i], h2[i], acc);
+        out[a] = acc;
+    }
+}
+
+// delta of the layer below a linear map: dz[i] = (sum_o w[o][i] d[o]) (1 - h[i]^2)
+template <int NP>
+MSE_PPO_HD void backprop(const float *w, const float (&d)[NP], const float (&h)[kH], float (&dz)[kH])
+{
+    float dh[kH];
+#pragma unroll
+    for (int i = 0; i < kH; ++i) dh[i] = 0.0f;
+#pragma unroll
+    for (int o = 0; o < NP; ++o) {
+#pragma unroll
+        for (int i = 0; i < kH; ++i) dh[i] = fmaf(w[o * kH + i], d[o], dh[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < kH; ++i) dz[i] = dh[i] * fmaf(-h[i], h[i], 1.0f);
+}
+
+// ---- the heads: loss terms of one row and the gradient w.r.t. the head's outputs -----------------------------------------
+struct PolicyTerms {
+    float surrogate; // -min(adv ratio, adv clamp(ratio))
+    float entropy;   // -sum over legal actions of p log p
+    float kl;        // (ratio - 1) - log ratio
+    float clipped;   // |ratio - 1| > clip_range
+    float logp;      // log-probability of the action taken
+};
+
+// logit[a] (a < A real, the rest padding) -> terms; on return logit[] holds
+//   d/d logit of ( surrogate + ent_coef * (-entropy) ) * inv_b      (0 for illegal actions and for the padding).
+// legal: bit a set = action a may be taken.  torch.min splits a tie evenly and clamp passes the gradient on its closed
+// range, so the surrogate's derivative w.r.t. the ratio is adv wherever adv ratio <= adv clamp(ratio), else 0.
+template <int AP>
+MSE_PPO_HD PolicyTerms policy_head_terms(float (&logit)[AP], int A, uint32_t legal, int action, float old_logp, float adv,
+                                         const Params &P, float inv_b)
+{
+    float m = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        if (a < A) {
+            logit[a] = ((legal >> a) & 1u) ? logit[a] : kMaskedLogit;
+            m = fmaxf(m, logit[a]);
+        }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a)
+        if (a < A) s += expf(logit[a] - m);
+    const float lse = m + logf(s);
+    float p[AP];
+    float ent = 0.0f, mass = 0.0f, logp_act = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float lp = logit[a] - lse;
+        p[a] = ok ? expf(lp) : 0.0f;
+        logit[a] = ok ? lp : 0.0f; // now the log-probability
+        ent -= ok ? p[a] * lp : 0.0f;
+        mass += p[a];
+        if (a == action) logp_act = a < A ? lp : 0.0f; // (an illegal action keeps its -1e8-based log-probability)
+    }
+    PolicyTerms t;
+    t.logp = logp_act;
+    t.entropy = ent;
+    const float log_ratio = logp_act - old_logp;
+    const float ratio = expf(log_ratio);
+    const float clamped = fminf(fmaxf(ratio, 1.0f - P.clip_range), 1.0f + P.clip_range);
+    const float s1 = adv * ratio, s2 = adv * clamped;
+    t.surrogate = -fminf(s1, s2);
+    t.kl = (ratio - 1.0f) - log_ratio;
+    t.clipped = fabsf(ratio - 1.0f) > P.clip_range ? 1.0f : 0.0f;
+    const float g_logp = s1 <= s2 ? -(adv * ratio) * inv_b : 0.0f;
+    const float ge = P.ent_coef * inv_b, rest = mass - ent; // sum over legal a of p (log p + 1)
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float onehot = a == action ? 1.0f : 0.0f;
+        const float d = g_logp * (onehot - p[a]) + ge * (p[a] * (logit[a] + 1.0f) - p[a] * rest);
+        logit[a] = ok ? d : 0.0f;
+    }
+    return t;
+}
+
+// value -> squared error; dv = d/d value of vf_coef * (returns - value)^2 * inv_b
+MSE_PPO_HD float value_head_terms(float value, float ret, const Params &P, float inv_b, float &dv)
+{
+    const float e = value - ret;
+    dv = P.vf_coef * 2.0f * e * inv_b;
+    return e * e;
+}
+
+MSE_PPO_HD float normalized_advantage(float a, float mean, float std) { return (a - mean) / (std + 1e-8f); }
+
+} // namespace mseppo

@@ -1,0 +1,152 @@
+"""The learner's half of PPO on the device (SB3's `model.learn` -> `MaskablePPO.train`, src/training.py:191).
+
+`compute_gae` is `RolloutBuffer.compute_returns_and_advantage` on a collector's buffers (`mse_gae`), and
+`PPOLearner.update` is `MaskablePPO.train` on them: per minibatch one `mse_ppo_loss_grad` (loss, its statistics and
+the gradient w.r.t. all weights, three launches) and one `mse_ppo_adam_step` (clip_grad_norm_ + Adam), all enqueued
+without a host synchronisation; the new weights go back into the policy the rollout kernels read once per update
+(`MlpPolicy.load_weights`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
+computes anything on this path, and there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from ._lib import MsePpoParams, check, load_library
+from .policy import MlpPolicy
+
+STAT_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
+
+
+def _ptr(x):
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def compute_gae(data: dict, gamma: float = 0.99, gae_lambda: float = 0.95) -> dict:
+    """Adds `advantages` and `returns` f32[K, N] to a collector's dict (`rewards`, `values`, `episode_starts` [K, N],
+    `last_values`, `last_dones` [N], device tensors): SB3's compute_returns_and_advantage, bit for bit."""
+    r = data["rewards"]
+    if not r.is_cuda:
+        raise RuntimeError("compute_gae needs device tensors: there is no CPU fallback")
+    K, n = r.shape
+    L = load_library()
+    names = ("rewards", "values", "episode_starts", "last_values", "last_dones")
+    dtypes = (torch.float32, torch.float32, torch.uint8, torch.float32, torch.uint8)
+    t = [data[k].to(device=r.device, dtype=d).contiguous() for k, d in zip(names, dtypes)]
+    if tuple(t[1].shape) != (K, n) or tuple(t[2].shape) != (K, n) or tuple(t[3].shape) != (n,) or tuple(t[4].shape) != (n,):
+        raise ValueError("rollout buffers must be [K, N] with last_values / last_dones [N]")
+    adv = data.get("advantages")
+    ret = data.get("returns")
+    if adv is None or adv.shape != r.shape or adv.dtype != torch.float32 or not adv.is_contiguous():
+        adv = torch.empty_like(t[0])
+    if ret is None or ret.shape != r.shape or ret.dtype != torch.float32 or not ret.is_contiguous():
+        ret = torch.empty_like(t[0])
+    with torch.cuda.device(r.device):
+        check(L.mse_gae(K, n, _ptr(t[0]), _ptr(t[1]), _ptr(t[2]), _ptr(t[3]), _ptr(t[4]), float(gamma), float(gae_lambda),
+                        _ptr(adv), _ptr(ret), _stream(r.device)))
+    data["advantages"], data["returns"] = adv, ret
+    return data
+
+
+class PPOLearner:
+    """SB3's PPO defaults (the reference overrides ent_coef=0.05, src/training.py:115-131).  `batch_size=None`: 64 rows
+    per env-step-column is far too small for a 10^6-row rollout, so the default is K * N / 4 rounded up - pass SB3's 64
+    explicitly to reproduce its schedule."""
+
+    def __init__(self, policy: MlpPolicy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
+                 gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: float = 0.2, ent_coef: float = 0.0,
+                 vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
+                 seed: int = 0):
+        self.policy, self.L = policy, policy.L
+        self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
+        self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
+        self.max_grad_norm, self.adam_eps = float(max_grad_norm), float(adam_eps)
+        self.beta1, self.beta2 = 0.9, 0.999
+        self.params = MsePpoParams(C.sizeof(MsePpoParams), float(clip_range), float(ent_coef), float(vf_coef),
+                                   1 if normalize_advantage else 0)
+        self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
+        dev = policy.device
+        self.device = dev
+        self.n_weights = int(self.L.mse_policy_num_weights(policy.obs_dim, policy.n_actions))
+        self.weights = torch.from_numpy(policy.flat_weights()).to(dev)  # the flat f32 master copy the kernels train
+        self.grad = torch.zeros(self.n_weights, dtype=torch.float32, device=dev)
+        self.m = torch.zeros_like(self.grad)
+        self.v = torch.zeros_like(self.grad)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        ws = int(self.L.mse_ppo_workspace_bytes(policy.obs_dim, policy.n_actions))
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
+        self.step = 0  # Adam steps taken
+        self.last_permutations: list = []  # the CPU permutations of the last update(), one per epoch
+
+    def loss_grad(self, data: dict, rows: Optional[torch.Tensor], batch: int, stats_out: torch.Tensor,
+                  weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One `mse_ppo_loss_grad` on the flattened rollout in `data` (which holds advantages / returns); returns the
+        gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1."""
+        p = self.policy
+        obs = data["observations"]
+        n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
+        mask = data.get("action_masks")
+        w = self.weights if weights is None else weights
+        g = self.grad if grad_out is None else grad_out
+        for name in ("observations", "actions", "log_probs", "advantages", "returns"):
+            if not data[name].is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_loss_grad(p.obs_dim, p.n_actions, _ptr(w), n_rows, _ptr(rows), int(batch), _ptr(obs), _ptr(mask),
+                                           _ptr(data["actions"]), _ptr(data["log_probs"]), _ptr(data["advantages"]),
+                                           _ptr(data["returns"]), C.byref(self.params), _ptr(g), _ptr(stats_out),
+                                           _ptr(self.workspace), _stream(self.device)))
+        return g
+
+    def adam_step(self):
+        self.step += 1
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_adam_step(self.n_weights, _ptr(self.weights), _ptr(self.grad), _ptr(self.m), _ptr(self.v),
+                                           self.step, self.learning_rate, self.beta1, self.beta2, self.adam_eps,
+                                           self.max_grad_norm, _ptr(self.grad_norm), _stream(self.device)))
+
+    def update(self, data: dict) -> dict:
+        """GAE, then n_epochs passes over a seeded CPU permutation of the K * N rows (copied to the device once per epoch;
+        the last minibatch of an epoch may be short), one loss_grad + adam_step per minibatch without a host
+        synchronisation, then one `policy.load_weights`.  Returns {"stats": f32[n_minibatches, 8] (device; columns
+        STAT_NAMES), "mean": {name: float}}."""
+        compute_gae(data, self.gamma, self.gae_lambda)
+        K, n = data["rewards"].shape
+        total = K * n
+        bs = self.batch_size if self.batch_size is not None else (total + 3) // 4
+        bs = max(1, min(int(bs), total))
+        per_epoch = (total + bs - 1) // bs
+        stats = torch.zeros((self.n_epochs * per_epoch, 8), dtype=torch.float32, device=self.device)
+        self.last_permutations = []
+        i = 0
+        for _ in range(self.n_epochs):
+            perm_cpu = torch.randperm(total, generator=self.generator)
+            self.last_permutations.append(perm_cpu)
+            perm = perm_cpu.to(self.device)
+            for start in range(0, total, bs):
+                rows = perm[start:start + bs]
+                self.loss_grad(data, rows, rows.numel(), stats[i])
+                self.adam_step()
+                i += 1
+        self.policy.load_weights(self.weights)  # the device-to-host copy waits for the stream
+        mean = stats.mean(dim=0).cpu().tolist()
+        return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+
+    def learn(self, collector, iterations: int, callback=None) -> list:
+        """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
+        mean reward per env-step under "reward"."""
+        history = []
+        for it in range(int(iterations)):
+            data = collector.collect()
+            out = self.update(data)
+            rec = dict(out["mean"], reward=float(data["rewards"].mean()))
+            history.append(rec)
+            if callback is not None:
+                callback(it, rec)
+        return history

@@ -96,6 +96,45 @@ class MlpPolicy:
                 w[key] = (rng.standard_normal(shape) * gain / np.sqrt(shape[1])).astype(np.float32)
         return cls(obs_dim, n_actions, w, device=device, library=library, precision=precision)
 
+    def load_weights(self, weights) -> "MlpPolicy":
+        """Replaces the weights in place (`mse_policy_set_weights`: the same host repacking as at creation, then a
+        blocking copy).  `weights`: a mapping under SB3_KEYS, or the flat vector in that order (array / tensor, any
+        device).  No rollout or forward on this policy may be in flight on another stream.  Refreshes `self.weights`
+        and `self.precision` (an "auto" policy moves to f32 when a folded weight leaves f16's range)."""
+        shapes = _shapes(self.obs_dim, self.n_actions)
+        if isinstance(weights, Mapping):
+            parts = []
+            for key, shape in zip(SB3_KEYS, shapes):
+                if key not in weights:
+                    raise KeyError(f"missing weight {key!r}")
+                w = weights[key]
+                w = w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else np.asarray(w)
+                if tuple(w.shape) != tuple(shape):
+                    raise ValueError(f"{key}: shape {tuple(w.shape)}, expected {tuple(shape)}")
+                parts.append(np.ascontiguousarray(w, dtype=np.float32).ravel())
+            blob = np.concatenate(parts)
+        else:
+            w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)
+            blob = np.ascontiguousarray(w, dtype=np.float32).ravel()
+        n = self.L.mse_policy_num_weights(self.obs_dim, self.n_actions)
+        if blob.size != n:
+            raise ValueError(f"expected {n} weights, got {blob.size}")
+        check(self.L.mse_policy_set_weights(self._h, blob.ctypes.data_as(C.POINTER(C.c_float))))
+        sizes = [int(np.prod(s)) for s in shapes]
+        self.weights = {k: p.copy() for k, p in zip(SB3_KEYS, np.split(blob, np.cumsum(sizes)[:-1]))}
+        self.precision = "f16x3" if self.L.mse_policy_precision(self._h) == 2 else "f32"
+        return self
+
+    def flat_weights(self) -> np.ndarray:
+        """The weights as one float32 vector in the order of include/mse.h (SB3_KEYS)."""
+        return np.concatenate([self.weights[k].ravel() for k in SB3_KEYS])
+
+    def state_dict(self) -> dict:
+        """CPU torch tensors under SB3's state_dict names and shapes: `torch.save` it, or load it into the
+        `mlp_extractor` / `action_net` / `value_net` of an SB3 (Maskable)ActorCriticPolicy elsewhere."""
+        return {k: torch.from_numpy(self.weights[k].reshape(s).copy())
+                for k, s in zip(SB3_KEYS, _shapes(self.obs_dim, self.n_actions))}
+
     def close(self):
         if getattr(self, "_h", None):
             self.L.mse_policy_destroy(self._h)

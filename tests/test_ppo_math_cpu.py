@@ -1,0 +1,280 @@
+"""CPU checks of the PPO learner's arithmetic and ABI (no device needed).
+
+marl-sortingenv_amd/csrc/mse_ppo_math.h is compiled on the host as it is, through the shim below (which composes the
+header's per-row pieces exactly as k_ppo_grad does, summing the outer products row after row in float32), and held
+against tests/ppo_reference.py: float64 autograd for the loss, its statistics and its gradient, numpy float32 for
+the GAE loop (bit-equal).  Tolerances: the rule in tests/ppo_reference.py (4 x the error of torch's own float32
+evaluation, computed each run)."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import marl_sortingenv_amd as M
+from marl_sortingenv_amd._lib import EXPORTS, MsePpoParams
+from tests import ppo_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "marl-sortingenv_amd", "csrc")
+
+SHIM = r"""
+#include "mse_ppo_math.h"
+#include <vector>
+using namespace mseppo;
+
+template <int N>
+static void outer(float *gw, float *gb, const float *d, int n_out, const float *a, int ld)
+{
+    for (int o = 0; o < n_out; ++o) {
+        for (int i = 0; i < N; ++i) gw[o * ld + i] = fmaf(d[o], a[i], gw[o * ld + i]);
+        gb[o] += d[o];
+    }
+}
+
+template <int DP, int AP>
+static void run(int D, int A, const float *wflat, long B, const float *obs, const unsigned char *mask, const int *act,
+                const float *old_logp, const float *adv, const float *ret, Params P, float *grad, double *stats)
+{
+    typedef Padded<DP, AP> PW;
+    const Flat F = flat_layout(D, A);
+    std::vector<float> w(PW::total, 0.0f), g(PW::total, 0.0f);
+    for (int f = 0; f < F.total; ++f) w[padded_index<DP, AP>(f, D, A)] = wflat[f];
+    float mean = 0.0f, std = 1.0f;
+    const bool normalize = P.normalize_advantage != 0 && B > 1;
+    if (normalize) {
+        double s = 0.0, q = 0.0;
+        for (long b = 0; b < B; ++b) s += adv[b];
+        for (long b = 0; b < B; ++b) q += (adv[b] - s / B) * (adv[b] - s / B);
+        mean = (float)(s / B);
+        std = (float)sqrt(q / (B - 1));
+    }
+    const float inv_b = 1.0f / (float)B;
+    double sums[5] = {0, 0, 0, 0, 0};
+    for (long b = 0; b < B; ++b) {
+        float x[DP];
+        for (int i = 0; i < DP; ++i) x[i] = i < D ? obs[b * D + i] : 0.0f;
+        unsigned legal = 0;
+        for (int a = 0; a < A; ++a) legal |= (mask == nullptr || mask[b * A + a] ? 1u : 0u) << a;
+        const float a_used = normalize ? normalized_advantage(adv[b], mean, std) : adv[b];
+        float h1[kH], h2[kH], dz2[kH], dz1[kH], dl[AP];
+        hidden_forward<DP>(&w[PW::pi_w1], &w[PW::pi_b1], &w[PW::pi_w2], &w[PW::pi_b2], x, h1, h2);
+        head_forward<AP>(&w[PW::act_w], &w[PW::act_b], h2, dl);
+        const PolicyTerms t = policy_head_terms<AP>(dl, A, legal, act[b], old_logp[b], a_used, P, inv_b);
+        sums[0] += t.surrogate; sums[2] += t.entropy; sums[3] += t.kl; sums[4] += t.clipped;
+        outer<kH>(&g[PW::act_w], &g[PW::act_b], dl, AP, h2, kH);
+        backprop<AP>(&w[PW::act_w], dl, h2, dz2);
+        outer<kH>(&g[PW::pi_w2], &g[PW::pi_b2], dz2, kH, h1, kH);
+        backprop<kH>(&w[PW::pi_w2], dz2, h1, dz1);
+        outer<DP>(&g[PW::pi_w1], &g[PW::pi_b1], dz1, kH, x, DP);
+        hidden_forward<DP>(&w[PW::vf_w1], &w[PW::vf_b1], &w[PW::vf_w2], &w[PW::vf_b2], x, h1, h2);
+        float v[1], dv[1];
+        head_forward<1>(&w[PW::val_w], &w[PW::val_b], h2, v);
+        sums[1] += value_head_terms(v[0], ret[b], P, inv_b, dv[0]);
+        outer<kH>(&g[PW::val_w], &g[PW::val_b], dv, 1, h2, kH);
+        backprop<1>(&w[PW::val_w], dv, h2, dz2);
+        outer<kH>(&g[PW::vf_w2], &g[PW::vf_b2], dz2, kH, h1, kH);
+        backprop<kH>(&w[PW::vf_w2], dz2, h1, dz1);
+        outer<DP>(&g[PW::vf_w1], &g[PW::vf_b1], dz1, kH, x, DP);
+    }
+    for (int f = 0; f < F.total; ++f) grad[f] = g[padded_index<DP, AP>(f, D, A)];
+    const double pl = sums[0] / B, vl = sums[1] / B, el = -sums[2] / B;
+    stats[0] = pl + P.ent_coef * el + P.vf_coef * vl; stats[1] = pl; stats[2] = vl; stats[3] = el;
+    stats[4] = sums[3] / B; stats[5] = sums[4] / B; stats[6] = mean; stats[7] = std;
+}
+
+extern "C" {
+int ppo_rows(int D, int A, const float *wflat, long B, const float *obs, const unsigned char *mask, const int *act,
+             const float *old_logp, const float *adv, const float *ret, float clip, float ent, float vf, int norm,
+             float *grad, double *stats)
+{
+    Params P{clip, ent, vf, norm};
+    if (D == 13 && A == 2) run<16, 4>(D, A, wflat, B, obs, mask, act, old_logp, adv, ret, P, grad, stats);
+    else if (D == 16 && A == 11) run<16, 12>(D, A, wflat, B, obs, mask, act, old_logp, adv, ret, P, grad, stats);
+    else if (D == 29 && A == 22) run<32, 24>(D, A, wflat, B, obs, mask, act, old_logp, adv, ret, P, grad, stats);
+    else return -1;
+    return 0;
+}
+void gae(int K, long n, const float *r, const float *v, const unsigned char *es, const float *lv, const unsigned char *ld,
+         double gamma, double lam, float *adv, float *ret)
+{
+    for (long i = 0; i < n; ++i) gae_column(K, n, i, r, v, es, lv, ld, (float)gamma, (float)(gamma * lam), adv, ret);
+}
+float tanh_host(float x) { return ppo_tanh(x); }
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.fail("no host C++ compiler to build the mse_ppo_math.h shim")
+    d = tmp_path_factory.mktemp("ppo")
+    src, so = d / "shim.cpp", d / "shim.so"
+    src.write_text(SHIM)
+    subprocess.run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-I", CSRC,
+                    str(src), "-o", str(so)], check=True)
+    L = C.CDLL(str(so))
+    L.tanh_host.restype = C.c_float
+    L.tanh_host.argtypes = [C.c_float]
+    return L
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def make_rows(D, A, B, seed, flat, masked):
+    """B rows whose first ones are the edge cases: a single legal action; ratios clipped below / above the range with
+    advantages of both signs; a ratio inside the range."""
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.rand((B, D), generator=g) * 2.0 - 1.0
+    mask = torch.rand((B, A), generator=g) < 0.6
+    mask[:, 0] = True
+    if B > 0:
+        mask[0] = False
+        mask[0, 0] = True  # a single legal action
+    mk = mask if masked else None
+    with torch.no_grad():
+        logsm, value = R.forward(flat.double(), D, A, obs.double(), mk)
+    legal = mask if masked else torch.ones_like(mask)
+    actions = torch.multinomial(legal.float(), 1, generator=g).squeeze(1).int()
+    logp = logsm.gather(1, actions.long().unsqueeze(1)).squeeze(1)
+    # old log-probabilities: the ratio exp(logp - old) spread over [0.6, 1.5], so both clip sides and the inside occur
+    log_ratio = torch.log(torch.rand(B, generator=g, dtype=torch.float64) * 0.9 + 0.6)
+    for i, lr in enumerate([0.0, np.log(0.5), np.log(0.5), np.log(1.6), np.log(1.6), np.log(1.05), np.log(0.95)][:B]):
+        log_ratio[i] = lr
+    old_logp = (logp - log_ratio).float()
+    adv = torch.randn(B, generator=g) * 1.5 + 0.3
+    for i, a in enumerate([0.7, 1.0, -1.0, 1.0, -1.0, 1.0, -1.0][:B]):
+        adv[i] = a
+    # returns at least 0.5 away from the value: with B = 1 the whole value-net gradient is proportional to the single
+    # difference (value - returns), and a draw with |value - returns| = 0.18 turned the check into a comparison of two
+    # float32 roundings of one scalar (header 2.5 ulp off in the value, torch's float32 0.4 ulp: 1.7e-6 against a bound
+    # of 1.3e-6) - cancellation luck, not arithmetic.  Applied to every row alike.
+    noise = torch.randn(B, generator=g, dtype=torch.float64) * 0.5
+    ret = (value + torch.where(noise < 0, noise - 0.5, noise + 0.5)).float()
+    return obs, mask, mk, actions, old_logp, adv, ret
+
+
+def run_shim(shim, D, A, flat, obs, mk, actions, old_logp, adv, ret, hp):
+    B = obs.shape[0]
+    grad = np.zeros(R.num_weights(D, A), np.float32)
+    stats = np.zeros(8, np.float64)
+    m8 = None if mk is None else np.ascontiguousarray(mk.numpy().astype(np.uint8))
+    rc = shim.ppo_rows(D, A, _p(flat.numpy()), C.c_long(B), _p(np.ascontiguousarray(obs.numpy())), _p(m8),
+                       _p(actions.numpy()), _p(old_logp.numpy()), _p(adv.numpy()), _p(ret.numpy()),
+                       C.c_float(hp["clip_range"]), C.c_float(hp["ent_coef"]), C.c_float(hp["vf_coef"]), 1, _p(grad), _p(stats))
+    assert rc == 0
+    return torch.from_numpy(grad), torch.from_numpy(stats)
+
+
+HP = dict(clip_range=0.2, ent_coef=0.05, vf_coef=0.5)
+
+
+@pytest.mark.parametrize("masked", [True, False])
+@pytest.mark.parametrize("B", [300, 1, 2])
+@pytest.mark.parametrize("D,A", [(13, 2), (16, 11), (29, 22)])
+def test_header_loss_and_gradient_match_float64_autograd(shim, D, A, B, masked):
+    flat = R.random_flat(D, A, seed=D * 100 + A)
+    obs, mask, mk, actions, old_logp, adv, ret = make_rows(D, A, B, seed=7 + B, flat=flat, masked=masked)
+    args = (D, A, obs, mk, actions, old_logp, adv, ret, HP["clip_range"], HP["ent_coef"], HP["vf_coef"])
+    g64, s64 = R.loss_and_grad(flat, torch.float64, *args)
+    g32, s32 = R.loss_and_grad(flat, torch.float32, *args)
+    if B >= 300:  # the edge rows are what they claim to be
+        ratio = torch.exp(R.forward(flat.double(), D, A, obs.double(), mk)[0].gather(1, actions.long().unsqueeze(1)).squeeze(1)
+                          - old_logp.double())
+        assert float(ratio[1]) < 0.8 and float(ratio[3]) > 1.2 and 0.8 < float(ratio[5]) < 1.2
+        assert float(s64[5]) > 0.1  # clip fraction
+        if masked:
+            assert int(mask[0].sum()) == 1
+    g, s = run_shim(shim, D, A, flat, obs, mk, actions, old_logp, adv, ret, HP)
+    scale, allowed = R.grad_bound(g64, g32)
+    err = float((g.double() - g64).abs().max()) / scale
+    print(f"D={D} A={A} B={B} masked={masked}: header grad err {err:.3e}, f32 yardstick {allowed / 4:.3e} (allowed {allowed:.3e})")
+    assert err <= allowed
+    assert np.all(np.abs((s - s64).numpy()) <= R.stats_bound(s64, s32)), (s, s64)
+    if B == 1:
+        assert float(s[6]) == 0.0 and float(s[7]) == 1.0  # not normalised
+
+
+def test_header_tanh_accuracy(shim):
+    x = np.concatenate([np.linspace(-12, 12, 200001), np.linspace(-0.3, 0.3, 100001), [0.0, 25.0, -25.0, 88.0, 1e-20]]).astype(np.float32)
+    got = np.array([shim.tanh_host(float(v)) for v in x[::7]], dtype=np.float64)
+    assert np.max(np.abs(got - np.tanh(x[::7].astype(np.float64)))) < 1.2e-7
+
+
+@pytest.mark.parametrize("K,n", [(16, 257), (1, 5), (7, 1)])
+def test_header_gae_is_bit_equal_to_sb3_loop(shim, K, n):
+    rng = np.random.default_rng(K * 1000 + n)
+    r = rng.standard_normal((K, n)).astype(np.float32)
+    v = rng.standard_normal((K, n)).astype(np.float32)
+    es = (rng.random((K, n)) < 0.2).astype(np.uint8)
+    es[0, :] = 1              # every env starts an episode at k = 0
+    es[K - 1, ::2] = 1        # ... some at the last step
+    if K > 3:
+        es[2:4, 1::3] = 1     # ... and in consecutive steps
+    lv = rng.standard_normal(n).astype(np.float32)
+    ld = (rng.random(n) < 0.5).astype(np.uint8)
+    ld[0] = 1
+    for gamma, lam in ((0.99, 0.95), (0.9, 1.0), (1.0, 0.0)):
+        adv, ret = np.empty_like(r), np.empty_like(r)
+        shim.gae(K, C.c_long(n), _p(r), _p(v), _p(es), _p(lv), _p(ld), C.c_double(gamma), C.c_double(lam), _p(adv), _p(ret))
+        ea, er = R.gae_numpy(r, v, es, lv, ld, gamma, lam)
+        assert np.array_equal(adv.view(np.uint32), ea.view(np.uint32))
+        assert np.array_equal(ret.view(np.uint32), er.view(np.uint32))
+
+
+def test_ppo_abi_without_a_device():
+    L = M.load_library()
+    for name in ("mse_gae", "mse_ppo_loss_grad", "mse_ppo_workspace_bytes", "mse_ppo_adam_step", "mse_policy_set_weights"):
+        assert hasattr(L, name) and name in EXPORTS
+    INVALID = -1
+    one = C.c_void_p(16)  # a non-null pointer that is never followed: every call below fails its argument checks
+    assert L.mse_gae(4, 8, None, one, one, one, one, 0.99, 0.95, one, one, None) == INVALID
+    assert b"mse_gae" in L.mse_last_error()
+    assert L.mse_gae(0, 8, one, one, one, one, one, 0.99, 0.95, one, one, None) == INVALID
+    assert L.mse_gae(4, -1, one, one, one, one, one, 0.99, 0.95, one, one, None) == INVALID
+    assert L.mse_gae(4, 8, one, one, one, one, one, 1.5, 0.95, one, one, None) == INVALID
+    p = MsePpoParams(C.sizeof(MsePpoParams), 0.2, 0.0, 0.5, 1)
+    ok = [29, 22, one, 64, None, 64, one, None, one, one, one, one, C.byref(p), one, one, one, None]
+
+    def call(**change):
+        a = list(ok)
+        for k, v in change.items():
+            a[int(k[1:])] = v
+        return L.mse_ppo_loss_grad(*a)
+
+    assert call(a2=None) == INVALID and b"mse_ppo_loss_grad" in L.mse_last_error()
+    assert call(a0=0) == INVALID and call(a1=33) == INVALID
+    assert call(a3=-1) == INVALID and call(a5=0) == INVALID
+    assert call(a5=65) == INVALID  # batch > n_rows without rows_dev
+    assert call(a13=None) == INVALID and call(a14=None) == INVALID and call(a15=None) == INVALID
+    bad = MsePpoParams(3, 0.2, 0.0, 0.5, 1)
+    assert call(a12=C.byref(bad)) == INVALID
+    neg = MsePpoParams(C.sizeof(MsePpoParams), -0.1, 0.0, 0.5, 1)
+    assert call(a12=C.byref(neg)) == INVALID
+    assert L.mse_ppo_adam_step(0, one, one, one, one, 1, 3e-4, 0.9, 0.999, 1e-5, 0.5, None, None) == INVALID
+    assert L.mse_ppo_adam_step(10, None, one, one, one, 1, 3e-4, 0.9, 0.999, 1e-5, 0.5, None, None) == INVALID
+    assert L.mse_ppo_adam_step(10, one, one, one, one, 0, 3e-4, 0.9, 0.999, 1e-5, 0.5, None, None) == INVALID
+    assert L.mse_ppo_adam_step(10, one, one, one, one, 1, 3e-4, 1.0, 0.999, 1e-5, 0.5, None, None) == INVALID
+    assert L.mse_policy_set_weights(None, None) == INVALID
+    small, mid, big = (L.mse_ppo_workspace_bytes(13, 2), L.mse_ppo_workspace_bytes(16, 11), L.mse_ppo_workspace_bytes(29, 22))
+    assert 0 < small < mid < big
+    assert L.mse_ppo_workspace_bytes(0, 2) == 0 and L.mse_ppo_workspace_bytes(29, 33) == 0
+    assert big >= 4 * L.mse_policy_num_weights(29, 22)
+
+
+def test_compute_gae_has_no_cpu_fallback():
+    from marl_sortingenv_amd import compute_gae
+
+    K, n = 4, 8
+    data = {"rewards": torch.zeros(K, n), "values": torch.zeros(K, n), "episode_starts": torch.zeros(K, n, dtype=torch.uint8),
+            "last_values": torch.zeros(n), "last_dones": torch.zeros(n, dtype=torch.uint8)}
+    with pytest.raises(RuntimeError):
+        compute_gae(data)
+    assert M.PPOLearner is not None and hasattr(M.MlpPolicy, "load_weights") and hasattr(M.MlpPolicy, "state_dict")

@@ -1,0 +1,139 @@
+"""Train one of the three envs with the on-device PPO learner, from MlpPolicy.random_init.
+
+    python tools/train_ppo.py --kind mono --envs 4096 --steps 16 --iterations 20
+    python tools/train_ppo.py --kind mono --time          # rows/s of mse_ppo_loss_grad beside torch f32 autograd
+
+Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import marl_sortingenv_amd as M  # noqa: E402
+from marl_sortingenv_amd.policy import _shapes  # noqa: E402
+
+KINDS = {"sort": "Env_1_Sorting", "press": "Env_2_Pressing", "mono": "Env_3_Monolith"}
+
+
+def torch_loss(w, D, A, obs, mask, actions, old_logp, adv, ret, clip, ent_coef, vf_coef):
+    """MaskablePPO.train's loss for one minibatch in torch ops on the tensors' device (f32)."""
+    import torch.nn.functional as F
+
+    parts, at = [], 0
+    for s in _shapes(D, A):
+        n = 1
+        for v in s:
+            n *= v
+        parts.append(w[at:at + n].reshape(s))
+        at += n
+    w1, b1, w2, b2, wa, ba, v1, c1, v2, c2, wv, bv = parts
+    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+    hp = torch.tanh(F.linear(torch.tanh(F.linear(obs, w1, b1)), w2, b2))
+    hv = torch.tanh(F.linear(torch.tanh(F.linear(obs, v1, c1)), v2, c2))
+    logits = torch.where(mask, F.linear(hp, wa, ba), torch.tensor(-1e8, device=obs.device))
+    logsm = torch.log_softmax(logits, dim=1)
+    logp = logsm.gather(1, actions.long().unsqueeze(1)).squeeze(1)
+    ratio = torch.exp(logp - old_logp)
+    pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip, 1 + clip)).mean()
+    vl = F.mse_loss(ret, F.linear(hv, wv, bv).squeeze(1))
+    el = torch.where(mask, logsm * logsm.exp(), torch.zeros((), device=obs.device)).sum(dim=1).mean()
+    return pl + ent_coef * el + vf_coef * vl
+
+
+def time_loss_grad(args):
+    D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
+    pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+    for n in (256, 4096, 65536):
+        K = 16
+        env = M.BatchedSortingEnv(kind=args.kind, num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+        col = M.FusedPolicyRollout(env, pol, K, seed=args.seed)
+        learner = M.PPOLearner(pol, ent_coef=0.05)
+        data = M.compute_gae(col.collect())
+        rows = K * n
+        stats = torch.zeros(8, device="cuda")
+
+        def fused():
+            learner.loss_grad(data, None, rows, stats)
+
+        flat = [data[k].reshape(rows, -1) if data[k].dim() == 3 else data[k].reshape(rows)
+                for k in ("observations", "action_masks", "actions", "log_probs", "advantages", "returns")]
+        flat[1] = flat[1].bool()
+        w = learner.weights.clone().requires_grad_(True)
+
+        def autograd():
+            w.grad = None
+            torch_loss(w, D, A, *flat, 0.2, 0.05, 0.5).backward()
+
+        res = {}
+        for name, fn in (("mse_ppo_loss_grad", fused), ("torch f32 autograd", autograd)):
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            reps = 20 if rows <= 65536 else 5
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            res[name] = (time.perf_counter() - t0) / reps
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(20):
+            M.compute_gae(data)
+        torch.cuda.synchronize()
+        t_gae = (time.perf_counter() - t0) / 20
+        print(f"{args.kind} rows={rows}: mse_gae {t_gae * 1e6:.1f} us = {17 * rows / t_gae / 1e9:.0f} GB/s of its 17 B/row")
+        # one update() beside the collect() that feeds it
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        col.collect()
+        torch.cuda.synchronize()
+        t_col = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        learner.update(data)
+        torch.cuda.synchronize()
+        t_upd = time.perf_counter() - t0
+        print(f"{args.kind} rows={rows}: " + ", ".join(f"{k} {v * 1e6:.1f} us ({rows / v / 1e6:.1f} M rows/s)" for k, v in res.items())
+              + f"; collect {t_col * 1e6:.0f} us, update (10 epochs x 4 minibatches) {t_upd * 1e3:.2f} ms")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=sorted(KINDS), default="mono")
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=16)
+    ap.add_argument("--iterations", type=int, default=20)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--ent-coef", type=float, default=0.05)
+    ap.add_argument("--max-steps", type=int, default=50)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--time", action="store_true")
+    ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
+    args = ap.parse_args()
+    if args.time:
+        return time_loss_grad(args)
+    D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
+    pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+    env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
+                              auto_reset=True)
+    col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
+    learner = M.PPOLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
+                           seed=args.seed)
+    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration")
+
+    def show(it, rec):
+        print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
+              f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
+
+    learner.learn(col, args.iterations, callback=show)
+    if args.save:
+        torch.save(pol.state_dict(), args.save)
+
+
+if __name__ == "__main__":
+    main()
