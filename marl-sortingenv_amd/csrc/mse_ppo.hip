@@ -375,6 +375,9 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
 struct AdamArgs {
     int n;
     float lr_over_bc1, inv_sqrt_bc2, beta1, beta2, eps, max_norm;
+    // 1 - beta, formed in double on the host and rounded once, as torch's addcmul_(value = 1 - beta2) does (the float32
+    // difference 1.0f - 0.999f is 1.3e-5 below 0.001)
+    float one_minus_beta1, one_minus_beta2;
 };
 
 __global__ __launch_bounds__(1024) void k_ppo_adam(AdamArgs a, float *__restrict__ w, const float *__restrict__ grad,
@@ -395,8 +398,8 @@ __global__ __launch_bounds__(1024) void k_ppo_adam(AdamArgs a, float *__restrict
     if (threadIdx.x == 0 && norm_out != nullptr) norm_out[0] = norm;
     for (int i = threadIdx.x; i < a.n; i += 1024) {
         const float g = grad[i] * coef;
-        const float mi = a.beta1 * m[i] + (1.0f - a.beta1) * g;
-        const float vi = a.beta2 * v[i] + (1.0f - a.beta2) * g * g;
+        const float mi = a.beta1 * m[i] + a.one_minus_beta1 * g;
+        const float vi = a.beta2 * v[i] + a.one_minus_beta2 * g * g;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) * a.inv_sqrt_bc2 + a.eps;
@@ -488,13 +491,10 @@ int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int6
     long long n_slabs = (tiles + 1) / 2;
     const long long cap = 2LL * cus < kMaxSlabs ? 2LL * cus : kMaxSlabs;
     if (n_slabs > cap) n_slabs = cap;
-    // four shapes: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
+    // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
 #define MSE_PPO_LAUNCH(DP, AP) \
     launch_grad<DP, AP>(G, (int)n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs)
-    if (obs_dim <= 16 && n_actions <= 4) MSE_PPO_LAUNCH(16, 4);
-    else if (obs_dim <= 16 && n_actions <= 12) MSE_PPO_LAUNCH(16, 12);
-    else if (n_actions <= 24) MSE_PPO_LAUNCH(32, 24);
-    else MSE_PPO_LAUNCH(32, 32);
+    MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
 #undef MSE_PPO_LAUNCH
     const int w_total = flat_layout(obs_dim, n_actions).total;
     hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)n_slabs, w_total, slabs, rows,
@@ -514,7 +514,7 @@ int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, floa
         return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: bad lr / beta / eps");
     const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
     AdamArgs a{(int)n_weights, (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2)), (float)beta1, (float)beta2, (float)eps,
-               (float)max_grad_norm};
+               (float)max_grad_norm, (float)(1.0 - beta1), (float)(1.0 - beta2)};
     hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, weights, grad, m, v, grad_norm_out);
     if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_adam_step: kernel launch failed");
     return MSE_OK;

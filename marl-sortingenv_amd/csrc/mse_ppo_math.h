@@ -118,6 +118,37 @@ MSE_PPO_HD int padded_index(int f, int D, int A)
     return P::vf_b1 + (f - F.vf_b1); // vf_b1 .. val_b are contiguous in both
 }
 
+// ---- which instantiation of the gradient kernel a policy shape gets -----------------------------------------------------
+// Four padded shapes (DP, AP) are compiled: Env_1 (13 -> 2) in (16, 4), Env_2 (16 -> 11) in (16, 12), Env_3 (29 -> 22) in
+// (32, 24) and the general (32, 32).  mse_ppo_loss_grad and the host shim of tests/test_ppo_math_cpu.py both ask this
+// function and dispatch through MSE_PPO_DISPATCH, so the two cannot drift apart (mse_plan.h does the same for rollouts).
+enum GradShape { kShape16x4 = 0, kShape16x12 = 1, kShape32x24 = 2, kShape32x32 = 3, kShapeNone = -1 };
+
+MSE_PPO_HD GradShape select_grad_shape(int D, int A) // 1 <= D, A <= 32, else kShapeNone
+{
+    if (D < 1 || D > 32 || A < 1 || A > 32) return kShapeNone;
+    if (D <= 16 && A <= 4) return kShape16x4;
+    if (D <= 16 && A <= 12) return kShape16x12;
+    if (A <= 24) return kShape32x24;
+    return kShape32x32;
+}
+
+MSE_PPO_HD void grad_shape_dims(GradShape s, int &dp, int &ap)
+{
+    dp = (s == kShape16x4 || s == kShape16x12) ? 16 : 32;
+    ap = s == kShape16x4 ? 4 : s == kShape16x12 ? 12 : s == kShape32x24 ? 24 : 32;
+}
+
+// MSE_PPO_DISPATCH(shape, CALL): expands CALL(DP, AP) for the instantiation `shape` names; nothing for kShapeNone
+#define MSE_PPO_DISPATCH(shape, CALL)                          \
+    switch (shape) {                                           \
+    case ::mseppo::kShape16x4: CALL(16, 4); break;             \
+    case ::mseppo::kShape16x12: CALL(16, 12); break;           \
+    case ::mseppo::kShape32x24: CALL(32, 24); break;           \
+    case ::mseppo::kShape32x32: CALL(32, 32); break;           \
+    default: break;                                            \
+    }
+
 // tanh without branches (a lane-divergent libm call would run every path).  Below 0.625: x (1 + u P(u)), u = x^2, P a
 // degree-5 least-squares fit of (tanh(x) / x - 1) / u on Chebyshev nodes (error < 1e-10 in exact arithmetic, 4e-8 as
 // evaluated in float32).  Above: 1 - 2 q with q = 1 / (e^(2|x|) + 1) <= 0.223, so q's few ulp of relative error stay

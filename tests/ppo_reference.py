@@ -68,6 +68,40 @@ def forward(flat, D, A, obs, mask):
     return torch.log_softmax(logits, dim=1), F.linear(hv, wv, bv).squeeze(1)
 
 
+def make_rows(D, A, B, seed, flat, masked):
+    """B rows whose first ones are the edge cases: a single legal action; ratios clipped below / above the range with
+    advantages of both signs; a ratio inside the range.  -> obs f32[B, D], mask bool[B, A], mask or None (what the
+    loss is given), actions i32[B], old_logp, adv, ret f32[B]."""
+    g = torch.Generator().manual_seed(seed)
+    obs = torch.rand((B, D), generator=g) * 2.0 - 1.0
+    mask = torch.rand((B, A), generator=g) < 0.6
+    mask[:, 0] = True
+    if B > 0:
+        mask[0] = False
+        mask[0, 0] = True  # a single legal action
+    mk = mask if masked else None
+    with torch.no_grad():
+        logsm, value = forward(flat.double(), D, A, obs.double(), mk)
+    legal = mask if masked else torch.ones_like(mask)
+    actions = torch.multinomial(legal.float(), 1, generator=g).squeeze(1).int()
+    logp = logsm.gather(1, actions.long().unsqueeze(1)).squeeze(1)
+    # old log-probabilities: the ratio exp(logp - old) spread over [0.6, 1.5], so both clip sides and the inside occur
+    log_ratio = torch.log(torch.rand(B, generator=g, dtype=torch.float64) * 0.9 + 0.6)
+    for i, lr in enumerate([0.0, np.log(0.5), np.log(0.5), np.log(1.6), np.log(1.6), np.log(1.05), np.log(0.95)][:B]):
+        log_ratio[i] = lr
+    old_logp = (logp - log_ratio).float()
+    adv = torch.randn(B, generator=g) * 1.5 + 0.3
+    for i, a in enumerate([0.7, 1.0, -1.0, 1.0, -1.0, 1.0, -1.0][:B]):
+        adv[i] = a
+    # returns at least 0.5 away from the value: with B = 1 the whole value-net gradient is proportional to the single
+    # difference (value - returns), and a draw with |value - returns| = 0.18 turned the check into a comparison of two
+    # float32 roundings of one scalar (header 2.5 ulp off in the value, torch's float32 0.4 ulp: 1.7e-6 against a bound
+    # of 1.3e-6) - cancellation luck, not arithmetic.  Applied to every row alike.
+    noise = torch.randn(B, generator=g, dtype=torch.float64) * 0.5
+    ret = (value + torch.where(noise < 0, noise - 0.5, noise + 0.5)).float()
+    return obs, mask, mk, actions, old_logp, adv, ret
+
+
 def ppo_loss(flat, D, A, obs, mask, actions, old_logp, adv, ret, clip_range, ent_coef, vf_coef, normalize=True):
     """MaskablePPO.train for one minibatch -> (loss, stats[8]) in flat's dtype.  mask: bool [B, A] or None."""
     dt = flat.dtype
@@ -110,8 +144,10 @@ def grad_bound(g64, g32):
     return scale, 4.0 * float((g32.double() - g64).abs().max()) / scale
 
 
-def stats_bound(s64, s32):
-    e32 = float((s32.double() - s64).abs().max())
+def stats_bound(s64, s32, e32_others=0.0):
+    """e32_others (B <= 2 only, where one evaluation's float32 error is a single draw of a heavy-tailed quantity): the
+    largest float32 error of the statistics among evaluations of the same size on other rows - torch alone."""
+    e32 = max(float((s32.double() - s64).abs().max()), e32_others)
     return 4.0 * e32 + 4.0 * float(np.finfo(np.float32).eps) * np.maximum(1.0, np.abs(s64.numpy()))
 
 
@@ -138,10 +174,16 @@ def gae_numpy(rewards, values, episode_starts, last_values, last_dones, gamma, g
     return advantages, returns
 
 
-def adam_reference(w0, grads, lr, eps, max_grad_norm, dtype=torch.float64):
-    """clip_grad_norm_ + torch.optim.Adam over the gradient sequence -> list of weights after each step, norms"""
+def adam_reference(w0, grads, lr, eps, max_grad_norm, dtype=torch.float64, start_step=0, m0=None, v0=None, states=None):
+    """clip_grad_norm_ + torch.optim.Adam over the gradient sequence -> list of weights after each step, norms.
+    start_step / m0 / v0: the optimiser's state before the first gradient (default: a fresh one).  states: a list that
+    receives (exp_avg, exp_avg_sq) after each step."""
     w = torch.nn.Parameter(w0.detach().to(dtype).clone())
     opt = torch.optim.Adam([w], lr=lr, eps=eps)
+    if start_step or m0 is not None or v0 is not None:
+        opt.state[w] = {"step": torch.tensor(float(start_step)),
+                        "exp_avg": torch.zeros_like(w.data) if m0 is None else m0.detach().to(dtype).clone(),
+                        "exp_avg_sq": torch.zeros_like(w.data) if v0 is None else v0.detach().to(dtype).clone()}
     out, norms = [], []
     for g in grads:
         w.grad = g.detach().to(dtype).clone()
@@ -151,4 +193,6 @@ def adam_reference(w0, grads, lr, eps, max_grad_norm, dtype=torch.float64):
             norms.append(float(w.grad.norm()))
         opt.step()
         out.append(w.detach().clone())
+        if states is not None:
+            states.append((opt.state[w]["exp_avg"].detach().clone(), opt.state[w]["exp_avg_sq"].detach().clone()))
     return out, norms
