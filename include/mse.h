@@ -396,6 +396,18 @@ int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int6
 int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
                       double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream);
 
+/* The learner's minibatch shuffle: rows_out[j] = perm(seed, epoch, total, first + j) for j < count, where perm(seed, epoch,
+ * total, .) is a bijection of [0, total) computed per element from its arguments alone (a keyed Feistel network with
+ * cycle walking, 32-bit integer arithmetic; csrc/mse_ppo_math.h specifies it completely).  No generator and no state:
+ * any window (first, count) of any epoch can be produced anywhere, and the host twin returns the very same integers,
+ * so an update is replayed without the device.  The learner passes its seed and a counter of the epochs it has run.
+ *   total        1 .. 2^31 rows; first >= 0, count >= 0, first + count <= total, else MSE_ERR_INVALID_ARGUMENT
+ *   rows_out     i64[count], 8-byte aligned; may be NULL only when count == 0 (which succeeds and does nothing)
+ * The device form is one launch on `stream` (16-byte stores where the address allows), the host form needs no device. */
+int mse_ppo_shuffle(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out_dev,
+                    void *stream);
+int mse_ppo_shuffle_host(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ EXPORTS = [
     "mse_get_policy_step", "mse_set_policy_step", "mse_model_actions", "mse_trace_begin", "mse_trace_end", "mse_press_agent_obs", "mse_rollout_policy", "mse_policy_set_precision", "mse_policy_precision",
     "mse_rollout_model",
     "mse_policy_set_weights", "mse_gae", "mse_ppo_workspace_bytes", "mse_ppo_loss_grad", "mse_ppo_adam_step",
+    "mse_ppo_shuffle", "mse_ppo_shuffle_host",
 ]
 
 _other_libs: dict = {}
@@ -133,6 +134,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_workspace_bytes.restype = i64
     L.mse_ppo_loss_grad.argtypes = [C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, vp]
     L.mse_ppo_adam_step.argtypes = [i64, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
+    L.mse_ppo_shuffle.argtypes = [i64, u64, u64, i64, i64, vp, vp]
+    L.mse_ppo_shuffle_host.argtypes = [i64, u64, u64, i64, i64, vp]
     if path is None:
         _lib = L
     else:

@@ -1,5 +1,6 @@
 // The second half of PPO on the device: returns and advantages (mse_gae), the clipped-surrogate loss of one minibatch
-// with its gradient w.r.t. all weights (mse_ppo_loss_grad) and clip_grad_norm_ + Adam (mse_ppo_adam_step).  The
+// with its gradient w.r.t. all weights (mse_ppo_loss_grad), clip_grad_norm_ + Adam (mse_ppo_adam_step) and the
+// counter-based permutation that orders an epoch's rows into minibatches (mse_ppo_shuffle, and its host twin).  The
 // per-row arithmetic lives in mse_ppo_math.h (host + device); this file holds the kernels and the C ABI.  gfx950 only.
 //
 // Gradient kernel (k_ppo_grad), DESIGN.md 4.12.  A workgroup is four waves: wave w works on the actor (w & 1 == 0) or
@@ -16,6 +17,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "mse.h"
 #include "mse_ppo_math.h"
@@ -407,6 +409,40 @@ __global__ __launch_bounds__(1024) void k_ppo_adam(AdamArgs a, float *__restrict
     }
 }
 
+// ---- the minibatch shuffle: rows_out[j] = perm(first + j), j < count ----------------------------------------------------
+// A lane takes two consecutive outputs per trip and stores them as one 16-byte word; `head` (0 or 1) outputs in front
+// bring the pairs onto a 16-byte boundary (rows_out itself is only 8-byte aligned), and an odd one may be left at the
+// end.  Lanes 0 and 1 of the grid write those two with 8-byte stores.
+constexpr int kShuffleRowsPerGroup = 512; // 256 lanes x 2 rows per trip of the grid-stride loop
+constexpr int kShuffleGroupsPerCu = 8;    // the grid cap: 32 waves per CU
+
+__global__ __launch_bounds__(256) void k_ppo_shuffle(ShuffleKey key, uint32_t total, int bits, uint32_t first, long long count,
+                                                     int head, long long *__restrict__ rows_out)
+{
+    const long long gtid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long n_pairs = (count - head) >> 1;
+    longlong2 *pairs = reinterpret_cast<longlong2 *>(rows_out + head);
+    for (long long p = gtid; p < n_pairs; p += (long long)gridDim.x * 256) {
+        const uint32_t i = first + (uint32_t)head + 2u * (uint32_t)p;
+        longlong2 v;
+        v.x = (long long)shuffle_index(key, total, bits, i);
+        v.y = (long long)shuffle_index(key, total, bits, i + 1u);
+        pairs[p] = v;
+    }
+    if (gtid == 0 && head != 0) rows_out[0] = (long long)shuffle_index(key, total, bits, first);
+    const long long last = head + 2 * n_pairs;
+    if (gtid == 1 && last < count) rows_out[last] = (long long)shuffle_index(key, total, bits, first + (uint32_t)last);
+}
+
+// the argument rules of both entry points; nullptr if they hold
+const char *shuffle_args_error(int64_t total, int64_t first, int64_t count, const int64_t *rows_out)
+{
+    if (total < 1 || total > (int64_t)1 << 31) return "total must be in 1 .. 2^31";
+    if (first < 0 || count < 0 || first > total || count > total - first) return "need 0 <= first, 0 <= count, first + count <= total";
+    if (count > 0 && rows_out == nullptr) return "null output";
+    return nullptr;
+}
+
 int cu_count()
 {
     int dev = 0, cus = 0;
@@ -517,6 +553,36 @@ int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, floa
                (float)max_grad_norm, (float)(1.0 - beta1), (float)(1.0 - beta2)};
     hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, weights, grad, m, v, grad_norm_out);
     if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_adam_step: kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_ppo_shuffle(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out_dev, void *stream)
+{
+    if (const char *why = shuffle_args_error(total, first, count, rows_out_dev))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, (std::string("mse_ppo_shuffle: ") + why).c_str());
+    if (count == 0) return MSE_OK;
+    if ((reinterpret_cast<uintptr_t>(rows_out_dev) & 7u) != 0)
+        return mse_internal_fail(MSE_ERR_ALIGNMENT, "mse_ppo_shuffle: rows_out_dev must be 8-byte aligned");
+    const int cus = cu_count();
+    if (cus <= 0) return mse_internal_fail(MSE_ERR_NO_DEVICE, "mse_ppo_shuffle: no HIP device (mse_ppo_shuffle_host runs on the CPU)");
+    const int head = (int)((reinterpret_cast<uintptr_t>(rows_out_dev) >> 3) & 1u);
+    long long groups = (count + kShuffleRowsPerGroup - 1) / kShuffleRowsPerGroup;
+    const long long cap = (long long)kShuffleGroupsPerCu * cus;
+    if (groups > cap) groups = cap;
+    hipLaunchKernelGGL(k_ppo_shuffle, dim3((unsigned)groups), dim3(256), 0, static_cast<hipStream_t>(stream), shuffle_key(seed, epoch),
+                       (uint32_t)total, shuffle_bits((uint32_t)total), (uint32_t)first, (long long)count, head,
+                       reinterpret_cast<long long *>(rows_out_dev));
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_shuffle: kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_ppo_shuffle_host(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out)
+{
+    if (const char *why = shuffle_args_error(total, first, count, rows_out))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, (std::string("mse_ppo_shuffle_host: ") + why).c_str());
+    const ShuffleKey key = shuffle_key(seed, epoch);
+    const int bits = shuffle_bits((uint32_t)total);
+    for (int64_t j = 0; j < count; ++j) rows_out[j] = (int64_t)shuffle_index(key, (uint32_t)total, bits, (uint32_t)(first + j));
     return MSE_OK;
 }
 

@@ -8,6 +8,8 @@
 //                       MaskablePPO.train and the gradient of  policy_loss + ent_coef * entropy_loss  w.r.t. the logits
 //   value_head_terms    F.mse_loss(returns, values) and its gradient
 //   hidden_forward / head_forward / backprop            the 2 x 32 tanh MLP and the deltas of its layers
+// and, restating nothing (SB3 shuffles with numpy's generator):
+//   shuffle_key / shuffle_index   the counter-based permutation of an epoch's rows, specified in full where it is defined
 // The weights are read from a PADDED image (Padded<DP, AP>: rows of the first layer padded to DP inputs, the action
 // head to AP rows, zeros in the padding, every block 16-byte aligned) so that all loops have compile-time bounds and
 // every array lives in registers on the device.  padded_index() maps the flat order of include/mse.h to it.
@@ -301,5 +303,84 @@ MSE_PPO_HD float value_head_terms(float value, float ret, const Params &P, float
 }
 
 MSE_PPO_HD float normalized_advantage(float a, float mean, float std) { return (a - mean) / (std + 1e-8f); }
+
+// ---- the minibatch shuffle: a counter-based permutation of [0, total) ------------------------------------------------------
+// perm(seed, epoch, total, i) is a function of its four arguments alone (no generator, no state shared between elements), so
+// the device fills an epoch's index array with one lane per element and the host replays any element of any epoch
+// (mse_ppo_shuffle / mse_ppo_shuffle_host, tests/ppo_shuffle_reference.py restates what follows in numpy).  It is a keyed
+// Feistel network on b bits with cycle walking.  All arithmetic is on uint32 and wraps; ^ is xor, >> a logical shift.
+//
+//   mix32(h):   h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16      (murmur3's finaliser)
+//
+//   key (shuffle_key; the only place the 64-bit seed and epoch are read):
+//     h = 0x9E3779B9
+//     for w in  seed & 0xFFFFFFFF,  seed >> 32,  epoch & 0xFFFFFFFF,  epoch >> 32   (in this order):
+//         h = mix32((h ^ w) + 0x9E3779B9)
+//     k[r] = mix32(h ^ ((r + 1) * 0x85EBCA77))                 for the six rounds r = 0 .. 5
+//   Every absorbing step is a bijection of h for a fixed w and of w for a fixed h, so two seeds that differ in either half
+//   (or two epochs) never share h, whatever the other words are.
+//
+//   split:  b = max(2, ceil(log2 total)) = max(2, number of significant bits of total - 1),  2 <= b <= 31;
+//           the LOW half has lo_bits = b / 2 (rounded down) bits, the HIGH half hi_bits = b - lo_bits (the larger when b is odd)
+//
+//   cipher E on a b-bit value x:   hi = x >> lo_bits;  lo = x & (2^lo_bits - 1)
+//     for r = 0 .. 5:   r even:  hi ^= mix32(lo ^ k[r]) & (2^hi_bits - 1)
+//                       r odd:   lo ^= mix32(hi ^ k[r]) & (2^lo_bits - 1)
+//     E(x) = (hi << lo_bits) | lo
+//   Each round xors one half with a function of the other, so E is a bijection of [0, 2^b) for every key.
+//
+//   shuffle_index(key, total, i):   x = E(i);  while x >= total: x = E(x);  return x
+//   Cycle walking: following i's cycle of E until it re-enters [0, total) is a bijection of [0, total).  2^b < 2 total for
+//   total >= 2 (2^b = 4 for total = 1), so fewer than two applications of E are expected per element.
+constexpr int kShuffleRounds = 6;
+
+struct ShuffleKey {
+    uint32_t k[kShuffleRounds];
+};
+
+MSE_PPO_HD uint32_t mix32(uint32_t h)
+{
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+MSE_PPO_HD ShuffleKey shuffle_key(uint64_t seed, uint64_t epoch)
+{
+    const uint32_t words[4] = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)epoch, (uint32_t)(epoch >> 32)};
+    uint32_t h = 0x9E3779B9u;
+    for (int i = 0; i < 4; ++i) h = mix32((h ^ words[i]) + 0x9E3779B9u);
+    ShuffleKey key;
+    for (int r = 0; r < kShuffleRounds; ++r) key.k[r] = mix32(h ^ ((uint32_t)(r + 1) * 0x85EBCA77u));
+    return key;
+}
+
+// b for `total` in 1 .. 2^31 (given as uint32)
+MSE_PPO_HD int shuffle_bits(uint32_t total)
+{
+    int b = 0;
+    for (uint32_t v = total - 1u; v != 0u; v >>= 1) ++b; // significant bits of total - 1 (a loop: no builtin on the host)
+    return b < 2 ? 2 : b;
+}
+
+MSE_PPO_HD uint32_t shuffle_index(const ShuffleKey &key, uint32_t total, int bits, uint32_t i) // bits = shuffle_bits(total)
+{
+    const int lo_bits = bits >> 1, hi_bits = bits - lo_bits;
+    const uint32_t lo_mask = (1u << lo_bits) - 1u, hi_mask = (1u << hi_bits) - 1u;
+    uint32_t x = i;
+    do {
+        uint32_t hi = x >> lo_bits, lo = x & lo_mask;
+#pragma unroll
+        for (int r = 0; r < kShuffleRounds; r += 2) {
+            hi ^= mix32(lo ^ key.k[r]) & hi_mask;
+            lo ^= mix32(hi ^ key.k[r + 1]) & lo_mask;
+        }
+        x = (hi << lo_bits) | lo;
+    } while (x >= total);
+    return x;
+}
 
 } // namespace mseppo

@@ -5,7 +5,8 @@
 the gradient w.r.t. all weights, three launches) and one `mse_ppo_adam_step` (clip_grad_norm_ + Adam), all enqueued
 without a host synchronisation; the new weights go back into the policy the rollout kernels read once per update
 (`MlpPolicy.load_weights`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
-computes anything on this path, and there is no CPU fallback.
+computes anything on this path, and there is no CPU fallback.  With `shuffle="device"` the permutation is a kernel too
+(`mse_ppo_shuffle`, a counter-based function of seed and epoch that `PPOLearner.permutation` replays on the host).
 """
 from __future__ import annotations
 
@@ -57,12 +58,20 @@ def compute_gae(data: dict, gamma: float = 0.99, gae_lambda: float = 0.95) -> di
 class PPOLearner:
     """SB3's PPO defaults (the reference overrides ent_coef=0.05, src/training.py:115-131).  `batch_size=None`: 64 rows
     per env-step-column is far too small for a 10^6-row rollout, so the default is K * N / 4 rounded up - pass SB3's 64
-    explicitly to reproduce its schedule."""
+    explicitly to reproduce its schedule.
+
+    `shuffle="cpu"` (the default) permutes the rows of each epoch with `torch.randperm` on a seeded CPU generator and
+    copies the indices up; `last_permutations` keeps them.  `shuffle="device"` fills one i64[K * N] device buffer per
+    epoch with `mse_ppo_shuffle(total, seed, epochs_done, ...)` on the current stream: no host work, no copy.
+    `epochs_done` counts the epochs of the learner's lifetime, so no two share a permutation; `last_epochs` lists the
+    counters the last `update()` used and `permutation(total, epoch)` returns the same rows on the CPU."""
 
     def __init__(self, policy: MlpPolicy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
                  gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: float = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
-                 seed: int = 0):
+                 seed: int = 0, shuffle: str = "cpu"):
+        if shuffle not in ("cpu", "device"):
+            raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
         self.policy, self.L = policy, policy.L
         self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
@@ -70,6 +79,7 @@ class PPOLearner:
         self.beta1, self.beta2 = 0.9, 0.999
         self.params = MsePpoParams(C.sizeof(MsePpoParams), float(clip_range), float(ent_coef), float(vf_coef),
                                    1 if normalize_advantage else 0)
+        self.shuffle, self.seed = shuffle, int(seed) & (2 ** 64 - 1)
         self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
         dev = policy.device
         self.device = dev
@@ -82,7 +92,10 @@ class PPOLearner:
         ws = int(self.L.mse_ppo_workspace_bytes(policy.obs_dim, policy.n_actions))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.step = 0  # Adam steps taken
-        self.last_permutations: list = []  # the CPU permutations of the last update(), one per epoch
+        self.last_permutations: list = []  # the CPU permutations of the last update(), one per epoch (shuffle="cpu")
+        self.epochs_done = 0  # shuffle="device": epochs shuffled so far, the counter the next permutation is keyed by
+        self.last_epochs: list = []  # shuffle="device": the counters of the last update(), one per epoch
+        self._perm = None  # shuffle="device": i64[K * N], kept until the rollout size changes
 
     def loss_grad(self, data: dict, rows: Optional[torch.Tensor], batch: int, stats_out: torch.Tensor,
                   weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -111,9 +124,26 @@ class PPOLearner:
                                            self.step, self.learning_rate, self.beta1, self.beta2, self.adam_eps,
                                            self.max_grad_norm, _ptr(self.grad_norm), _stream(self.device)))
 
+    def permutation(self, total: int, epoch: int) -> torch.Tensor:
+        """The rows of epoch counter `epoch` over a rollout of `total` rows as shuffle="device" orders them: an i64 CPU
+        tensor from `mse_ppo_shuffle_host` (the kernel's arithmetic on the host; no device is touched)."""
+        rows = torch.empty(int(total), dtype=torch.int64)
+        check(self.L.mse_ppo_shuffle_host(int(total), self.seed, int(epoch), 0, int(total), _ptr(rows)))
+        return rows
+
+    def _device_permutation(self, total: int) -> torch.Tensor:
+        if self._perm is None or self._perm.numel() != total:
+            self._perm = torch.empty(total, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_shuffle(total, self.seed, self.epochs_done, 0, total, _ptr(self._perm), _stream(self.device)))
+        self.last_epochs.append(self.epochs_done)
+        self.epochs_done += 1
+        return self._perm
+
     def update(self, data: dict) -> dict:
-        """GAE, then n_epochs passes over a seeded CPU permutation of the K * N rows (copied to the device once per epoch;
-        the last minibatch of an epoch may be short), one loss_grad + adam_step per minibatch without a host
+        """GAE, then n_epochs passes over a permutation of the K * N rows (shuffle="cpu": seeded on the CPU and copied to
+        the device once per epoch; shuffle="device": one `mse_ppo_shuffle` launch per epoch; the last minibatch of an
+        epoch may be short), one loss_grad + adam_step per minibatch without a host
         synchronisation, then one `policy.load_weights`.  Returns {"stats": f32[n_minibatches, 8] (device; columns
         STAT_NAMES), "mean": {name: float}}."""
         compute_gae(data, self.gamma, self.gae_lambda)
@@ -123,12 +153,15 @@ class PPOLearner:
         bs = max(1, min(int(bs), total))
         per_epoch = (total + bs - 1) // bs
         stats = torch.zeros((self.n_epochs * per_epoch, 8), dtype=torch.float32, device=self.device)
-        self.last_permutations = []
+        self.last_permutations, self.last_epochs = [], []
         i = 0
         for _ in range(self.n_epochs):
-            perm_cpu = torch.randperm(total, generator=self.generator)
-            self.last_permutations.append(perm_cpu)
-            perm = perm_cpu.to(self.device)
+            if self.shuffle == "device":
+                perm = self._device_permutation(total)
+            else:
+                perm_cpu = torch.randperm(total, generator=self.generator)
+                self.last_permutations.append(perm_cpu)
+                perm = perm_cpu.to(self.device)
             for start in range(0, total, bs):
                 rows = perm[start:start + bs]
                 self.loss_grad(data, rows, rows.numel(), stats[i])

@@ -1,7 +1,9 @@
 """Train one of the three envs with the on-device PPO learner, from MlpPolicy.random_init.
 
     python tools/train_ppo.py --kind mono --envs 4096 --steps 16 --iterations 20
-    python tools/train_ppo.py --kind mono --time          # rows/s of mse_ppo_loss_grad beside torch f32 autograd
+    python tools/train_ppo.py --kind mono --shuffle device   # the epoch permutations from mse_ppo_shuffle, not the CPU
+    python tools/train_ppo.py --kind mono --time          # rows/s of mse_ppo_loss_grad beside torch f32 autograd, and one
+                                                          # update() with shuffle="cpu" and shuffle="device"
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -86,18 +88,26 @@ def time_loss_grad(args):
         torch.cuda.synchronize()
         t_gae = (time.perf_counter() - t0) / 20
         print(f"{args.kind} rows={rows}: mse_gae {t_gae * 1e6:.1f} us = {17 * rows / t_gae / 1e9:.0f} GB/s of its 17 B/row")
-        # one update() beside the collect() that feeds it
+        # one update() beside the collect() that feeds it, in both shuffle modes: one warm-up each, then three timed
+        # updates each, alternating
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         col.collect()
         torch.cuda.synchronize()
         t_col = time.perf_counter() - t0
-        t0 = time.perf_counter()
-        learner.update(data)
-        torch.cuda.synchronize()
-        t_upd = time.perf_counter() - t0
+        learners = {mode: M.PPOLearner(pol, ent_coef=0.05, shuffle=mode) for mode in ("cpu", "device")}
+        t_upd = {mode: [] for mode in learners}
+        for rep in range(4):
+            for mode, lrn in learners.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                lrn.update(data)
+                torch.cuda.synchronize()
+                if rep > 0:
+                    t_upd[mode].append(time.perf_counter() - t0)
         print(f"{args.kind} rows={rows}: " + ", ".join(f"{k} {v * 1e6:.1f} us ({rows / v / 1e6:.1f} M rows/s)" for k, v in res.items())
-              + f"; collect {t_col * 1e6:.0f} us, update (10 epochs x 4 minibatches) {t_upd * 1e3:.2f} ms")
+              + f"; collect {t_col * 1e6:.0f} us, update (10 epochs x 4 minibatches) "
+              + ", ".join(f"shuffle={mode} " + " / ".join(f"{t * 1e3:.2f}" for t in ts) + " ms" for mode, ts in t_upd.items()))
 
 
 def main():
@@ -112,6 +122,8 @@ def main():
     ap.add_argument("--ent-coef", type=float, default=0.05)
     ap.add_argument("--max-steps", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--shuffle", choices=("cpu", "device"), default="cpu",
+                    help="where an epoch's row permutation comes from: the seeded CPU generator or mse_ppo_shuffle")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
@@ -123,8 +135,8 @@ def main():
                               auto_reset=True)
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
     learner = M.PPOLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
-                           seed=args.seed)
-    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration")
+                           seed=args.seed, shuffle=args.shuffle)
+    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}")
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
