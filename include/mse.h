@@ -408,6 +408,59 @@ int mse_ppo_shuffle(int64_t total, uint64_t seed, uint64_t epoch, int64_t first,
                     void *stream);
 int mse_ppo_shuffle_host(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out);
 
+/* ---- Episode accounting: cumulative reward per episode, the unit the reference measures a policy in ---------------------
+ * (SB3's Monitor: rollout/ep_rew_mean, ep_len_mean; evaluate_policy(model, env, n_eval_episodes) and EvalCallback,
+ * src/training.py:69,149-157,196-209; np.mean / np.std of cumulative rewards, utils/benchmark_models.py:39;
+ * cumulative_reward, src/testing.py:54.)  All buffers are caller-owned device memory (host memory for the *_host forms),
+ * all work goes to `stream`, nothing allocates or synchronises, and the arguments are checked before any device call.
+ * csrc/mse_episode_math.h specifies the arithmetic completely; the kernels and the host forms run that one header.
+ *
+ * mse_episode_scan walks step-major rollout buffers, one env per lane, steps k = 0 .. K - 1 in order:
+ *   rewards        f32[K,N]
+ *   the end of an episode, given in exactly ONE of the project's two forms (else MSE_ERR_INVALID_ARGUMENT):
+ *     dones          u8[K,N]   done_out of mse_rollout / mse_rollout_model: step k ended an episode iff dones[k] != 0
+ *     episode_starts u8[K,N] + last_dones u8[N]   the buffers of mse_rollout_policy: step k ended an episode iff
+ *                    episode_starts[k + 1] != 0, last_dones at k = K - 1; episode_starts[0] is not read
+ *   run_return f64[N], run_length i32[N]   the carry, read and written: zero it once, then a return spans any number of calls
+ *   ep_count   i32[N]   read and written: the episodes of env i counted so far
+ *   targets    i32[N] or NULL: an ended episode is counted iff targets == NULL or ep_count[i] < targets[i] - the per-env
+ *              rule of evaluate_policy, whose targets are (n_eval_episodes + i) / N rounded down
+ *   slots, ledger_return f64[slots,N], ledger_length i32[slots,N], or 0 / NULL / NULL: a counted episode is stored at slot
+ *              ep_count[i] while that is < slots (slot-major, so the stores coalesce); cells of episodes that did not
+ *              happen are not written
+ *   totals     f64[5] or NULL: counted episodes, sum of returns, sum of lengths, min return, max return.  ADDED TO what
+ *              is passed in (min / max combined; those of a totals[] whose count is 0 are ignored), so a window over
+ *              several rollouts is one zero-fill and then calls
+ *   workspace  mse_episode_workspace_bytes() bytes, 8-byte aligned, needed with totals; contents need not survive
+ * Per step: run_return += (double)reward, run_length += 1; at an episode's end it is counted (ledger, totals,
+ * ep_count += 1) or not, and the carry is cleared either way.  A return is thus the float64 sum, in step order, of the
+ * FLOAT32 rewards the buffer holds; Monitor sums the env's float64 rewards and rounds to 6 digits, so the two differ by
+ * at most  episode length x 2^-24 x max |reward|  (plus Monitor's own rounding).  Per-env outputs do not depend on the
+ * launch shape.  The totals are reduced per wave, then over the workgroup's waves in LDS, one slab per workgroup goes to
+ * the workspace and a one-workgroup launch folds the slabs in a fixed order: no atomics, equal inputs give bit-equal
+ * outputs.  The lane -> env mapping and the grid cap are fixed functions of N and the device.  Two launches (one
+ * without totals).
+ *
+ * mse_episode_summary: np.mean / np.std (ddof 0) over the ledger entries of the counted episodes, two passes with the
+ * rounded mean subtracted in the second, in a fixed order.  summary f64[6]: episodes, mean return, std return, mean
+ * length, min return, max return (NaN beside a count of 0).  It covers what the ledger holds: slots 0 ..
+ * min(ep_count[i], slots) - 1 of env i.  Without a ledger it refuses (MSE_ERR_INVALID_ARGUMENT, nothing launched).
+ * One launch of one workgroup.
+ *
+ * The *_host forms run the same walk and the same formulas on host arrays (envs in ascending order) and need no
+ * device: per-env outputs, counts, lengths, min and max equal the device's bit for bit, the sums to rounding. */
+int64_t mse_episode_workspace_bytes(void);
+int mse_episode_scan(int32_t k_steps, int64_t n, const float *rewards, const uint8_t *dones, const uint8_t *episode_starts,
+                     const uint8_t *last_dones, double *run_return, int32_t *run_length, int32_t *ep_count, const int32_t *targets,
+                     int32_t slots, double *ledger_return, int32_t *ledger_length, double *totals, void *workspace, void *stream);
+int mse_episode_scan_host(int32_t k_steps, int64_t n, const float *rewards, const uint8_t *dones, const uint8_t *episode_starts,
+                          const uint8_t *last_dones, double *run_return, int32_t *run_length, int32_t *ep_count,
+                          const int32_t *targets, int32_t slots, double *ledger_return, int32_t *ledger_length, double *totals);
+int mse_episode_summary(int64_t n, int32_t slots, const int32_t *ep_count, const double *ledger_return, const int32_t *ledger_length,
+                        double *summary, void *stream);
+int mse_episode_summary_host(int64_t n, int32_t slots, const int32_t *ep_count, const double *ledger_return,
+                             const int32_t *ledger_length, double *summary);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ EXPORTS = [
     "mse_rollout_model",
     "mse_policy_set_weights", "mse_gae", "mse_ppo_workspace_bytes", "mse_ppo_loss_grad", "mse_ppo_adam_step",
     "mse_ppo_shuffle", "mse_ppo_shuffle_host",
+    "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
 ]
 
 _other_libs: dict = {}
@@ -136,6 +137,12 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_adam_step.argtypes = [i64, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     L.mse_ppo_shuffle.argtypes = [i64, u64, u64, i64, i64, vp, vp]
     L.mse_ppo_shuffle_host.argtypes = [i64, u64, u64, i64, i64, vp]
+    L.mse_episode_workspace_bytes.argtypes = []
+    L.mse_episode_workspace_bytes.restype = i64
+    L.mse_episode_scan.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.mse_episode_scan_host.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.mse_episode_summary.argtypes = [i64, i32, vp, vp, vp, vp, vp]
+    L.mse_episode_summary_host.argtypes = [i64, i32, vp, vp, vp, vp]
     if path is None:
         _lib = L
     else:

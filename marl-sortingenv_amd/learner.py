@@ -7,6 +7,8 @@ without a host synchronisation; the new weights go back into the policy the roll
 (`MlpPolicy.load_weights`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
 computes anything on this path, and there is no CPU fallback.  With `shuffle="device"` the permutation is a kernel too
 (`mse_ppo_shuffle`, a counter-based function of seed and epoch that `PPOLearner.permutation` replays on the host).
+`learn` can report the reference's unit, cumulative reward per episode (episodes.py): SB3's `rollout/ep_rew_mean` from an
+`EpisodeStats` over the training rollouts, and `EvalCallback`'s periodic `evaluate_policy` with the best weights kept.
 """
 from __future__ import annotations
 
@@ -96,6 +98,9 @@ class PPOLearner:
         self.epochs_done = 0  # shuffle="device": epochs shuffled so far, the counter the next permutation is keyed by
         self.last_epochs: list = []  # shuffle="device": the counters of the last update(), one per epoch
         self._perm = None  # shuffle="device": i64[K * N], kept until the rollout size changes
+        self.episode_stats = None  # learn(episode_stats=True): the EpisodeStats whose carry spans the iterations
+        self.best_mean_reward = float("-inf")  # learn(eval_collector=...): EvalCallback's best model so far
+        self.best_weights = None  # f32[W] on the device, a copy of `weights` at the best evaluation
 
     def loss_grad(self, data: dict, rows: Optional[torch.Tensor], batch: int, stats_out: torch.Tensor,
                   weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -171,15 +176,53 @@ class PPOLearner:
         mean = stats.mean(dim=0).cpu().tolist()
         return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
 
-    def learn(self, collector, iterations: int, callback=None) -> list:
+    def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
+              eval_freq: int = 0, n_eval_episodes: int = 10) -> list:
         """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
-        mean reward per env-step under "reward"."""
+        mean reward per env-step under "reward".
+        episode_stats=True: each record gains `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in
+        that iteration's rollout (NaN when none did); the running returns persist in `self.episode_stats` across
+        iterations and across calls.
+        eval_collector (a FusedPolicyRollout over this learner's policy and an env of its own) with eval_freq > 0: every
+        eval_freq-th iteration gains `eval_mean_reward`, `eval_std_reward` from `evaluate_policy(eval_collector,
+        n_eval_episodes)`; the best mean so far is kept in `best_mean_reward` with a device copy of the weights in
+        `best_weights` (`restore_best()` loads them back).  With the defaults the records and the device work are
+        what they were without these arguments."""
+        from .episodes import EpisodeStats, evaluate_policy
+
+        evaluating = eval_collector is not None and int(eval_freq) > 0
+        if evaluating and eval_collector.policy is not self.policy:
+            raise ValueError("eval_collector must run this learner's policy")
         history = []
         for it in range(int(iterations)):
             data = collector.collect()
+            if episode_stats:
+                n = data["rewards"].shape[1]
+                if self.episode_stats is None or self.episode_stats.num_envs != n:
+                    self.episode_stats = EpisodeStats(n, self.device)
+                self.episode_stats.reset_totals()
+                self.episode_stats.update(data)
             out = self.update(data)
             rec = dict(out["mean"], reward=float(data["rewards"].mean()))
+            if episode_stats:
+                t = self.episode_stats.totals()
+                rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
+            if evaluating and (it + 1) % int(eval_freq) == 0:
+                mean, std = evaluate_policy(eval_collector, n_eval_episodes=n_eval_episodes)
+                rec.update(eval_mean_reward=mean, eval_std_reward=std)
+                if mean > self.best_mean_reward:
+                    self.best_mean_reward = mean
+                    if self.best_weights is None:
+                        self.best_weights = torch.empty_like(self.weights)
+                    self.best_weights.copy_(self.weights)  # device to device
             history.append(rec)
             if callback is not None:
                 callback(it, rec)
         return history
+
+    def restore_best(self) -> None:
+        """Loads `best_weights` back into the learner's master copy and the policy (EvalCallback's best_model)."""
+        if self.best_weights is None:
+            raise RuntimeError("no evaluation has run: there are no best weights")
+        self.weights.copy_(self.best_weights)
+        self.policy.load_weights(self.weights)

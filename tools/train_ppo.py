@@ -2,6 +2,8 @@
 
     python tools/train_ppo.py --kind mono --envs 4096 --steps 16 --iterations 20
     python tools/train_ppo.py --kind mono --shuffle device   # the epoch permutations from mse_ppo_shuffle, not the CPU
+    python tools/train_ppo.py --kind mono --episode-stats --eval-every 5   # ep_rew_mean / ep_len_mean of the training rollouts and
+                                                          # evaluate_policy on 10 envs of their own every 5th iteration
     python tools/train_ppo.py --kind mono --time          # rows/s of mse_ppo_loss_grad beside torch f32 autograd, and one
                                                           # update() with shuffle="cpu" and shuffle="device"
 
@@ -124,6 +126,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--shuffle", choices=("cpu", "device"), default="cpu",
                     help="where an epoch's row permutation comes from: the seeded CPU generator or mse_ppo_shuffle")
+    ap.add_argument("--episode-stats", action="store_true",
+                    help="print the episodes that ended in each rollout with their mean return and length (SB3's ep_rew_mean)")
+    ap.add_argument("--eval-every", type=int, default=0,
+                    help="every this many iterations evaluate_policy (10 deterministic episodes) and keep the best weights")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
@@ -142,7 +148,20 @@ def main():
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
               f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
 
-    learner.learn(col, args.iterations, callback=show)
+        if "episodes" in rec:
+            print(f"       episodes {rec['episodes']:6d} ep_rew_mean {rec['ep_rew_mean']:+.3f} ep_len_mean {rec['ep_len_mean']:.1f}")
+        if "eval_mean_reward" in rec:
+            print(f"       eval {rec['eval_mean_reward']:+.3f} +- {rec['eval_std_reward']:.3f} (best {learner.best_mean_reward:+.3f})")
+
+    eval_col = None
+    if args.eval_every > 0:
+        eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
+                                       auto_reset=True)
+        eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
+    learner.learn(col, args.iterations, callback=show, episode_stats=args.episode_stats, eval_collector=eval_col,
+                  eval_freq=args.eval_every)
+    if eval_col is not None:
+        learner.restore_best()
     if args.save:
         torch.save(pol.state_dict(), args.save)
 
