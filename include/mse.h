@@ -349,6 +349,33 @@ int mse_rollout_policy(mse_env *env, mse_policy *policy, mse_policy *sort_policy
  * any stream when it is called; launches enqueued afterwards see the new weights. */
 int mse_policy_set_weights(mse_policy *policy, const float *weights_host);
 
+/* The same replacement without the host: the repack runs on the device (csrc/mse_policy_pack.h specifies the image
+ * completely and is the one arithmetic both packers run, float64 operations in the same order, so the device image
+ * equals mse_policy_set_weights' byte for byte).  The handle also keeps a device copy of the flat weights its image was
+ * packed from; mse_policy_create and mse_policy_set_weights keep it current too.
+ *
+ * mse_policy_set_weights_device: weights_dev f32[W] in device memory, flat order.  ONE launch of one workgroup on
+ * `stream`; never synchronises, never allocates.  Ordering rule: launches enqueued on that stream afterwards see the new
+ * weights; for every other stream the rule of mse_policy_set_weights stands.  The f16 range check happens inside the
+ * launch: an "auto" or f32 policy always gets the new head and f32 operands, and the f16 operands when every folded
+ * weight fits (their content is unspecified otherwise); a policy pinned to f16x3 whose new weights do not fit is left
+ * untouched - image and flat copy - and a status word on the device says "refused".
+ * mse_policy_sync: one small blocking read of that status word (behind the repack on its stream; nothing is read when
+ * no device repack is outstanding).  It brings the host's view up to date, so an "auto" policy changes form exactly as
+ * after mse_policy_set_weights, and returns MSE_ERR_UNSUPPORTED_CONFIG for a refused pinned policy.  UNTIL IT IS CALLED,
+ * launches use the form last known: call it before the next launch whenever the new weights may cross f16's range.
+ * mse_policy_pack_host / mse_policy_image_floats: the host twin, which needs no device: image_out
+ * f32[mse_policy_image_floats()], *f16_ok_out = every folded weight is below 65 504 (the image's f16 section is specified
+ * only then).  Dimensions outside 1..32: MSE_ERR_UNSUPPORTED_CONFIG.
+ * mse_policy_read_image: a blocking copy of the device image into image_out_host (same size), for tests and debugging.
+ * mse_policy_get_weights: a blocking copy of the handle's flat weights into out_host f32[W]. */
+int mse_policy_set_weights_device(mse_policy *policy, const float *weights_dev, void *stream);
+int mse_policy_sync(mse_policy *policy);
+int64_t mse_policy_image_floats(void);
+int mse_policy_pack_host(int obs_dim, int n_actions, const float *weights_host, float *image_out, int32_t *f16_ok_out);
+int mse_policy_read_image(mse_policy *policy, float *image_out_host);
+int mse_policy_get_weights(mse_policy *policy, float *out_host);
+
 /* ---- The learner's half of PPO (SB3's model.learn -> MaskablePPO.train, src/training.py:191) ---------------------------
  * All buffers are caller-owned device memory, all work goes to `stream`, nothing allocates or synchronises, and the
  * arguments are checked before any device call.
@@ -395,6 +422,27 @@ int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int6
  * One workgroup (a policy has at most 4 791 weights). */
 int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
                       double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream);
+
+/* SB3's target_kl (PPO.train: after a minibatch's loss, `if approx_kl_div > 1.5 * target_kl` the minibatch takes no
+ * optimiser step and no further minibatch of any epoch runs; its statistics are still logged) with the decision on the
+ * device, so the host enqueues every minibatch of an update and never reads a value in between.
+ *   control_dev  i32[2] = {stopped, minibatches_run}, caller-owned device memory, zeroed by the caller before an update
+ * mse_ppo_loss_grad_gated: with stopped != 0 on entry all three launches exit at once: grad_out and stats_out are not
+ * written (the workspace, whose contents never survive a call, gets one marker cell).  Otherwise it is
+ * mse_ppo_loss_grad, same bits; the lane that writes stats_out then increments minibatches_run and sets stopped = 1 when
+ * (double)stats_out[4] > 1.5 * target_kl - the comparison SB3 makes between a float32 mean and a Python float.
+ * target_kl <= 0: the flag is honoured and the count kept, but never set.
+ * mse_ppo_adam_step_gated: does nothing when stopped != 0, else mse_ppo_adam_step.  `step` is the caller's count as if
+ * every step were taken: no step follows a skipped one, so the steps that run have the right number.
+ * The flag is only ever written by that one lane and read at the entry of LATER launches of the same stream, so every
+ * wave of a launch sees the same value.  The ungated entry points are these with no control block. */
+int mse_ppo_loss_grad_gated(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                            float *stats_out, void *workspace, void *stream, double target_kl, int32_t *control_dev);
+int mse_ppo_adam_step_gated(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
+                            double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream,
+                            const int32_t *control_dev);
 
 /* The learner's minibatch shuffle: rows_out[j] = perm(seed, epoch, total, first + j) for j < count, where perm(seed, epoch,
  * total, .) is a bijection of [0, total) computed per element from its arguments alone (a keyed Feistel network with

@@ -24,6 +24,8 @@ EXPORTS = [
     "mse_rollout_model",
     "mse_policy_set_weights", "mse_gae", "mse_ppo_workspace_bytes", "mse_ppo_loss_grad", "mse_ppo_adam_step",
     "mse_ppo_shuffle", "mse_ppo_shuffle_host",
+    "mse_policy_set_weights_device", "mse_policy_sync", "mse_policy_image_floats", "mse_policy_pack_host",
+    "mse_policy_read_image", "mse_policy_get_weights", "mse_ppo_loss_grad_gated", "mse_ppo_adam_step_gated",
     "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
 ]
 
@@ -130,11 +132,20 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_rollout_policy.argtypes = [vp, vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
+    L.mse_policy_set_weights_device.argtypes = [vp, vp, vp]
+    L.mse_policy_sync.argtypes = [vp]
+    L.mse_policy_image_floats.argtypes = []
+    L.mse_policy_image_floats.restype = i64
+    L.mse_policy_pack_host.argtypes = [C.c_int, C.c_int, vp, vp, vp]
+    L.mse_policy_read_image.argtypes = [vp, vp]
+    L.mse_policy_get_weights.argtypes = [vp, vp]
     L.mse_gae.argtypes = [i32, i64, vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     L.mse_ppo_workspace_bytes.argtypes = [C.c_int, C.c_int]
     L.mse_ppo_workspace_bytes.restype = i64
     L.mse_ppo_loss_grad.argtypes = [C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, vp]
     L.mse_ppo_adam_step.argtypes = [i64, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
+    L.mse_ppo_loss_grad_gated.argtypes = L.mse_ppo_loss_grad.argtypes + [C.c_double, vp]
+    L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
     L.mse_ppo_shuffle.argtypes = [i64, u64, u64, i64, i64, vp, vp]
     L.mse_ppo_shuffle_host.argtypes = [i64, u64, u64, i64, i64, vp]
     L.mse_episode_workspace_bytes.argtypes = []

@@ -1,8 +1,9 @@
 // Batched forward of the reference's actor-critic policy with masked categorical sampling, on the matrix cores:
 // the standalone launch (mse_policy_forward).  The network, its MFMA layout and the sampling rule live in
 // mse_policy_device.h (one device function per 32-env tile, shared with the fused learned-policy rollout kernel of
-// mse_lib.hip); this file holds the kernel that feeds it from observation / mask tensors, the host-side packing of
-// torch.nn.Linear weights into MFMA operand order, and the C ABI.  gfx950 only.
+// mse_lib.hip); this file holds the kernel that feeds it from observation / mask tensors, the packing of
+// torch.nn.Linear weights into MFMA operand order on the host and on the device (one arithmetic: mse_policy_pack.h),
+// and the C ABI.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,6 +14,7 @@
 
 #include "mse.h"
 #include "mse_policy_device.h"
+#include "mse_policy_pack.h"
 #include "mse_policy_stream.h"
 
 int mse_internal_fail(int status, const char *msg); // mse_lib.hip: sets mse_last_error()
@@ -82,100 +84,114 @@ __global__ __launch_bounds__(512) void k_policy_mlp(PolicyArgs P, const float *_
 }
 
 // torch.nn.Linear tensors (include/mse.h order) -> the image of mse_policy_device.h: A operands in the k order the
-// accumulator registers impose, biases in register order, tanh folded into the weights.  Folding in double:
-//   hidden unit:  r = 1 / (2^z + 1)  with  z = c (W in + b),  c = 2 log2 e,  tanh = 1 - 2 r
-//   a layer fed by r instead of tanh:  W tanh + b = (b + W 1) + (-2 W) r
+// accumulator registers impose, biases in register order, tanh folded into the weights.  mse_policy_pack.h specifies the
+// image and holds its arithmetic; this is the host's walk over the cells.  From the first weight that leaves f16's range
+// on, the f16 cells are left zero (their content is unspecified then).
+void pack_weights(const float *w, int D, int A, float *out, bool &f16_ok)
+{
+    using namespace msepack;
+    const Flat F = flat_offsets(D, A);
+    for (int i = 0; i < kBlobFloats; ++i) out[i] = 0.0f;
+    for (int i = 0; i < kOffW; ++i) out[i] = head_cell(w, F, A, i);
+    f16_ok = true;
+    uint16_t *h16 = reinterpret_cast<uint16_t *>(out + kOffW16); // [hi | lo][layer][chunk][lane][8]
+    for (int L = 0; L < 5; ++L)
+        for (int s = 0; s < 16; ++s)
+            for (int lane = 0; lane < 64; ++lane) {
+                const float wf = operand(w, F, D, A, L, s, lane);
+                out[f32_cell(L, s, lane)] = wf;
+                if (!fits_half(wf)) f16_ok = false;
+                if (!f16_ok) continue;
+                const HalfPair hp = split_half(wf);
+                h16[f16_cell(L, s, lane)] = hp.hi;
+                h16[kOperandCells + f16_cell(L, s, lane)] = hp.lo;
+            }
+}
+
 std::vector<float> pack_weights(const float *w, int D, int A, bool &f16_ok)
 {
-    const int H = kHidden;
-    const float *pi_w1 = w, *pi_b1 = pi_w1 + H * D, *pi_w2 = pi_b1 + H, *pi_b2 = pi_w2 + H * H;
-    const float *act_w = pi_b2 + H, *act_b = act_w + A * H;
-    const float *vf_w1 = act_b + A, *vf_b1 = vf_w1 + H * D, *vf_w2 = vf_b1 + H, *vf_b2 = vf_w2 + H * H;
-    const float *val_w = vf_b2 + H, *val_b = val_w + H;
-    const double c = 2.0 * 1.4426950408889634073599246810019;
-    // folded dense forms: Wd[L][out][in] (32 x 32, zero padded), bd[L][out]
-    std::vector<double> Wd(5 * 32 * 32, 0.0), bd(5 * 32, 0.0);
-    auto W = [&](int L, int o, int i) -> double & { return Wd[(size_t)(L * 32 + o) * 32 + i]; };
-    auto B = [&](int L, int o) -> double & { return bd[(size_t)L * 32 + o]; };
-    for (int o = 0; o < H; ++o) {
-        for (int i = 0; i < D; ++i) {
-            W(0, o, i) = c * (double)pi_w1[o * D + i];
-            W(3, o, i) = c * (double)vf_w1[o * D + i];
-        }
-        B(0, o) = c * (double)pi_b1[o];
-        B(3, o) = c * (double)vf_b1[o];
-        double s1 = 0.0, s4 = 0.0;
-        for (int i = 0; i < H; ++i) {
-            W(1, o, i) = -2.0 * c * (double)pi_w2[o * H + i];
-            W(4, o, i) = -2.0 * c * (double)vf_w2[o * H + i];
-            s1 += (double)pi_w2[o * H + i];
-            s4 += (double)vf_w2[o * H + i];
-        }
-        B(1, o) = c * ((double)pi_b2[o] + s1);
-        B(4, o) = c * ((double)vf_b2[o] + s4);
-    }
-    for (int o = 0; o < A; ++o) {
-        double s2 = 0.0;
-        for (int i = 0; i < H; ++i) {
-            W(2, o, i) = -2.0 * (double)act_w[o * H + i];
-            s2 += (double)act_w[o * H + i];
-        }
-        B(2, o) = (double)act_b[o] + s2;
-    }
-    std::vector<float> out(kBlobFloats, 0.0f);
-    f16_ok = true;
-    uint16_t *h16 = reinterpret_cast<uint16_t *>(out.data() + kOffW16); // [hi | lo][layer][chunk][lane][8]
-    auto f32_of_half = [](uint16_t hb) -> float {
-        const uint32_t sgn = (uint32_t)(hb & 0x8000u) << 16, ex = (hb >> 10) & 0x1Fu, man = hb & 0x3FFu;
-        if (ex == 0) return (sgn ? -1.0f : 1.0f) * std::ldexp((float)man, -24);
-        uint32_t u = sgn | ((ex + 112u) << 23) | (man << 13);
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    auto half_rtz = [](float v) -> uint16_t { // f32 -> f16, round toward zero, subnormals kept, |v| < 65520
-        uint32_t u;
-        std::memcpy(&u, &v, 4);
-        const uint16_t sgn = (uint16_t)((u >> 16) & 0x8000u);
-        const int ex = (int)((u >> 23) & 0xFFu) - 127;
-        const uint32_t man = (u & 0x7FFFFFu) | 0x800000u;
-        if (((u >> 23) & 0xFFu) == 0) return sgn;                        // f32 zero / subnormal
-        if (ex >= -14) return (uint16_t)(sgn | ((uint32_t)(ex + 15) << 10) | ((man >> 13) & 0x3FFu));
-        if (ex < -25) return sgn;
-        return (uint16_t)(sgn | (man >> (13 + (-14 - ex))));             // subnormal: shift the mantissa out
-    };
-    auto half_rne = [&](float v) -> uint16_t { // to nearest: the truncated value or its successor, whichever is closer
-        const uint16_t lo_b = half_rtz(v);
-        const uint16_t hi_b = (uint16_t)(lo_b + 1); // next magnitude (same sign); fine below the largest finite half
-        const float a = f32_of_half(lo_b), b = f32_of_half(hi_b);
-        const float da = std::fabs(v - a), db = std::fabs(b - v);
-        return (db < da || (db == da && (hi_b & 1u) == 0)) ? hi_b : lo_b;
-    };
-    for (int L = 0; L < 5; ++L) {
-        const bool input_layer = L == 0 || L == 3;
-        for (int s = 0; s < 16; ++s) {
-            for (int lane = 0; lane < 64; ++lane) {
-                const int hp = lane >> 5, i = lane & 31;
-                const int k = input_layer ? 2 * s + hp : row_of(s, hp); // what this k-step's B operand holds in half hp
-                const float wf = (float)W(L, i, k);
-                out[(size_t)kOffW + ((size_t)(L * 4 + (s >> 2)) * 64 + lane) * 4 + (s & 3)] = wf;
-                if (!(std::fabs(wf) < 65504.0f)) f16_ok = false;
-                const uint16_t hb = f16_ok ? half_rtz(wf) : 0;
-                const uint16_t lb = f16_ok ? half_rne(wf - f32_of_half(hb)) : 0;
-                const size_t at = ((size_t)(L * 2 + (s >> 3)) * 64 + lane) * 8 + (s & 7);
-                h16[at] = hb;
-                h16[(size_t)5 * 2 * 64 * 8 + at] = lb;
+    std::vector<float> out(kBlobFloats);
+    pack_weights(w, D, A, out.data(), f16_ok);
+    return out;
+}
+
+// The same image from flat weights in device memory, one workgroup (about 10 k cells and 32-term sums: the launch is
+// latency-bound whatever its shape).  Two phases: every lane computes its cells into registers and the workgroup reduces
+// "some |folded weight| >= 65 504" through LDS; only then is anything stored, so a policy pinned to f16x3 (`pinned`)
+// whose new weights do not fit keeps its image, its flat copy and status[0], and status[1] says refused.  Otherwise
+// the head and the f32 operands are always written, the f16 operands only when all fit, and status = {f16_ok, 0}.
+// A lane owns groups of four consecutive k-steps of one operand lane: one 16-byte f32 word, 8 bytes of hi, 8 of lo.
+constexpr int kPackThreads = 1024;
+constexpr int kPackTrips = (msepack::kOperandGroups + kPackThreads - 1) / kPackThreads;
+constexpr int kMaxWeights = 2 * (2 * kHidden * kHidden + 2 * kHidden) + kHidden * kHidden + 2 * kHidden + 1; // D = A = 32
+
+__global__ __launch_bounds__(kPackThreads) void k_policy_pack(int D, int A, int pinned, const float *__restrict__ weights,
+                                                              float *__restrict__ blob, float *__restrict__ flat_copy,
+                                                              int *__restrict__ status)
+{
+    using namespace msepack;
+    __shared__ __attribute__((aligned(16))) float w[kMaxWeights];
+    __shared__ int wave_bad[kPackThreads / 64];
+    const int tid = threadIdx.x;
+    const Flat F = flat_offsets(D, A);
+    for (int i = tid; i < F.total; i += kPackThreads) w[i] = weights[i];
+    __syncthreads();
+    float wf[kPackTrips][4];
+    bool bad = false;
+#pragma unroll
+    for (int q = 0; q < kPackTrips; ++q) {
+        const int g = tid + q * kPackThreads; // = (4 L + s / 4) * 64 + lane
+        if (g < kOperandGroups) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                wf[q][j] = operand(w, F, D, A, g >> 8, 4 * ((g >> 6) & 3) + j, g & 63);
+                bad = bad || !fits_half(wf[q][j]);
             }
         }
-        for (int hh = 0; hh < 2; ++hh)
-            for (int r = 0; r < 16; ++r) out[(size_t)kOffB + (L * 2 + hh) * 16 + r] = (float)B(L, row_of(r, hh));
     }
-    double sv = 0.0;
-    for (int i = 0; i < H; ++i) sv += (double)val_w[i];
-    for (int hh = 0; hh < 2; ++hh)
-        for (int r = 0; r < 16; ++r) out[(size_t)kOffWV + hh * 16 + r] = (float)(-2.0 * (double)val_w[row_of(r, hh)]);
-    out[kOffBV] = (float)((double)val_b[0] + sv);
-    return out;
+    const int head_idx = tid - (kPackThreads - kOffW); // the last lanes, which have one operand group at most
+    float head = 0.0f;
+    if (head_idx >= 0) head = head_cell(w, F, A, head_idx);
+    const bool wave_has_bad = __ballot(bad) != 0;
+    if ((tid & 63) == 0) wave_bad[tid >> 6] = wave_has_bad ? 1 : 0;
+    __syncthreads();
+    int any_bad = 0;
+#pragma unroll
+    for (int k = 0; k < kPackThreads / 64; ++k) any_bad |= wave_bad[k];
+    if (any_bad != 0 && pinned != 0) { // wave-uniform, in fact workgroup-uniform
+        if (tid == 0) status[1] = 1;
+        return;
+    }
+    for (int i = tid; i < F.total; i += kPackThreads) flat_copy[i] = w[i];
+    if (head_idx >= 0) blob[head_idx] = head;
+    uint2 *h16 = reinterpret_cast<uint2 *>(blob + kOffW16); // four 16-bit cells per word
+#pragma unroll
+    for (int q = 0; q < kPackTrips; ++q) {
+        const int g = tid + q * kPackThreads;
+        if (g < kOperandGroups) {
+            reinterpret_cast<float4 *>(blob + kOffW)[g] = make_float4(wf[q][0], wf[q][1], wf[q][2], wf[q][3]);
+            if (any_bad == 0) {
+                HalfPair p[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p[j] = split_half(wf[q][j]);
+                const int at = f16_cell(g >> 8, 4 * ((g >> 6) & 3), g & 63) >> 2;
+                h16[at] = make_uint2((uint32_t)p[0].hi | ((uint32_t)p[1].hi << 16), (uint32_t)p[2].hi | ((uint32_t)p[3].hi << 16));
+                h16[kOperandCells / 4 + at] =
+                    make_uint2((uint32_t)p[0].lo | ((uint32_t)p[1].lo << 16), (uint32_t)p[2].lo | ((uint32_t)p[3].lo << 16));
+            }
+        }
+    }
+    if (tid == 0) {
+        status[0] = any_bad == 0 ? 1 : 0;
+        status[1] = 0;
+    }
+}
+
+// blocking read of device memory the last device repack may still be writing: behind it on its stream
+bool read_behind_repack(const mse_policy *p, void *dst, const void *src, size_t bytes)
+{
+    hipStream_t s = static_cast<hipStream_t>(p->stream);
+    return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
 }
 
 } // namespace
@@ -199,10 +215,18 @@ int mse_policy_create(mse_policy **out, int obs_dim, int n_actions, const float 
     if (hipSetDevice(device_id) != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "hipSetDevice failed");
     bool f16_ok = false;
     const std::vector<float> packed = pack_weights(weights_host, obs_dim, n_actions, f16_ok);
-    mse_policy *p = new mse_policy{obs_dim, n_actions, device_id, nullptr, packed.size(), f16_ok ? 1 : 0, 0};
+    const int n_weights = (int)mse_policy_num_weights(obs_dim, n_actions);
+    const int status0[2] = {f16_ok ? 1 : 0, 0};
+    mse_policy *p = new mse_policy{obs_dim, n_actions, device_id, nullptr, packed.size(), f16_ok ? 1 : 0, 0, nullptr, nullptr, n_weights, 0, nullptr};
     if (hipMalloc(reinterpret_cast<void **>(&p->blob), p->blob_floats * sizeof(float)) != hipSuccess ||
-        hipMemcpy(p->blob, packed.data(), p->blob_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMalloc(reinterpret_cast<void **>(&p->flat), (size_t)n_weights * sizeof(float)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&p->status), sizeof(status0)) != hipSuccess ||
+        hipMemcpy(p->blob, packed.data(), p->blob_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p->flat, weights_host, (size_t)n_weights * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p->status, status0, sizeof(status0), hipMemcpyHostToDevice) != hipSuccess) {
         if (p->blob) (void)hipFree(p->blob);
+        if (p->flat) (void)hipFree(p->flat);
+        if (p->status) (void)hipFree(p->status);
         delete p;
         return mse_internal_fail(MSE_ERR_HIP, "mse_policy_create: device allocation or copy failed");
     }
@@ -219,9 +243,66 @@ int mse_policy_set_weights(mse_policy *p, const float *weights_host)
         return mse_internal_fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_policy_set_weights: a folded weight exceeds f16's range (65 504) and the f16x3 form was asked for");
     // blocking copy from pageable memory: hipMemcpy returns once the device image is written.  The caller keeps the
     // ordering rule of mse.h (no launch that reads this policy in flight on another stream).
-    if (hipMemcpy(p->blob, packed.data(), p->blob_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(p->blob, packed.data(), p->blob_floats * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(p->flat, weights_host, (size_t)p->n_weights * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
         return mse_internal_fail(MSE_ERR_HIP, "mse_policy_set_weights: device copy failed");
     p->f16_ok = f16_ok ? 1 : 0;
+    p->pending = 0; // this image replaces whatever a device repack left: its status no longer matters
+    return MSE_OK;
+}
+
+int mse_policy_set_weights_device(mse_policy *p, const float *weights_dev, void *stream)
+{
+    if (p == nullptr || weights_dev == nullptr)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_set_weights_device: null argument");
+    hipLaunchKernelGGL(k_policy_pack, dim3(1), dim3(kPackThreads), 0, static_cast<hipStream_t>(stream), p->d_in, p->n_act,
+                       p->precision == 2 ? 1 : 0, weights_dev, p->blob, p->flat, p->status);
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_policy_set_weights_device: kernel launch failed");
+    p->pending = 1;
+    p->stream = stream;
+    return MSE_OK;
+}
+
+int mse_policy_sync(mse_policy *p)
+{
+    if (p == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_sync: null argument");
+    if (!p->pending) return MSE_OK;
+    int status[2] = {0, 0};
+    if (!read_behind_repack(p, status, p->status, sizeof(status))) return mse_internal_fail(MSE_ERR_HIP, "mse_policy_sync: device read failed");
+    p->pending = 0;
+    if (status[1] != 0)
+        return mse_internal_fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_policy_sync: a folded weight exceeds f16's range (65 504) and the f16x3 form was asked for; the policy keeps its previous weights");
+    p->f16_ok = status[0] != 0 ? 1 : 0;
+    return MSE_OK;
+}
+
+int64_t mse_policy_image_floats(void) { return kBlobFloats; }
+
+int mse_policy_pack_host(int obs_dim, int n_actions, const float *weights_host, float *image_out, int32_t *f16_ok_out)
+{
+    if (weights_host == nullptr || image_out == nullptr || f16_ok_out == nullptr)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_pack_host: null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return mse_internal_fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_policy_pack_host: obs_dim and n_actions must be in 1..32");
+    bool f16_ok = false;
+    pack_weights(weights_host, obs_dim, n_actions, image_out, f16_ok);
+    *f16_ok_out = f16_ok ? 1 : 0;
+    return MSE_OK;
+}
+
+int mse_policy_read_image(mse_policy *p, float *image_out_host)
+{
+    if (p == nullptr || image_out_host == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_read_image: null argument");
+    if (!read_behind_repack(p, image_out_host, p->blob, p->blob_floats * sizeof(float)))
+        return mse_internal_fail(MSE_ERR_HIP, "mse_policy_read_image: device read failed");
+    return MSE_OK;
+}
+
+int mse_policy_get_weights(mse_policy *p, float *out_host)
+{
+    if (p == nullptr || out_host == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_policy_get_weights: null argument");
+    if (!read_behind_repack(p, out_host, p->flat, (size_t)p->n_weights * sizeof(float)))
+        return mse_internal_fail(MSE_ERR_HIP, "mse_policy_get_weights: device read failed");
     return MSE_OK;
 }
 
@@ -240,6 +321,8 @@ int mse_policy_destroy(mse_policy *p)
 {
     if (p == nullptr) return MSE_OK;
     (void)hipFree(p->blob);
+    (void)hipFree(p->flat);
+    (void)hipFree(p->status);
     delete p;
     return MSE_OK;
 }

@@ -534,6 +534,12 @@ struct mse_policy {
     size_t blob_floats;
     int f16_ok;       // every folded weight fits f16's range: the f16x3 form may be used
     int precision;    // 0 auto (f16x3 when f16_ok), 1 exact f32, 2 f16x3
+    // the device repack (mse_policy_set_weights_device); all allocated at creation
+    float *flat;      // device copy of the flat weights the image was packed from (n_weights floats)
+    int *status;      // device int[2], written by k_policy_pack: {f16_ok of the new image, refused}
+    int n_weights;
+    int pending;      // a device repack has been enqueued whose status mse_policy_sync has not read yet
+    void *stream;     // the stream of the last device repack: blocking reads of blob / flat / status wait for it
     bool use_f16() const { return precision == 2 || (precision == 0 && f16_ok); }
 };
 

@@ -37,6 +37,19 @@ constexpr int kMiscFloats = 20;        // advantage mean / std, the waves' loss 
 
 __host__ __device__ constexpr long long slab_stride(long long w) { return (w + kStatFloats + 3) / 4 * 4; }
 
+// ---- the target_kl gate ------------------------------------------------------------------------------------------------
+// control = {stopped, minibatches_run} (caller-owned, NULL: no gate).  Only the lane of k_ppo_reduce that writes stats_out
+// ever writes it, so a kernel that reads `stopped` at entry reads what an EARLIER launch of the stream left: the load
+// is uniform over the whole grid.  k_ppo_reduce itself cannot read it that way (its other workgroups may start after
+// that lane has stored), so workgroup 0 of k_ppo_grad, one launch earlier, leaves the value it saw in float 5 of slab 0's
+// statistics (a cell no sum reads; 0 when there is no gate, as it always was) and k_ppo_reduce gates on that.
+constexpr int kGateCell = 5;
+struct Gate {
+    int *control;    // NULL: no gate
+    double kl_limit; // 1.5 * target_kl; <= 0: the flag is honoured and the count kept, but never set
+};
+__device__ __forceinline__ bool gate_closed(const int *control) { return control != nullptr && control[0] != 0; }
+
 // ---- GAE ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_gae(int k_steps, long long n, const float *__restrict__ rewards,
                                              const float *__restrict__ values, const uint8_t *__restrict__ episode_starts,
@@ -56,9 +69,11 @@ __device__ __forceinline__ long long row_at(const long long *rows, long long b, 
 }
 
 __global__ __launch_bounds__(256) void k_ppo_adv_partial(long long batch, long long n_rows, const long long *__restrict__ rows,
-                                                         const float *__restrict__ adv, double *__restrict__ partial)
+                                                         const float *__restrict__ adv, double *__restrict__ partial,
+                                                         const int *__restrict__ control)
 {
     __shared__ double sh[2][256];
+    if (gate_closed(control)) return;
     const double pivot = (double)adv[row_at(rows, 0, n_rows)];
     double s = 0.0, q = 0.0;
     for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < batch; b += (long long)gridDim.x * 256) {
@@ -183,10 +198,15 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
                                                   const float *__restrict__ obs, const uint8_t *__restrict__ mask,
                                                   const int *__restrict__ actions, const float *__restrict__ old_logp,
                                                   const float *__restrict__ adv, const float *__restrict__ ret,
-                                                  const double *__restrict__ adv_partial, float *__restrict__ slabs)
+                                                  const double *__restrict__ adv_partial, float *__restrict__ slabs,
+                                                  const int *__restrict__ control)
 {
     typedef Padded<DP, AP> PW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    if (gate_closed(control)) { // grid-uniform; the mark for k_ppo_reduce is all a closed gate writes
+        if (blockIdx.x == 0 && threadIdx.x == 0) slabs[flat_layout(G.D, G.A).total + kGateCell] = 1.0f;
+        return;
+    }
     float *wl0 = lds;                     // PW::total floats: the padded weights
     float *strips = lds + PW::total;      // 4 x kStageFloats: one staging strip per wave
     // (no static __shared__: it would shift the dynamic base off its 16-byte alignment)
@@ -338,9 +358,10 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
 __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int w_total, const float *__restrict__ slabs,
                                                     const long long *__restrict__ rows, const float *__restrict__ adv,
                                                     const double *__restrict__ adv_partial, float *__restrict__ grad_out,
-                                                    float *__restrict__ stats_out)
+                                                    float *__restrict__ stats_out, Gate gate)
 {
     const long long stride = slab_stride(w_total);
+    if (gate.control != nullptr && slabs[w_total + kGateCell] != 0.0f) return; // the gate as k_ppo_grad saw it
     if (blockIdx.x + 1 < gridDim.x) {
         const int i = blockIdx.x * 256 + threadIdx.x;
         if (i >= w_total) return;
@@ -370,6 +391,11 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
         stats_out[5] = (float)sums[4];
         stats_out[6] = mean;
         stats_out[7] = std;
+        if (gate.control != nullptr) {
+            gate.control[1] = gate.control[1] + 1;
+            // SB3: `approx_kl_div > 1.5 * self.target_kl`, a float32 mean against a Python float
+            if (gate.kl_limit > 0.0 && (double)stats_out[4] > gate.kl_limit) gate.control[0] = 1;
+        }
     }
 }
 
@@ -383,9 +409,11 @@ struct AdamArgs {
 };
 
 __global__ __launch_bounds__(1024) void k_ppo_adam(AdamArgs a, float *__restrict__ w, const float *__restrict__ grad,
-                                                   float *__restrict__ m, float *__restrict__ v, float *__restrict__ norm_out)
+                                                   float *__restrict__ m, float *__restrict__ v, float *__restrict__ norm_out,
+                                                   const int *__restrict__ control)
 {
     __shared__ double sh[1024];
+    if (gate_closed(control)) return;
     double s = 0.0;
     for (int i = threadIdx.x; i < a.n; i += 1024) s += (double)grad[i] * (double)grad[i];
     sh[threadIdx.x] = s;
@@ -454,12 +482,79 @@ int cu_count()
 template <int DP, int AP>
 int launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
                 const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
-                const double *adv_partial, float *slabs)
+                const double *adv_partial, float *slabs, const int *control)
 {
     const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
     hipLaunchKernelGGL((k_ppo_grad<DP, AP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
-                       old_logp, adv, ret, adv_partial, slabs);
+                       old_logp, adv, ret, adv_partial, slabs, control);
     return 0;
+}
+
+// mse_ppo_loss_grad (control == NULL) and mse_ppo_loss_grad_gated; `who` names the entry point in messages
+int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+              int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+              const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out, float *stats_out,
+              void *workspace, void *stream, Gate gate)
+{
+    auto fail = [who](int status, const char *why) { return mse_internal_fail(status, (std::string(who) + ": " + why).c_str()); };
+    if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
+        returns == nullptr || params == nullptr || grad_out == nullptr || stats_out == nullptr || workspace == nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "obs_dim and n_actions must be in 1..32");
+    if (params->struct_size != sizeof(mse_ppo_params))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_params.struct_size mismatch");
+    if (n_rows < 1 || batch < 1 || (rows_dev == nullptr && batch > n_rows))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need 1 <= batch (<= n_rows without rows_dev)");
+    if (!(params->clip_range >= 0.0f) || !std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "bad clip_range / ent_coef / vf_coef");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
+        return fail(MSE_ERR_ALIGNMENT, "workspace must be 16-byte aligned");
+    const int cus = cu_count();
+    if (cus <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *adv_partial = static_cast<double *>(workspace);
+    float *slabs = reinterpret_cast<float *>(adv_partial + 2 * kMaxAdvPartials);
+    const long long *rows = reinterpret_cast<const long long *>(rows_dev);
+    GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch, 0,
+               Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage}};
+    if (params->normalize_advantage != 0 && batch > 1) {
+        long long g1 = (batch + 1023) / 1024;
+        G.n_adv_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
+        hipLaunchKernelGGL(k_ppo_adv_partial, dim3((unsigned)G.n_adv_partial), dim3(256), 0, s, (long long)batch, (long long)n_rows, rows,
+                           advantages, adv_partial, gate.control);
+    }
+    const long long tiles = (batch + 63) / 64;
+    long long n_slabs = (tiles + 1) / 2;
+    const long long cap = 2LL * cus < kMaxSlabs ? 2LL * cus : kMaxSlabs;
+    if (n_slabs > cap) n_slabs = cap;
+    // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
+#define MSE_PPO_LAUNCH(DP, AP) \
+    launch_grad<DP, AP>(G, (int)n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, gate.control)
+    MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
+#undef MSE_PPO_LAUNCH
+    const int w_total = flat_layout(obs_dim, n_actions).total;
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)n_slabs, w_total, slabs, rows,
+                       advantages, adv_partial, grad_out, stats_out, gate);
+    if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
+}
+
+int adam_step(const char *who, int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
+              double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream, const int *control)
+{
+    auto fail = [who](int status, const char *why) { return mse_internal_fail(status, (std::string(who) + ": " + why).c_str()); };
+    if (weights == nullptr || grad == nullptr || m == nullptr || v == nullptr) return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_weights < 1 || n_weights > (1 << 24) || step < 1)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need 1 <= n_weights <= 2^24 and step >= 1");
+    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "bad lr / beta / eps");
+    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
+    AdamArgs a{(int)n_weights, (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2)), (float)beta1, (float)beta2, (float)eps,
+               (float)max_grad_norm, (float)(1.0 - beta1), (float)(1.0 - beta2)};
+    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, weights, grad, m, v, grad_norm_out, control);
+    if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
 }
 
 } // namespace
@@ -496,64 +591,35 @@ int mse_ppo_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int6
                       const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
                       float *stats_out, void *workspace, void *stream)
 {
-    if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
-        returns == nullptr || params == nullptr || grad_out == nullptr || stats_out == nullptr || workspace == nullptr)
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: null argument");
-    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: obs_dim and n_actions must be in 1..32");
-    if (params->struct_size != sizeof(mse_ppo_params))
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: mse_ppo_params.struct_size mismatch");
-    if (n_rows < 1 || batch < 1 || (rows_dev == nullptr && batch > n_rows))
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: need 1 <= batch (<= n_rows without rows_dev)");
-    if (!(params->clip_range >= 0.0f) || !std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef))
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad: bad clip_range / ent_coef / vf_coef");
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
-        return mse_internal_fail(MSE_ERR_ALIGNMENT, "mse_ppo_loss_grad: workspace must be 16-byte aligned");
-    const int cus = cu_count();
-    if (cus <= 0) return mse_internal_fail(MSE_ERR_NO_DEVICE, "mse_ppo_loss_grad: no HIP device (there is no CPU path)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double *adv_partial = static_cast<double *>(workspace);
-    float *slabs = reinterpret_cast<float *>(adv_partial + 2 * kMaxAdvPartials);
-    const long long *rows = reinterpret_cast<const long long *>(rows_dev);
-    GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch, 0,
-               Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage}};
-    if (params->normalize_advantage != 0 && batch > 1) {
-        long long g1 = (batch + 1023) / 1024;
-        G.n_adv_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
-        hipLaunchKernelGGL(k_ppo_adv_partial, dim3((unsigned)G.n_adv_partial), dim3(256), 0, s, (long long)batch, (long long)n_rows, rows,
-                           advantages, adv_partial);
-    }
-    const long long tiles = (batch + 63) / 64;
-    long long n_slabs = (tiles + 1) / 2;
-    const long long cap = 2LL * cus < kMaxSlabs ? 2LL * cus : kMaxSlabs;
-    if (n_slabs > cap) n_slabs = cap;
-    // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
-#define MSE_PPO_LAUNCH(DP, AP) \
-    launch_grad<DP, AP>(G, (int)n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs)
-    MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
-#undef MSE_PPO_LAUNCH
-    const int w_total = flat_layout(obs_dim, n_actions).total;
-    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)n_slabs, w_total, slabs, rows,
-                       advantages, adv_partial, grad_out, stats_out);
-    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_loss_grad: kernel launch failed");
-    return MSE_OK;
+    return loss_grad("mse_ppo_loss_grad", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
+                     advantages, returns, params, grad_out, stats_out, workspace, stream, Gate{nullptr, 0.0});
+}
+
+int mse_ppo_loss_grad_gated(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                            float *stats_out, void *workspace, void *stream, double target_kl, int32_t *control_dev)
+{
+    if (control_dev == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_gated: null control block");
+    if (target_kl != target_kl) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_gated: target_kl is NaN");
+    return loss_grad("mse_ppo_loss_grad_gated", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
+                     advantages, returns, params, grad_out, stats_out, workspace, stream, Gate{control_dev, 1.5 * target_kl});
 }
 
 int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
                       double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream)
 {
-    if (weights == nullptr || grad == nullptr || m == nullptr || v == nullptr)
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: null argument");
-    if (n_weights < 1 || n_weights > (1 << 24) || step < 1)
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: need 1 <= n_weights <= 2^24 and step >= 1");
-    if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0))
-        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step: bad lr / beta / eps");
-    const double bc1 = 1.0 - std::pow(beta1, (double)step), bc2 = 1.0 - std::pow(beta2, (double)step);
-    AdamArgs a{(int)n_weights, (float)(lr / bc1), (float)(1.0 / std::sqrt(bc2)), (float)beta1, (float)beta2, (float)eps,
-               (float)max_grad_norm, (float)(1.0 - beta1), (float)(1.0 - beta2)};
-    hipLaunchKernelGGL(k_ppo_adam, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), a, weights, grad, m, v, grad_norm_out);
-    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_ppo_adam_step: kernel launch failed");
-    return MSE_OK;
+    return adam_step("mse_ppo_adam_step", n_weights, weights, grad, m, v, step, lr, beta1, beta2, eps, max_grad_norm, grad_norm_out,
+                     stream, nullptr);
+}
+
+int mse_ppo_adam_step_gated(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,
+                            double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream,
+                            const int32_t *control_dev)
+{
+    if (control_dev == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_adam_step_gated: null control block");
+    return adam_step("mse_ppo_adam_step_gated", n_weights, weights, grad, m, v, step, lr, beta1, beta2, eps, max_grad_norm,
+                     grad_norm_out, stream, control_dev);
 }
 
 int mse_ppo_shuffle(int64_t total, uint64_t seed, uint64_t epoch, int64_t first, int64_t count, int64_t *rows_out_dev, void *stream)

@@ -4,7 +4,8 @@
 `PPOLearner.update` is `MaskablePPO.train` on them: per minibatch one `mse_ppo_loss_grad` (loss, its statistics and
 the gradient w.r.t. all weights, three launches) and one `mse_ppo_adam_step` (clip_grad_norm_ + Adam), all enqueued
 without a host synchronisation; the new weights go back into the policy the rollout kernels read once per update
-(`MlpPolicy.load_weights`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
+(`MlpPolicy.load_weights`, or with `weight_sync="device"` one repack launch, `MlpPolicy.load_weights_device`).  SB3's
+`target_kl` early stop is a flag on the device that the gated entry points read (`mse_ppo_loss_grad_gated`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
 computes anything on this path, and there is no CPU fallback.  With `shuffle="device"` the permutation is a kernel too
 (`mse_ppo_shuffle`, a counter-based function of seed and epoch that `PPOLearner.permutation` replays on the host).
 `learn` can report the reference's unit, cumulative reward per episode (episodes.py): SB3's `rollout/ep_rew_mean` from an
@@ -66,14 +67,27 @@ class PPOLearner:
     copies the indices up; `last_permutations` keeps them.  `shuffle="device"` fills one i64[K * N] device buffer per
     epoch with `mse_ppo_shuffle(total, seed, epochs_done, ...)` on the current stream: no host work, no copy.
     `epochs_done` counts the epochs of the learner's lifetime, so no two share a permutation; `last_epochs` lists the
-    counters the last `update()` used and `permutation(total, epoch)` returns the same rows on the CPU."""
+    counters the last `update()` used and `permutation(total, epoch)` returns the same rows on the CPU.
+
+    `weight_sync="host"` (the default) hands the new weights to the policy through the host (`load_weights`: a copy down,
+    the host repack, a blocking copy up); `"device"` enqueues `load_weights_device` behind the last Adam step, so an
+    update ends in the one small copy of its statistics and `policy.sync()`.  Same weights, same image, bit for bit.
+
+    `target_kl` (SB3's; None = off): after a minibatch whose approx_kl exceeds 1.5 * target_kl that minibatch takes no
+    optimiser step and no later minibatch of the update runs.  The decision is taken on the device: `update()` still
+    enqueues every minibatch, the ones after the stop exit at once, and the result says what ran.  `step` counts the
+    Adam steps actually taken; `epochs_done` advances by the epochs ENQUEUED (n_epochs per update), run or not."""
 
     def __init__(self, policy: MlpPolicy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
                  gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: float = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
-                 seed: int = 0, shuffle: str = "cpu"):
+                 seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None):
         if shuffle not in ("cpu", "device"):
             raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
+        if weight_sync not in ("host", "device"):
+            raise ValueError(f"weight_sync must be 'host' or 'device', not {weight_sync!r}")
+        self.weight_sync = weight_sync
+        self.target_kl = None if target_kl is None else float(target_kl)
         self.policy, self.L = policy, policy.L
         self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
@@ -103,9 +117,11 @@ class PPOLearner:
         self.best_weights = None  # f32[W] on the device, a copy of `weights` at the best evaluation
 
     def loss_grad(self, data: dict, rows: Optional[torch.Tensor], batch: int, stats_out: torch.Tensor,
-                  weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None,
+                  control: Optional[torch.Tensor] = None, target_kl: float = 0.0) -> torch.Tensor:
         """One `mse_ppo_loss_grad` on the flattened rollout in `data` (which holds advantages / returns); returns the
-        gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1."""
+        gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1.
+        control: i32[2] device tensor {stopped, minibatches_run}: `mse_ppo_loss_grad_gated` with `target_kl` instead."""
         p = self.policy
         obs = data["observations"]
         n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
@@ -115,19 +131,34 @@ class PPOLearner:
         for name in ("observations", "actions", "log_probs", "advantages", "returns"):
             if not data[name].is_contiguous():
                 raise ValueError(f"{name} must be contiguous")
+        args = (p.obs_dim, p.n_actions, _ptr(w), n_rows, _ptr(rows), int(batch), _ptr(obs), _ptr(mask), _ptr(data["actions"]),
+                _ptr(data["log_probs"]), _ptr(data["advantages"]), _ptr(data["returns"]), C.byref(self.params), _ptr(g),
+                _ptr(stats_out), _ptr(self.workspace), _stream(self.device))
         with torch.cuda.device(self.device):
-            check(self.L.mse_ppo_loss_grad(p.obs_dim, p.n_actions, _ptr(w), n_rows, _ptr(rows), int(batch), _ptr(obs), _ptr(mask),
-                                           _ptr(data["actions"]), _ptr(data["log_probs"]), _ptr(data["advantages"]),
-                                           _ptr(data["returns"]), C.byref(self.params), _ptr(g), _ptr(stats_out),
-                                           _ptr(self.workspace), _stream(self.device)))
+            if control is None:
+                check(self.L.mse_ppo_loss_grad(*args))
+            else:
+                check(self.L.mse_ppo_loss_grad_gated(*args, float(target_kl), _ptr(control)))
         return g
 
-    def adam_step(self):
+    def adam_step(self, control: Optional[torch.Tensor] = None):
+        """One Adam step; with `control`, `mse_ppo_adam_step_gated`: nothing happens on the device once it says stopped
+        (`step` still advances here: `update()` corrects it from the control block)."""
         self.step += 1
+        args = (self.n_weights, _ptr(self.weights), _ptr(self.grad), _ptr(self.m), _ptr(self.v), self.step, self.learning_rate,
+                self.beta1, self.beta2, self.adam_eps, self.max_grad_norm, _ptr(self.grad_norm), _stream(self.device))
         with torch.cuda.device(self.device):
-            check(self.L.mse_ppo_adam_step(self.n_weights, _ptr(self.weights), _ptr(self.grad), _ptr(self.m), _ptr(self.v),
-                                           self.step, self.learning_rate, self.beta1, self.beta2, self.adam_eps,
-                                           self.max_grad_norm, _ptr(self.grad_norm), _stream(self.device)))
+            if control is None:
+                check(self.L.mse_ppo_adam_step(*args))
+            else:
+                check(self.L.mse_ppo_adam_step_gated(*args, _ptr(control)))
+
+    def _hand_over(self) -> None:
+        """The master weights into the policy the rollout kernels read."""
+        if self.weight_sync == "device":
+            self.policy.load_weights_device(self.weights, sync=False)  # one launch behind the last Adam step
+        else:
+            self.policy.load_weights(self.weights)  # the device-to-host copy waits for the stream
 
     def permutation(self, total: int, epoch: int) -> torch.Tensor:
         """The rows of epoch counter `epoch` over a rollout of `total` rows as shuffle="device" orders them: an i64 CPU
@@ -149,15 +180,24 @@ class PPOLearner:
         """GAE, then n_epochs passes over a permutation of the K * N rows (shuffle="cpu": seeded on the CPU and copied to
         the device once per epoch; shuffle="device": one `mse_ppo_shuffle` launch per epoch; the last minibatch of an
         epoch may be short), one loss_grad + adam_step per minibatch without a host
-        synchronisation, then one `policy.load_weights`.  Returns {"stats": f32[n_minibatches, 8] (device; columns
-        STAT_NAMES), "mean": {name: float}}."""
+        synchronisation, then the weights' hand-over to the policy (`weight_sync`).  Returns {"stats":
+        f32[n_minibatches, 8] (device; columns STAT_NAMES), "mean": {name: float}}.
+        With `target_kl` the result gains "stopped" (bool) and "minibatches_run" (int): "mean" is over the first
+        minibatches_run rows of "stats", the rows after them stay zero."""
         compute_gae(data, self.gamma, self.gae_lambda)
         K, n = data["rewards"].shape
         total = K * n
         bs = self.batch_size if self.batch_size is not None else (total + 3) // 4
         bs = max(1, min(int(bs), total))
         per_epoch = (total + bs - 1) // bs
-        stats = torch.zeros((self.n_epochs * per_epoch, 8), dtype=torch.float32, device=self.device)
+        n_mb = self.n_epochs * per_epoch
+        gated = self.target_kl is not None
+        if gated:  # statistics and control block in one buffer, so that one copy brings both to the host
+            buf = torch.zeros(n_mb * 8 + 2, dtype=torch.float32, device=self.device)
+            stats, control = buf[:n_mb * 8].view(n_mb, 8), buf[n_mb * 8:].view(torch.int32)
+        else:
+            stats, control = torch.zeros((n_mb, 8), dtype=torch.float32, device=self.device), None
+        step0 = self.step
         self.last_permutations, self.last_epochs = [], []
         i = 0
         for _ in range(self.n_epochs):
@@ -169,17 +209,25 @@ class PPOLearner:
                 perm = perm_cpu.to(self.device)
             for start in range(0, total, bs):
                 rows = perm[start:start + bs]
-                self.loss_grad(data, rows, rows.numel(), stats[i])
-                self.adam_step()
+                self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
+                self.adam_step(control)
                 i += 1
-        self.policy.load_weights(self.weights)  # the device-to-host copy waits for the stream
-        mean = stats.mean(dim=0).cpu().tolist()
-        return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+        self._hand_over()
+        if not gated:
+            mean = stats.mean(dim=0).cpu().tolist()
+            self.policy.sync()
+            return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+        host = buf.cpu()
+        self.policy.sync()
+        stopped, run = (int(x) for x in host[n_mb * 8:].view(torch.int32))
+        self.step = step0 + run - (1 if stopped else 0)  # the stopping minibatch took no step, nor did any after it
+        mean = host[:n_mb * 8].view(n_mb, 8)[:run].mean(dim=0).tolist()
+        return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean)), "stopped": bool(stopped), "minibatches_run": run}
 
     def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
               eval_freq: int = 0, n_eval_episodes: int = 10) -> list:
         """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
-        mean reward per env-step under "reward".
+        mean reward per env-step under "reward" (and, with `target_kl`, the update's "stopped" and "minibatches_run").
         episode_stats=True: each record gains `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in
         that iteration's rollout (NaN when none did); the running returns persist in `self.episode_stats` across
         iterations and across calls.
@@ -204,6 +252,8 @@ class PPOLearner:
                 self.episode_stats.update(data)
             out = self.update(data)
             rec = dict(out["mean"], reward=float(data["rewards"].mean()))
+            if "stopped" in out:  # target_kl is set
+                rec.update(stopped=out["stopped"], minibatches_run=out["minibatches_run"])
             if episode_stats:
                 t = self.episode_stats.totals()
                 rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
@@ -225,4 +275,5 @@ class PPOLearner:
         if self.best_weights is None:
             raise RuntimeError("no evaluation has run: there are no best weights")
         self.weights.copy_(self.best_weights)
-        self.policy.load_weights(self.weights)
+        self._hand_over()
+        self.policy.sync()

@@ -66,6 +66,22 @@ class MlpPolicy:
         self._h = h
         self.set_precision(precision)
 
+    @property
+    def weights(self) -> dict:
+        """The weights under SB3_KEYS as flat numpy arrays.  After `load_weights_device` the first access reads them back
+        from the handle's own device copy (`mse_policy_get_weights`, a blocking copy)."""
+        if self._weights is None:
+            flat = np.empty(self.L.mse_policy_num_weights(self.obs_dim, self.n_actions), dtype=np.float32)
+            with torch.cuda.device(self.device):
+                check(self.L.mse_policy_get_weights(self._h, C.c_void_p(flat.ctypes.data)))
+            sizes = [int(np.prod(s)) for s in _shapes(self.obs_dim, self.n_actions)]
+            self._weights = dict(zip(SB3_KEYS, np.split(flat, np.cumsum(sizes)[:-1])))
+        return self._weights
+
+    @weights.setter
+    def weights(self, value: dict) -> None:
+        self._weights = value
+
     def set_precision(self, precision: str) -> str:
         """"f32": exact f32 matrix products; "f16x3": three f16 MFMAs per product on 22-bit operand splits (logits
         within ~1e-6 of f32 at SB3-scale weights, ~3e-5 of float64 with hidden pre-activations of ~40; 5x the matrix
@@ -124,6 +140,37 @@ class MlpPolicy:
         self.weights = {k: p.copy() for k, p in zip(SB3_KEYS, np.split(blob, np.cumsum(sizes)[:-1]))}
         self.precision = "f16x3" if self.L.mse_policy_precision(self._h) == 2 else "f32"
         return self
+
+    def load_weights_device(self, weights: torch.Tensor, sync: bool = True) -> "MlpPolicy":
+        """Replaces the weights from a flat f32 device tensor (SB3_KEYS order) without the host: one launch on the current
+        stream repacks them on the device (`mse_policy_set_weights_device`, the image `load_weights` would write, byte
+        for byte) and copies them into a buffer the handle owns, which `weights`, `flat_weights()` and `state_dict()`
+        read back on their next use - `weights` itself may be overwritten afterwards.  Launches enqueued on that stream
+        afterwards see the new weights; for other streams the rule of `load_weights` stands.
+        sync=True: `sync()` right away.  sync=False: nothing waits; call `sync()` before the next launch whenever the new
+        weights may cross f16's range - until then `precision` and the launches keep the form last known."""
+        n = self.L.mse_policy_num_weights(self.obs_dim, self.n_actions)
+        if not isinstance(weights, torch.Tensor) or weights.device != self.device or weights.dtype != torch.float32 \
+                or not weights.is_contiguous():
+            raise ValueError(f"weights must be a contiguous float32 tensor on {self.device}")
+        if weights.numel() != n:
+            raise ValueError(f"expected {n} weights, got {weights.numel()}")
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            check(self.L.mse_policy_set_weights_device(self._h, C.c_void_p(weights.data_ptr()), stream))
+        self._weights = None  # read back from the handle on the next access
+        if sync:
+            self.sync()
+        return self
+
+    def sync(self) -> str:
+        """After `load_weights_device(sync=False)`: one small blocking read (`mse_policy_sync`) that brings `precision`
+        up to date (an "auto" policy moves to f32 when a folded weight has left f16's range, and back).  Raises MseError
+        when the policy is pinned to f16x3 and refused the weights: it then still holds the previous ones."""
+        with torch.cuda.device(self.device):
+            check(self.L.mse_policy_sync(self._h))
+        self.precision = "f16x3" if self.L.mse_policy_precision(self._h) == 2 else "f32"
+        return self.precision
 
     def flat_weights(self) -> np.ndarray:
         """The weights as one float32 vector in the order of include/mse.h (SB3_KEYS)."""

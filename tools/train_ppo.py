@@ -5,7 +5,9 @@
     python tools/train_ppo.py --kind mono --episode-stats --eval-every 5   # ep_rew_mean / ep_len_mean of the training rollouts and
                                                           # evaluate_policy on 10 envs of their own every 5th iteration
     python tools/train_ppo.py --kind mono --time          # rows/s of mse_ppo_loss_grad beside torch f32 autograd, and one
-                                                          # update() with shuffle="cpu" and shuffle="device"
+                                                          # update() with shuffle="cpu" and shuffle="device"; then the weight
+                                                          # hand-over alone and inside update(), host against device
+    python tools/train_ppo.py --kind mono --weight-sync device --target-kl 0.03   # repack on the device; SB3's early stop
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -112,6 +114,43 @@ def time_loss_grad(args):
               + ", ".join(f"shuffle={mode} " + " / ".join(f"{t * 1e3:.2f}" for t in ts) + " ms" for mode, ts in t_upd.items()))
 
 
+def time_weight_sync(args):
+    """The weight hand-over, host against device, at 4 096, 65 536 and 2^20 rows: `load_weights` against
+    `load_weights_device(sync=True)` alone, and one update() with shuffle="device" under each `weight_sync`.  One warm-up
+    each, then three timed calls each, alternating; every timed region ends in a device synchronise."""
+    D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
+    K = 16
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for rows in (4096, 65536, 2 ** 20):
+        n = rows // K
+        pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+        env = M.BatchedSortingEnv(kind=args.kind, num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+        col = M.FusedPolicyRollout(env, pol, K, seed=args.seed)
+        data = col.collect()
+        w = torch.from_numpy(pol.flat_weights()).cuda()
+        loads = {"load_weights": lambda: pol.load_weights(w), "load_weights_device": lambda: pol.load_weights_device(w, sync=True)}
+        learners = {mode: M.PPOLearner(pol, ent_coef=0.05, shuffle="device", weight_sync=mode) for mode in ("host", "device")}
+        updates = {f"update weight_sync={mode}": (lambda lrn=lrn: lrn.update(data)) for mode, lrn in learners.items()}
+        for group in (loads, updates):
+            times = {name: [] for name in group}
+            for rep in range(4):
+                for name, fn in group.items():
+                    t = timed(fn)
+                    if rep > 0:
+                        times[name].append(t)
+            unit = 1e6 if group is loads else 1e3
+            print(f"{args.kind} rows={rows}: " + ", ".join(
+                f"{name} " + " / ".join(f"{t * unit:.1f}" if group is loads else f"{t * unit:.2f}" for t in ts)
+                + (" us" if group is loads else " ms") for name, ts in times.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=sorted(KINDS), default="mono")
@@ -126,6 +165,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--shuffle", choices=("cpu", "device"), default="cpu",
                     help="where an epoch's row permutation comes from: the seeded CPU generator or mse_ppo_shuffle")
+    ap.add_argument("--weight-sync", choices=("host", "device"), default="host",
+                    help="how an update hands its weights to the policy: through the host repack, or one repack launch on the device")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="SB3's target_kl: stop an update after the minibatch whose approx_kl exceeds 1.5 times this")
     ap.add_argument("--episode-stats", action="store_true",
                     help="print the episodes that ended in each rollout with their mean return and length (SB3's ep_rew_mean)")
     ap.add_argument("--eval-every", type=int, default=0,
@@ -134,20 +177,24 @@ def main():
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
     if args.time:
-        return time_loss_grad(args)
+        time_loss_grad(args)
+        return time_weight_sync(args)
     D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
     env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
     learner = M.PPOLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
-                           seed=args.seed, shuffle=args.shuffle)
-    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}")
+                           seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl)
+    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
+          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}")
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
               f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
 
+        if "stopped" in rec:
+            print(f"       minibatches run {rec['minibatches_run']}" + (" (stopped on target_kl)" if rec["stopped"] else ""))
         if "episodes" in rec:
             print(f"       episodes {rec['episodes']:6d} ep_rew_mean {rec['ep_rew_mean']:+.3f} ep_len_mean {rec['ep_len_mean']:.1f}")
         if "eval_mean_reward" in rec:
