@@ -1277,7 +1277,7 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
         const uint32_t legal[2] = {legal_of(mb0), legal_of(mb1)};
         const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
         msep::TileOut p[2];
-        msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, legal, deterministic != 0, words, nullptr, p);
+        msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, A, legal, deterministic != 0, words, nullptr, p);
         int a = p[0].action;
         float logp = p[0].logp, value = p[0].value;
         if (TILES == 2) { // lane l is env l: tile l >> 5, column l & 31 (results are valid in both halves)
@@ -1564,8 +1564,8 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
             const uint32_t legal[2] = {legal_of(mb0), legal_of(mb1)};
             const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
             msep::TileOut p[2];
-            if (kPipelinedActor) msep::actor_tiles_pipelined<NR>(wl, lane, x, legal, deterministic != 0, words, p);
-            else msep::actor_tiles<NR, true, 2>(wl, lane, x, legal, deterministic != 0, words, p);
+            if (kPipelinedActor) msep::actor_tiles_pipelined<NR>(wl, lane, x, A, legal, deterministic != 0, words, p);
+            else msep::actor_tiles<NR, true, 2>(wl, lane, x, A, legal, deterministic != 0, words, p);
             const int a = h ? p[1].action : p[0].action; // lane l is env l: tile l >> 5, column l & 31
             const float logp = h ? p[1].logp : p[0].logp;
             MSE_TLB(e.tl, 0); // actor network and sampling
@@ -1854,7 +1854,7 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
             const uint32_t legal[2] = {legal_of(pb0), legal_of(pb1)};
             const uint32_t words[2] = {0u, 0u};
             msep::TileOut p[2];
-            msep::actor_tiles<NR, true, TILES>(wl_press, lane, px, legal, true, words, p);
+            msep::actor_tiles<NR, true, TILES>(wl_press, lane, px, 11, legal, true, words, p);
             pa = (TILES == 2 && h) ? p[1].action : p[0].action;
         } else if (unmasked_draw) {
             pa = (int)prs.lemire(11u); // rng_pressing.choice(11)

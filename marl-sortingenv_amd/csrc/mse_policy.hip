@@ -69,7 +69,7 @@ __global__ __launch_bounds__(512) void k_policy_mlp(PolicyArgs P, const float *_
         }
         const uint32_t word = mse_policy_word(mse_policy_key(P.seed, (uint64_t)(P.index_offset + env)), P.t);
         float lgm[NR];
-        const TileOut o = policy_tile<NR, F16X3>(wl, lane, x, legal, P.deterministic != 0, word, lgm);
+        const TileOut o = policy_tile<NR, F16X3>(wl, lane, x, A, legal, P.deterministic != 0, word, lgm);
         if (logits_out != nullptr) { // wave-uniform
 #pragma unroll
             for (int r = 0; r < NR; ++r)

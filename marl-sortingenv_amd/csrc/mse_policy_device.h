@@ -211,10 +211,16 @@ struct TileOut {
     float logp, value;
 };
 
-// masked softmax + sample of one tile.  lg: the head's accumulator; legal: bit r set iff the action in accumulator
-// register r (row row_of(r, h)) exists and may be taken; word: the env's 32-bit draw for this step.
+// masked softmax + sample of one tile.  lg: the head's accumulator; A: the number of actions; legal: bit r set iff the
+// action in accumulator register r (row row_of(r, h)) exists and may be taken; word: the env's 32-bit draw for this step.
+// The decision rules (tests/policy_head_reference.py restates them; tests/test_gpu_policy_shapes.py pins them):
+//   deterministic  argmax of the masked logits, ties to the lowest action index (torch.argmax's first maximum);
+//   sampled        inverse cdf in register order: the first register whose running sum exceeds u x total;
+//   no legal action (an all-zero mask row): every action reads -1e8 as in sb3_contrib's MaskableCategorical, which is
+//                  the uniform distribution over the A actions - registers that hold no action ("phantoms",
+//                  row_of(r, h) >= A) carry no mass, the log-probability is -log A, the argmax is action 0.
 template <int NR>
-__device__ __forceinline__ void sample_tile(const f32x16 &lg, int h, uint32_t legal, bool deterministic, uint32_t word,
+__device__ __forceinline__ void sample_tile(const f32x16 &lg, int h, int A, uint32_t legal, bool deterministic, uint32_t word,
                                             float *lgm_out, TileOut &out)
 {
     // masked logits of the NR registers that can hold an action: illegal -> -1e8 (sb3_contrib's HUGE_NEG)
@@ -241,7 +247,10 @@ __device__ __forceinline__ void sample_tile(const f32x16 &lg, int h, uint32_t le
     float c[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
-        const float e = __builtin_amdgcn_exp2f(fmaf(lgm[r], 1.44269504088896340736f, nm)); // exp(lgm - m); illegal -> 0
+        float e = __builtin_amdgcn_exp2f(fmaf(lgm[r], 1.44269504088896340736f, nm)); // exp(lgm - m); illegal -> 0
+        // a phantom weighs as much as an illegal action: nothing, unless no action is legal (m = -1e8), where every
+        // register would weigh the same.  Folds away for the registers that hold an action in both halves.
+        e = row_of(r, h) < A ? e : 0.0f;
         c[r] = r == 0 ? e : c[r - 1] + e;
     }
     const Halves S = both_halves(c[NR - 1]); // S.lo = mass of half 0's actions, S.hi = half 1's
@@ -283,7 +292,12 @@ __device__ __forceinline__ void sample_tile(const f32x16 &lg, int h, uint32_t le
     const Halves l2 = both_halves(la);
     out.action = (int)(take_hi ? a_hi : a_lo);
     const float la_f = take_hi ? l2.hi : l2.lo;
-    out.logp = (la_f - m) - __builtin_amdgcn_logf(total) * 0.693147180559945309417f; // v_log_f32 = log2
+    // The masses are 2^(lgm log2e + nm), and nm = -m log2e is rounded: the largest mass is 2^res with res = fma(m, log2e,
+    // nm), not 1.  |res| <= half an ulp of m log2e, far below the log-probability's own error for any logit a network
+    // gives, but 1.84 at m = -1e8 (no legal action, every mass 2^res): there the numerator is res ln 2, not la - m = 0.
+    const float res = fmaf(m, 1.44269504088896340736f, nm) * 0.693147180559945309417f;
+    const float num = __float_as_uint(m) == 0xCCBEBC20u ? res : la_f - m;
+    out.logp = num - __builtin_amdgcn_logf(total) * 0.693147180559945309417f; // v_log_f32 = log2
 }
 
 // value head of one tile: the critic's second hidden layer (pre-activation c2) . wv + bv
@@ -307,7 +321,7 @@ __device__ __forceinline__ float value_tile(lds_f4 wl, int h, const f32x16 &c2)
 // The arithmetic of a tile does not depend on T or on the order below (every tile's operations are its own); the order
 // only decides what overlaps: with one tile the critic's and the actor's layers alternate, with two the tiles do.
 template <int NR, bool F16X3, int T>
-__device__ __forceinline__ void policy_tiles(lds_f4 wl, int lane, const float (*x)[16], const uint32_t *legal, bool deterministic,
+__device__ __forceinline__ void policy_tiles(lds_f4 wl, int lane, const float (*x)[16], int A, const uint32_t *legal, bool deterministic,
                                              const uint32_t *word, float *lgm_out, TileOut *out)
 {
     const int h = lane >> 5;
@@ -366,7 +380,7 @@ __device__ __forceinline__ void policy_tiles(lds_f4 wl, int lane, const float (*
     }
 #pragma unroll
     for (int t = 0; t < T; ++t)
-        sample_tile<NR>(lg[t], h, legal[t], deterministic, word[t], lgm_out == nullptr ? nullptr : lgm_out + t * NR, out[t]);
+        sample_tile<NR>(lg[t], h, A, legal[t], deterministic, word[t], lgm_out == nullptr ? nullptr : lgm_out + t * NR, out[t]);
 }
 
 // The actor alone, argmax of a two-action head, for T tiles: what Env_2_Pressing.step asks its sorting agent
@@ -408,7 +422,7 @@ __device__ __forceinline__ void actor_argmax2_tiles(lds_f4 wl, int lane, const f
 // (mse_lib.hip: k_rollout_policy_roles), whose critic runs on a partner wave.  Same layers, same bits as policy_tiles;
 // out[t].value is left alone.
 template <int NR, bool F16X3, int T>
-__device__ __forceinline__ void actor_tiles(lds_f4 wl, int lane, const float (*x)[16], const uint32_t *legal, bool deterministic,
+__device__ __forceinline__ void actor_tiles(lds_f4 wl, int lane, const float (*x)[16], int A, const uint32_t *legal, bool deterministic,
                                             const uint32_t *word, TileOut *out)
 {
     const int h = lane >> 5;
@@ -433,7 +447,7 @@ __device__ __forceinline__ void actor_tiles(lds_f4 wl, int lane, const float (*x
     }
     apply_layer<T>(wl, lane, h, 2, op, lg);
 #pragma unroll
-    for (int t = 0; t < T; ++t) sample_tile<NR>(lg[t], h, legal[t], deterministic, word[t], nullptr, out[t]);
+    for (int t = 0; t < T; ++t) sample_tile<NR>(lg[t], h, A, legal[t], deterministic, word[t], nullptr, out[t]);
 }
 
 // actor_tiles for two tiles as a software pipeline: a tile's matrix products are issued between the other tile's
@@ -450,7 +464,7 @@ __device__ __forceinline__ void actor_tiles(lds_f4 wl, int lane, const float (*x
         }                                                               \
     } while (0)
 template <int NR>
-__device__ __forceinline__ void actor_tiles_pipelined(lds_f4 wl, int lane, const float (*x)[16], const uint32_t *legal,
+__device__ __forceinline__ void actor_tiles_pipelined(lds_f4 wl, int lane, const float (*x)[16], int A, const uint32_t *legal,
                                                       bool deterministic, const uint32_t *word, TileOut *out)
 {
     const int h = lane >> 5;
@@ -483,10 +497,10 @@ __device__ __forceinline__ void actor_tiles_pipelined(lds_f4 wl, int lane, const
     MSEP_INTERLEAVE_6(12);
     __builtin_amdgcn_sched_barrier(0);
     apply_layer<1>(wl, lane, h, 2, op1, a1);
-    sample_tile<NR>(a0[0], h, legal[0], deterministic, word[0], nullptr, out[0]);
+    sample_tile<NR>(a0[0], h, A, legal[0], deterministic, word[0], nullptr, out[0]);
     MSEP_INTERLEAVE_6(12);
     __builtin_amdgcn_sched_barrier(0);
-    sample_tile<NR>(a1[0], h, legal[1], deterministic, word[1], nullptr, out[1]);
+    sample_tile<NR>(a1[0], h, A, legal[1], deterministic, word[1], nullptr, out[1]);
 }
 
 // The critic alone for T tiles: the bootstrap value of the state a rollout ends in.  Same layers, same bits as
@@ -514,14 +528,14 @@ __device__ __forceinline__ void value_tiles(lds_f4 wl, int lane, const float (*x
 
 // one tile (the standalone forward)
 template <int NR, bool F16X3>
-__device__ __forceinline__ TileOut policy_tile(lds_f4 wl, int lane, const float *x, uint32_t legal, bool deterministic,
+__device__ __forceinline__ TileOut policy_tile(lds_f4 wl, int lane, const float *x, int A, uint32_t legal, bool deterministic,
                                                uint32_t word, float *lgm_out)
 {
     float xs[1][16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) xs[0][r] = x[r];
     TileOut out[1];
-    policy_tiles<NR, F16X3, 1>(wl, lane, xs, &legal, deterministic, &word, lgm_out, out);
+    policy_tiles<NR, F16X3, 1>(wl, lane, xs, A, &legal, deterministic, &word, lgm_out, out);
     return out[0];
 }
 

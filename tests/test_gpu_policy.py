@@ -6,63 +6,14 @@ Floating point, so tolerances (written here): logits / value 2e-5 absolute (MFMA
 v_exp_f32 + v_rcp_f32), log-probabilities 1e-4.  stable_baselines3 is not installed in this image and the
 reference ships no policy fixture, so the network itself is "parity unpinned" beyond this torch reference of the
 same op; the weights are random with SB3's state_dict names and shapes."""
-import numpy as np
 import pytest
 
-from tests import policy_stream as ps
+from tests.policy_head_reference import LOGIT_TOL, SATURATING_F16X3_LOGIT_TOL, check_forward, forward_inputs
+from tests.policy_head_reference import saturating_weights as _saturating_weights
+from tests.policy_head_reference import torch_reference as _torch_reference
+from tests.policy_head_reference import weights as _weights
 
 pytestmark = pytest.mark.gpu
-
-LOGIT_TOL, LOGP_TOL = 2e-5, 1e-4
-# the f16x3 form on the saturating weight set (pre-activations up to ~40): it carries 22-bit operand splits, not f32's
-# 24 bits; measured 2.7e-5 against float64 (the f32 form 1.8e-5, torch's own fp32 1.1e-5)
-SATURATING_F16X3_LOGIT_TOL = 4e-5
-
-
-def _weights(obs_dim, n_actions, seed):
-    import torch
-
-    from marl_sortingenv_amd.policy import SB3_KEYS, _shapes
-
-    g = torch.Generator().manual_seed(seed)
-    return {k: (torch.randn(s, generator=g) * (0.5 if len(s) == 2 else 0.1)).float()
-            for k, s in zip(SB3_KEYS, _shapes(obs_dim, n_actions))}
-
-
-def _torch_reference(w, obs, mask):
-    """obs [N, D] f32 cpu, mask [N, A] bool cpu or None -> masked logits, log-softmax, value (all fp32, CPU)."""
-    import torch
-    import torch.nn.functional as F
-
-    hp = torch.tanh(F.linear(torch.tanh(F.linear(obs, w["mlp_extractor.policy_net.0.weight"],
-                                                 w["mlp_extractor.policy_net.0.bias"])),
-                             w["mlp_extractor.policy_net.2.weight"], w["mlp_extractor.policy_net.2.bias"]))
-    hv = torch.tanh(F.linear(torch.tanh(F.linear(obs, w["mlp_extractor.value_net.0.weight"],
-                                                 w["mlp_extractor.value_net.0.bias"])),
-                             w["mlp_extractor.value_net.2.weight"], w["mlp_extractor.value_net.2.bias"]))
-    logits = F.linear(hp, w["action_net.weight"], w["action_net.bias"])
-    if mask is not None:
-        logits = torch.where(mask, logits, torch.tensor(-1e8))
-    value = F.linear(hv, w["value_net.weight"], w["value_net.bias"]).squeeze(1)
-    return logits, torch.log_softmax(logits, dim=1), value
-
-
-def _saturating_weights(obs_dim, n_actions, seed):
-    """Hidden layers at 8x SB3's initial scale (pre-activations of several units: tanh saturates, the folded tanh's
-    exp2 overflows) and the action head at gain 3 (logits reach tens: a softmax dominated by one action)."""
-    import torch
-
-    from marl_sortingenv_amd.policy import SB3_KEYS, _shapes
-
-    g = torch.Generator().manual_seed(seed)
-    w = {}
-    for k, s in zip(SB3_KEYS, _shapes(obs_dim, n_actions)):
-        if len(s) == 1:
-            w[k] = (torch.randn(s, generator=g) * 0.1).float()
-        else:
-            gain = 3.0 if k == "action_net.weight" else (1.0 if k == "value_net.weight" else 8.0 * 2.0 ** 0.5)
-            w[k] = (torch.randn(s, generator=g) * gain / s[1] ** 0.5).float()
-    return w
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
@@ -79,8 +30,7 @@ def test_policy_forward_with_saturating_weights_matches_float64(obs_dim, n_actio
 
 
 def _check_forward(obs_dim, n_actions, n, precision, weights):
-    import torch
-
+    """tests/policy_head_reference.check_forward on n random rows + six edge rows, seed 77, t 3."""
     import marl_sortingenv_amd as M
 
     make = _weights if weights == "test" else _saturating_weights
@@ -90,55 +40,8 @@ def _check_forward(obs_dim, n_actions, n, precision, weights):
     logit_tol = SATURATING_F16X3_LOGIT_TOL if (weights == "saturating" and precision == "f16x3") else LOGIT_TOL
     pol = M.MlpPolicy(obs_dim, n_actions, w, device=0, precision=precision)
     assert pol.precision == precision
-    g = torch.Generator().manual_seed(5)
-    # observations lie in [-1, 1]: the obs clip, and four sort-obs slots are purity - 0.9 (env_super.py:339-359)
-    obs = torch.rand((n, obs_dim), generator=g) * 2.0 - 1.0
-    mask = torch.rand((n, n_actions), generator=g) < 0.6
-    mask[:, 0] = True  # action 0 is always valid in the reference's masks
-    # fixed edge rows: all -1, all 0, all +1 under a mask with only action 0 valid (logp = 0) and an all-valid one
-    edge = torch.tensor([-1.0, 0.0, 1.0]).repeat_interleave(2).unsqueeze(1).expand(6, obs_dim)
-    only0 = torch.zeros((6, n_actions), dtype=torch.bool)
-    only0[:, 0] = True
-    only0[1::2] = True
-    obs, mask, n = torch.cat([obs, edge]), torch.cat([mask, only0]), n + 6
-    single = torch.zeros(n, dtype=torch.bool)
-    single[n - 6::2] = True
-    for use_mask in (True, False):
-        mk = mask if use_mask else None
-        ref_logits, ref_logsm, ref_value = _torch_reference(w_ref, obs.to(w_ref["action_net.bias"].dtype), mk)
-        rt = ref_logits.dtype
-        out = pol.forward(obs.cuda(), None if mk is None else mk.cuda(), seed=77, t=3, want_logits=True)
-        logits = out["logits"].cpu()
-        assert torch.allclose(logits.to(rt), ref_logits, atol=logit_tol, rtol=1e-6), (logits.to(rt) - ref_logits).abs().max()
-        assert torch.allclose(out["value"].cpu().to(rt), ref_value, atol=LOGIT_TOL, rtol=1e-6)
-        act = out["action"].cpu().long()
-        assert bool(((act >= 0) & (act < n_actions)).all())
-        if mk is not None:
-            assert bool(mk.gather(1, act.unsqueeze(1)).all()), "a masked action was sampled"
-        # log-probability of the sampled action
-        assert torch.allclose(out["logp"].cpu().to(rt), ref_logsm.gather(1, act.unsqueeze(1)).squeeze(1), atol=LOGP_TOL)
-        if mk is not None:  # a single valid action: taken with certainty
-            assert bool((act[single] == 0).all()) and float(out["logp"].cpu()[single].abs().max()) <= LOGP_TOL
-        # the sample is the inverse cdf of the engine's stream over the softmax masses in REGISTER order (the MFMA
-        # accumulator's rows of half 0, then half 1: csrc/mse_policy_device.h): recompute it in fp64 from the device's
-        # own logits; a draw that lands within 1e-5 of a boundary may fall on either side
-        order = [a for h in (0, 1) for r in range(16) for a in [(r & 3) + 8 * (r >> 2) + 4 * h] if a < n_actions]
-        assert sorted(order) == list(range(n_actions))
-        p = torch.softmax(logits.double(), dim=1).numpy()[:, order]
-        cdf = np.cumsum(p, axis=1)
-        u_all = ps.uniform24(ps.word(77, np.arange(n), 3))
-        for i in range(n):
-            u = float(u_all[i])
-            k = int(np.searchsorted(cdf[i], u, side="right"))
-            k = order[min(k, n_actions - 1)]
-            if int(act[i]) != k:
-                near = min(abs(u - cdf[i, j]) for j in range(n_actions))
-                assert near < 1e-5, (i, int(act[i]), k, u, cdf[i])
-        # deterministic = argmax of the masked logits
-        det = pol.forward(obs.cuda(), None if mk is None else mk.cuda(), deterministic=True)["action"].cpu().long()
-        top2 = torch.topk(ref_logits, 2, dim=1).values if n_actions > 1 else None
-        clear = (top2[:, 0] - top2[:, 1]) > 1e-4
-        assert bool((det[clear] == ref_logits.argmax(dim=1)[clear]).all())
+    obs, mask, single = forward_inputs(obs_dim, n_actions, n)
+    check_forward(pol, w_ref, obs, mask, single, logit_tol)
 
 
 def test_policy_sampling_frequencies_follow_the_softmax():
