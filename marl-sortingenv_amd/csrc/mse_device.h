@@ -112,7 +112,14 @@ struct Params {
 // ------------------------------------------------------------------------------------------
 struct Pcg {
     uint64_t s_lo, s_hi, i_lo, i_hi;
+    // a stream out of its two state planes, each {lo word, lo >> 32, hi word, hi >> 32}; pack_u64x2 is the way back
+    static __device__ __forceinline__ Pcg from_planes(uint4 state, uint4 inc);
 };
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+__device__ __forceinline__ Pcg Pcg::from_planes(uint4 state, uint4 inc)
+{
+    return Pcg{u64_of(state.x, state.y), u64_of(state.z, state.w), u64_of(inc.x, inc.y), u64_of(inc.z, inc.w)};
+}
 
 // 32x32+64 multiply-add on v_mad_u64_u32 (quarter-rate op: the 128-bit LCG step is built from exactly
 // six of them plus four v_mul_lo_u32; hipcc's own expansion of the 64-bit C expression used 14).
@@ -404,10 +411,7 @@ template <int KIND, bool NOISE>
 __device__ __forceinline__ void unpack_env(Env &e, const EnvRaw &r, const Params &P)
 {
     const uint4 a = r.a, b = r.b, c0 = r.c0, c1 = r.c1, t = r.t, f = r.f, m0 = r.m0, m1 = r.m1, m2 = r.m2;
-    e.rng.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
-    e.rng.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
-    e.rng.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
-    e.rng.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
+    e.rng = Pcg::from_planes(a, b);
     e.acc[0] = __hiloint2double((int)c0.y, (int)c0.x);
     e.acc[1] = __hiloint2double((int)c0.w, (int)c0.z);
     e.acc[2] = __hiloint2double((int)c1.y, (int)c1.x);
@@ -434,20 +438,8 @@ __device__ __forceinline__ void unpack_env(Env &e, const EnvRaw &r, const Params
     e.step = (int)(m2.y >> 16);
     e.episode = m2.z;
     e.press_uint = m2.w;
-    if (NOISE) {
-        const uint4 s = r.ns, q = r.nq;
-        e.noise.s_lo = (uint64_t)s.x | ((uint64_t)s.y << 32);
-        e.noise.s_hi = (uint64_t)s.z | ((uint64_t)s.w << 32);
-        e.noise.i_lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
-        e.noise.i_hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
-    }
-    if (KIND == 1) {
-        const uint4 s = r.ps, q = r.pq;
-        e.press.s_lo = (uint64_t)s.x | ((uint64_t)s.y << 32);
-        e.press.s_hi = (uint64_t)s.z | ((uint64_t)s.w << 32);
-        e.press.i_lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
-        e.press.i_hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
-    }
+    if (NOISE) e.noise = Pcg::from_planes(r.ns, r.nq);
+    if (KIND == 1) e.press = Pcg::from_planes(r.ps, r.pq);
 }
 
 template <int KIND, bool NOISE>
@@ -602,6 +594,34 @@ struct Rng32 {
             }
         }
         return (uint32_t)(m >> 32);
+    }
+    // rng_sorting (seed+2) in its planes: the stream and, in PL_SORTRNG_AUX, the 32-bit buffer {uinteger, has}; the
+    // increment only changes on a seeded reset (k_reset)
+    __device__ __forceinline__ void load_sortrng(const uint4 *planes, const Params &P, long long i)
+    {
+        const uint4 a = planes[(long long)PL_SORTRNG_STATE * P.n_pad + i], b = planes[(long long)PL_SORTRNG_INC * P.n_pad + i];
+        const uint4 x = planes[(long long)PL_SORTRNG_AUX * P.n_pad + i];
+        g = Pcg::from_planes(a, b);
+        uinteger = x.x;
+        has = (int)x.y;
+    }
+    __device__ __forceinline__ void store_sortrng(uint4 *planes, const Params &P, long long i) const
+    {
+        planes[(long long)PL_SORTRNG_STATE * P.n_pad + i] = pack_u64x2(g.s_lo, g.s_hi);
+        planes[(long long)PL_SORTRNG_AUX * P.n_pad + i] = make_uint4(uinteger, (uint32_t)has, 0, 0);
+    }
+    // rng_pressing (seed+3): the stream in its planes; its 32-bit buffer lives in PL_MISC2 and travels with the Env
+    // (load_env / store_env: press_uint, press_has)
+    __device__ __forceinline__ void load_press(const uint4 *planes, const Params &P, long long i, const Env &e)
+    {
+        const uint4 a = planes[(long long)PL_PRESS_STATE * P.n_pad + i], b = planes[(long long)PL_PRESS_INC * P.n_pad + i];
+        g = Pcg::from_planes(a, b);
+        uinteger = e.press_uint;
+        has = e.press_has;
+    }
+    __device__ __forceinline__ void store_press_state(uint4 *planes, const Params &P, long long i) const
+    {
+        planes[(long long)PL_PRESS_STATE * P.n_pad + i] = pack_u64x2(g.s_lo, g.s_hi);
     }
 };
 
@@ -770,6 +790,21 @@ struct RngRing {
 #ifdef MSE_TIMELINE
     Timeline *tl;
 #endif
+    // The consumer's view of env slot el's column, nothing consumed yet.  (The ring starts at LDS address 0:
+    // RingLayout::ring_offset == 0 and ring_kernels_static_lds_free(), checked at mse_create.)
+    __device__ __forceinline__ void open(uint32_t *lring, int el, const uint64_t *jump_table, Env &e)
+    {
+        lane_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(lring + el);
+        jump_tab = jump_table;
+        start = e.rng;
+        p10 = 0;
+        nxt = nxt2 = 0;
+#ifdef MSE_TIMELINE
+        tl = &e.tl;
+#endif
+        f_min = 0xFFFFFFFFu;
+        f_max = 0u;
+    }
     __device__ __forceinline__ uint32_t pos() const { return p10 >> 10; }
     // row (pos & 63) of the column: one v_and_or_b32
     __device__ __forceinline__ uint32_t load(uint32_t q10) const
@@ -1836,6 +1871,25 @@ struct Snap {
     int overflowed;  // check_overflow fired: reward = overflow_termination_penalty
 };
 
+// The small fields of a snapshot in one word, for the waves that pass it through LDS: timer[0] bits 0-7, timer[1] 8-15,
+// st_belt 16-17, st_sort 18-19, mode 20-21, lps 22, done 23, overflowed 24
+__device__ __forceinline__ uint32_t pack_snap_status(const Snap &sn)
+{
+    return (uint32_t)sn.timer[0] | ((uint32_t)sn.timer[1] << 8) | ((uint32_t)sn.st_belt << 16) | ((uint32_t)sn.st_sort << 18) |
+           ((uint32_t)sn.mode << 20) | ((uint32_t)sn.lps << 22) | ((uint32_t)sn.done << 23) | ((uint32_t)sn.overflowed << 24);
+}
+__device__ __forceinline__ void unpack_snap_status(uint32_t pk, Snap &sn)
+{
+    sn.timer[0] = (int)(pk & 0xFFu);
+    sn.timer[1] = (int)((pk >> 8) & 0xFFu);
+    sn.st_belt = (int)((pk >> 16) & 3u);
+    sn.st_sort = (int)((pk >> 18) & 3u);
+    sn.mode = (int)((pk >> 20) & 3u);
+    sn.lps = (int)((pk >> 22) & 1u);
+    sn.done = (int)((pk >> 23) & 1u);
+    sn.overflowed = (int)((pk >> 24) & 1u);
+}
+
 struct PenaltyClass {
     bool any_cat, any_sev, any_mild;
 };
@@ -2188,10 +2242,7 @@ __device__ __forceinline__ void load_gen(Env &e, const uint4 *__restrict__ plane
 {
     const uint4 a = planes[(long long)PL_GEN_STATE * P.n_pad + i], b = planes[(long long)PL_GEN_INC * P.n_pad + i];
     const uint4 x = planes[(long long)PL_GEN_AUX * P.n_pad + i];
-    e.gen.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
-    e.gen.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
-    e.gen.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
-    e.gen.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
+    e.gen = Pcg::from_planes(a, b);
     e.gen_uint = x.x;
     e.gen_has = (int)x.y;
 }

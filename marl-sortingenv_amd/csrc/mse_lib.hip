@@ -472,8 +472,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
         if (live) {
             if (NOISE) { // the parked increment comes back for this step's update_accuracy (RolloutLayout::noise_offset)
                 const uint4 q = lnoise[tid];
-                e.noise.i_lo = (uint64_t)q.x | ((uint64_t)q.y << 32);
-                e.noise.i_hi = (uint64_t)q.z | ((uint64_t)q.w << 32);
+                e.noise.i_lo = u64_of(q.x, q.y);
+                e.noise.i_hi = u64_of(q.z, q.w);
             }
             int a = policy_action<KIND, GEN>(e, cur_mask, tb, flags, pkey, policy_t0 + (uint64_t)s);
             int k[4];
@@ -518,13 +518,17 @@ constexpr int kPoEnvs = 256;                 // envs per workgroup
 constexpr int kPoThreads = 2 * kPoEnvs;      // waves 0-3 dynamics, waves 4-7 observers: a workgroup's waves go round the
                                              // CU's four SIMDs, so wave w and wave w+4 share one - each SIMD gets one
                                              // multiply-heavy dynamics wave and one observer wave
-constexpr int kSnapWordsBase = 13;           // ct[4] cf[4] ce lpa packed action mask
-constexpr int kSnapWordsNoise = kSnapWordsBase + 8; // + accuracy_belt (4 x f64)
+// The snapshot a dynamics wave posts and an observer wave takes, as LDS words [word][kPoEnvs] (one column per env slot):
+// the Snap's counters, its small fields in one word (pack_snap_status), the step's action, the action-mask bits of the
+// state after any auto-reset and, with noise, accuracy_belt from kSnapAcc on: k_rollout_po sends it as 4 x f64 (two
+// words each), k_rollout_ring as 4 x f32
+enum : int { kSnapCt = 0, kSnapCf = 4, kSnapCe = 8, kSnapLpa = 9, kSnapStatus = 10, kSnapAction = 11, kSnapMask = 12, kSnapAcc = 13 };
+constexpr int snap_word_count(bool noise, bool acc64) { return kSnapAcc + (noise ? (acc64 ? 8 : 4) : 0); }
 
 template <int KIND, bool NOISE>
 struct PoLayout {
     static constexpr int D = Dims<KIND>::D, A = Dims<KIND>::A;
-    static constexpr int snap_words = NOISE ? kSnapWordsNoise : kSnapWordsBase;
+    static constexpr int snap_words = snap_word_count(NOISE, /*acc64=*/true);
     static constexpr int obs_bytes = kPoEnvs * D * 4;
     static constexpr int mask_bytes = (kPoEnvs * A + 15) / 16 * 16;
     static constexpr int snap_offset = obs_bytes + mask_bytes;
@@ -598,21 +602,19 @@ __global__ __launch_bounds__(kPoThreads) void k_rollout_po(Params P, uint4 *__re
                 uint32_t *w = lsnap + (s & 1) * SW * kPoEnvs + el;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    w[m * kPoEnvs] = (uint32_t)sn.ct[m];
-                    w[(4 + m) * kPoEnvs] = (uint32_t)sn.cf[m];
+                    w[(kSnapCt + m) * kPoEnvs] = (uint32_t)sn.ct[m];
+                    w[(kSnapCf + m) * kPoEnvs] = (uint32_t)sn.cf[m];
                 }
-                w[8 * kPoEnvs] = (uint32_t)sn.ce;
-                w[9 * kPoEnvs] = (uint32_t)sn.lpa;
-                w[10 * kPoEnvs] = (uint32_t)sn.timer[0] | ((uint32_t)sn.timer[1] << 8) | ((uint32_t)sn.st_belt << 16) |
-                                  ((uint32_t)sn.st_sort << 18) | ((uint32_t)sn.mode << 20) | ((uint32_t)sn.lps << 22) |
-                                  ((uint32_t)sn.done << 23) | ((uint32_t)sn.overflowed << 24);
-                w[11 * kPoEnvs] = (uint32_t)a;
-                w[12 * kPoEnvs] = mbits;
+                w[kSnapCe * kPoEnvs] = (uint32_t)sn.ce;
+                w[kSnapLpa * kPoEnvs] = (uint32_t)sn.lpa;
+                w[kSnapStatus * kPoEnvs] = pack_snap_status(sn);
+                w[kSnapAction * kPoEnvs] = (uint32_t)a;
+                w[kSnapMask * kPoEnvs] = mbits;
                 if (NOISE) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m) {
-                        w[(13 + 2 * m) * kPoEnvs] = (uint32_t)__double2loint(sn.acc[m]);
-                        w[(14 + 2 * m) * kPoEnvs] = (uint32_t)__double2hiint(sn.acc[m]);
+                        w[(kSnapAcc + 2 * m) * kPoEnvs] = (uint32_t)__double2loint(sn.acc[m]);
+                        w[(kSnapAcc + 2 * m + 1) * kPoEnvs] = (uint32_t)__double2hiint(sn.acc[m]);
                     }
                 }
             }
@@ -636,27 +638,20 @@ __global__ __launch_bounds__(kPoThreads) void k_rollout_po(Params P, uint4 *__re
             Snap sn;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                sn.ct[m] = (int)w[m * kPoEnvs];
-                sn.cf[m] = (int)w[(4 + m) * kPoEnvs];
+                sn.ct[m] = (int)w[(kSnapCt + m) * kPoEnvs];
+                sn.cf[m] = (int)w[(kSnapCf + m) * kPoEnvs];
             }
-            sn.ce = (int)w[8 * kPoEnvs];
-            sn.lpa = (int)w[9 * kPoEnvs];
-            const uint32_t pk = w[10 * kPoEnvs];
-            const int a = (int)w[11 * kPoEnvs];
-            const uint32_t mbits = w[12 * kPoEnvs];
+            sn.ce = (int)w[kSnapCe * kPoEnvs];
+            sn.lpa = (int)w[kSnapLpa * kPoEnvs];
+            const uint32_t pk = w[kSnapStatus * kPoEnvs];
+            const int a = (int)w[kSnapAction * kPoEnvs];
+            const uint32_t mbits = w[kSnapMask * kPoEnvs];
             if (NOISE) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
-                    sn.acc[m] = __hiloint2double((int)w[(14 + 2 * m) * kPoEnvs], (int)w[(13 + 2 * m) * kPoEnvs]);
+                    sn.acc[m] = __hiloint2double((int)w[(kSnapAcc + 2 * m + 1) * kPoEnvs], (int)w[(kSnapAcc + 2 * m) * kPoEnvs]);
             }
-            sn.timer[0] = (int)(pk & 0xFFu);
-            sn.timer[1] = (int)((pk >> 8) & 0xFFu);
-            sn.st_belt = (int)((pk >> 16) & 3u);
-            sn.st_sort = (int)((pk >> 18) & 3u);
-            sn.mode = (int)((pk >> 20) & 3u);
-            sn.lps = (int)((pk >> 22) & 1u);
-            sn.done = (int)((pk >> 23) & 1u);
-            sn.overflowed = (int)((pk >> 24) & 1u);
+            unpack_snap_status(pk, sn);
             if (live) { // the snapshot slots of padding lanes are never written
                 int k[4];
                 StepResult r = env_observe<KIND, NOISE>(sn, P, tb, k, o);
@@ -699,7 +694,7 @@ constexpr int kRingThreads = 3 * kPoEnvs;
 template <int KIND, bool NOISE>
 struct RingLayout {
     static constexpr int D = Dims<KIND>::D, A = Dims<KIND>::A;
-    static constexpr int snap_words = kSnapWordsBase + (NOISE ? 4 : 0); // accuracy_belt travels as 4 x f32
+    static constexpr int snap_words = snap_word_count(NOISE, /*acc64=*/false);
     static constexpr int ring_offset = 0;                               // 64 KiB aligned: RngRing::load masks the row in
     static constexpr int ring_bytes = kRingDepth * kPoEnvs * 4;
     static_assert(ring_bytes == 65536, "RngRing::load assumes 64 rows of 1 KiB");
@@ -722,14 +717,7 @@ __device__ __forceinline__ void rng_server_role(const Params &P, uint4 *__restri
                                                 bool live, int k_steps, uint32_t *lring, uint32_t *lpos, int el, bool two_halves,
                                                 int barriers_before_init = 0)
 {
-    Pcg g;
-    {
-        const uint4 a = planes[PL_RNG_STATE * P.n_pad + i], b = planes[PL_RNG_INC * P.n_pad + i];
-        g.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
-        g.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
-        g.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
-        g.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
-    }
+    Pcg g = Pcg::from_planes(planes[PL_RNG_STATE * P.n_pad + i], planes[PL_RNG_INC * P.n_pad + i]);
     const uint32_t ring_lane_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(lring + el);
     uint64_t c2_lo, c2_hi; // (M + 1) inc: the increment of the double step s_{n+2} = M^2 s_n + (M + 1) inc
     mul128(0x4385DF649FCCF646ull, 0x2360ED051FC65DA4ull, g.i_lo, g.i_hi, c2_lo, c2_hi);
@@ -910,17 +898,7 @@ __global__ __launch_bounds__(kRingThreads) void k_rollout_ring(Params P, uint4 *
         }
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): no load is outstanding inside the step loop
         RngRing rng;
-        rng.lane_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(lring + el);
-        // (the ring starts at LDS address 0: RingLayout::ring_offset == 0 and ring_kernels_static_lds_free(), checked at mse_create)
-        rng.jump_tab = tb.jump;
-        rng.start = e.rng;
-        rng.p10 = 0;
-        rng.nxt = rng.nxt2 = 0;
-#ifdef MSE_TIMELINE
-        rng.tl = &e.tl;
-#endif
-        rng.f_min = 0xFFFFFFFFu;
-        rng.f_max = 0u;
+        rng.open(lring, el, tb.jump, e);
         uint32_t cur_mask = action_mask_bits<KIND>(e, P);
         const uint32_t pkey = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + i));
         lpos[el] = 0;
@@ -941,18 +919,16 @@ __global__ __launch_bounds__(kRingThreads) void k_rollout_ring(Params P, uint4 *
                 uint32_t *w = lsnap + (s & 1) * SW * kPoEnvs + el;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
-                    w[m * kPoEnvs] = (uint32_t)sn.ct[m];
-                    w[(4 + m) * kPoEnvs] = (uint32_t)sn.cf[m];
+                    w[(kSnapCt + m) * kPoEnvs] = (uint32_t)sn.ct[m];
+                    w[(kSnapCf + m) * kPoEnvs] = (uint32_t)sn.cf[m];
                 }
-                w[8 * kPoEnvs] = (uint32_t)sn.ce;
-                w[9 * kPoEnvs] = (uint32_t)sn.lpa;
-                w[10 * kPoEnvs] = (uint32_t)sn.timer[0] | ((uint32_t)sn.timer[1] << 8) | ((uint32_t)sn.st_belt << 16) |
-                                  ((uint32_t)sn.st_sort << 18) | ((uint32_t)sn.mode << 20) | ((uint32_t)sn.lps << 22) |
-                                  ((uint32_t)sn.done << 23) | ((uint32_t)sn.overflowed << 24);
-                w[11 * kPoEnvs] = (uint32_t)a;
+                w[kSnapCe * kPoEnvs] = (uint32_t)sn.ce;
+                w[kSnapLpa * kPoEnvs] = (uint32_t)sn.lpa;
+                w[kSnapStatus * kPoEnvs] = pack_snap_status(sn);
+                w[kSnapAction * kPoEnvs] = (uint32_t)a;
                 if (NOISE) {
 #pragma unroll
-                    for (int m = 0; m < 4; ++m) w[(13 + m) * kPoEnvs] = __float_as_uint((float)sn.acc[m]);
+                    for (int m = 0; m < 4; ++m) w[(kSnapAcc + m) * kPoEnvs] = __float_as_uint((float)sn.acc[m]);
                 }
                 if (__builtin_expect(sn.done != 0, 0)) { // all envs of a batch finish together: rare, wave-uniform
                     int kdummy[4];
@@ -960,7 +936,7 @@ __global__ __launch_bounds__(kRingThreads) void k_rollout_ring(Params P, uint4 *
                 }
                 const uint32_t mbits = action_mask_bits<KIND>(e, P); // what the next action sees (after auto-reset)
                 cur_mask = mbits;
-                w[12 * kPoEnvs] = mbits;
+                w[kSnapMask * kPoEnvs] = mbits;
                 lpos[el] = rng.pos(); // r_s for the RNG lane of this env
             }
             MSE_TLB(e.tl, 5);
@@ -1002,26 +978,19 @@ __global__ __launch_bounds__(kRingThreads) void k_rollout_ring(Params P, uint4 *
             Snap sn;
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
-                sn.ct[m] = (int)w[m * kPoEnvs];
-                sn.cf[m] = (int)w[(4 + m) * kPoEnvs];
+                sn.ct[m] = (int)w[(kSnapCt + m) * kPoEnvs];
+                sn.cf[m] = (int)w[(kSnapCf + m) * kPoEnvs];
             }
-            sn.ce = (int)w[8 * kPoEnvs];
-            sn.lpa = (int)w[9 * kPoEnvs];
-            const uint32_t pk = w[10 * kPoEnvs];
-            const int a = (int)w[11 * kPoEnvs];
-            const uint32_t mbits = w[12 * kPoEnvs];
+            sn.ce = (int)w[kSnapCe * kPoEnvs];
+            sn.lpa = (int)w[kSnapLpa * kPoEnvs];
+            const uint32_t pk = w[kSnapStatus * kPoEnvs];
+            const int a = (int)w[kSnapAction * kPoEnvs];
+            const uint32_t mbits = w[kSnapMask * kPoEnvs];
             if (NOISE) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) sn.acc[m] = (double)__uint_as_float(w[(13 + m) * kPoEnvs]);
+                for (int m = 0; m < 4; ++m) sn.acc[m] = (double)__uint_as_float(w[(kSnapAcc + m) * kPoEnvs]);
             }
-            sn.timer[0] = (int)(pk & 0xFFu);
-            sn.timer[1] = (int)((pk >> 8) & 0xFFu);
-            sn.st_belt = (int)((pk >> 16) & 3u);
-            sn.st_sort = (int)((pk >> 18) & 3u);
-            sn.mode = (int)((pk >> 20) & 3u);
-            sn.lps = (int)((pk >> 22) & 1u);
-            sn.done = (int)((pk >> 23) & 1u);
-            sn.overflowed = (int)((pk >> 24) & 1u);
+            unpack_snap_status(pk, sn);
             int k[4];
 #ifdef MSE_ABL_NOOBS // (ablation timing builds only: rows of zeros are staged and stored)
             StepResult r{0.0, sn.done, 0.0, 0.0};
@@ -1159,6 +1128,32 @@ __device__ __forceinline__ void wave_store_rows_mask(uint8_t *ltile, uint32_t lr
     __builtin_amdgcn_wave_barrier();
 }
 
+// The two-tile MFMA conventions of the policy waves.  Lane l = 32 h + col serves column col of both tiles; with one env
+// per lane, env l is column l & 31 of tile l >> 5.
+// legal_of: an env's action-mask bits -> bit r: the action of accumulator register r of half h is legal
+__device__ __forceinline__ uint32_t legal_of(uint32_t env_bits, int h)
+{
+    const uint32_t t = env_bits >> (4 * h);
+    return (t & 0xFu) | ((t >> 4) & 0xF0u) | ((t >> 8) & 0xF00u) | ((t >> 12) & 0xF000u);
+}
+// operands_of: swap(o[2q], o[2q+1]) = {tile 0's k-step q operand, tile 1's}: lanes 32-63 of tile 0 get the odd entries of
+// the envs in lanes 0-31, lanes 0-31 of tile 1 the even entries of the envs in lanes 32-63
+__device__ __forceinline__ void operands_of(const float *ob, float (*x)[16])
+{
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(ob[2 * q]), __float_as_uint(ob[2 * q + 1]), false, false);
+        x[0][q] = __uint_as_float(r[0]);
+        x[1][q] = __uint_as_float(r[1]);
+    }
+}
+// tile_pick: this lane's env's result out of the two tiles' (both are valid in both halves; TILES = 1: tile 0's)
+template <int TILES, class T>
+__device__ __forceinline__ T tile_pick(int h, T a0, T a1)
+{
+    return (TILES == 2 && h) ? a1 : a0;
+}
+
 // TILES = 2: a wave owns 64 envs, one per lane, as two MFMA tiles (lanes 0-31 / 32-63).
 // TILES = 1: a wave owns 32 envs in lanes 0-31 (lanes 32-63 only carry the other k-half of the MFMA operands): twice
 //            the waves for the same batch - the shape for batches that would otherwise leave one wave per SIMD, where
@@ -1234,22 +1229,6 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
     const uint32_t key0 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + col));
     const uint32_t key1 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
 
-    // action_masks() bits of env -> bit r: the action of accumulator register r of half h is legal
-    auto legal_of = [&](uint32_t env_bits) -> uint32_t {
-        const uint32_t t = env_bits >> (4 * h);
-        return (t & 0xFu) | ((t >> 4) & 0xF0u) | ((t >> 8) & 0xF00u) | ((t >> 12) & 0xF000u);
-    };
-    // swap(o[2q], o[2q+1]) = {tile 0's k-step q operand, tile 1's}: lanes 32-63 of tile 0 get the odd entries of the
-    // envs in lanes 0-31, lanes 0-31 of tile 1 the even entries of the envs in lanes 32-63
-    auto operands_of = [&](const float *ob, float (*x)[16]) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(ob[2 * q]), __float_as_uint(ob[2 * q + 1]), false, false);
-            x[0][q] = __uint_as_float(r[0]);
-            x[1][q] = __uint_as_float(r[1]);
-        }
-    };
-
     const uint32_t lrow_obs = lds_row_address(reinterpret_cast<float *>(lwave) + src_lane * D);
     const uint32_t lrow_mask = lds_row_address(lwave + src_lane * A);
     int last_done = 0;
@@ -1274,17 +1253,12 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
         uint32_t mb0, mb1;
         msep::both_halves_u32((flags & MSE_STEP_UNMASKED) ? ((1u << A) - 1u) : mbits, mb0, mb1);
         const uint64_t t = policy_t0 + (uint64_t)s;
-        const uint32_t legal[2] = {legal_of(mb0), legal_of(mb1)};
+        const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
         const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
         msep::TileOut p[2];
         msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, A, legal, deterministic != 0, words, nullptr, p);
-        int a = p[0].action;
-        float logp = p[0].logp, value = p[0].value;
-        if (TILES == 2) { // lane l is env l: tile l >> 5, column l & 31 (results are valid in both halves)
-            a = h ? p[1].action : a;
-            logp = h ? p[1].logp : logp;
-            value = h ? p[1].value : value;
-        }
+        const int a = tile_pick<TILES>(h, p[0].action, p[1].action);
+        const float logp = tile_pick<TILES>(h, p[0].logp, p[1].logp), value = tile_pick<TILES>(h, p[0].value, p[1].value);
         MSE_TLB(ptl, 1); // policy forward
         // Phase priorities: the two waves of a SIMD fall into step with each other (both in the policy, both in the
         // dynamics) and then compete for the same pipe; letting one phase win the issue arbitration pulls them apart so
@@ -1307,7 +1281,7 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
             operands_of(so, sx);
             int sa[2];
             msep::actor_argmax2_tiles<F16X3, TILES>(wl_sort, lane, sx, sa);
-            sm = (TILES == 2 && h) ? sa[1] : sa[0];
+            sm = tile_pick<TILES>(h, sa[0], sa[1]);
         }
         MSE_TLB(ptl, 2); // sorting agent
         // ---- the env transition under that action
@@ -1336,7 +1310,7 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
         float x[2][16], v[2];
         operands_of(o, x);
         msep::value_tiles<F16X3, TILES>(wl, lane, x, v);
-        if (live) last_value_out[i] = (TILES == 2 && h) ? v[1] : v[0];
+        if (live) last_value_out[i] = tile_pick<TILES>(h, v[0], v[1]);
     }
     if (live && last_done_out != nullptr) last_done_out[i] = (uint8_t)last_done;
     if (live) store_env<KIND, NOISE>(e, planes, P, i, false);
@@ -1484,23 +1458,8 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
         uint32_t mbits = action_mask_bits<KIND>(e, P);
         const uint32_t key0 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + col));
         const uint32_t key1 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
-        auto legal_of = [&](uint32_t env_bits) -> uint32_t { // as in k_rollout_policy
-            const uint32_t t = env_bits >> (4 * h);
-            return (t & 0xFu) | ((t >> 4) & 0xF0u) | ((t >> 8) & 0xF00u) | ((t >> 12) & 0xF000u);
-        };
         RngRing ring;
-        if (RING) { // as the dynamics role of k_rollout_ring
-            ring.lane_addr = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)(lring + el);
-            ring.jump_tab = tb.jump;
-            ring.start = e.rng;
-            ring.p10 = 0;
-            ring.nxt = ring.nxt2 = 0;
-            ring.f_min = 0xFFFFFFFFu;
-            ring.f_max = 0u;
-#ifdef MSE_TIMELINE
-            ring.tl = &e.tl;
-#endif
-        }
+        if (RING) ring.open(lring, el, tb.jump, e);
         const uint32_t lrow = lds_row_address(ltile + lane * D);
         // `taken` is read a phase early (its LDS round trip rides under the observation's arithmetic) and again only if
         // the critic wave had not got to the tile by then, which a whole actor network + env transition makes unlikely
@@ -1552,22 +1511,17 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
             lds_barrier_all();
             MSE_TLB(e.tl, 6); // barrier wait
             float x[2][16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(o[2 * q]), __float_as_uint(o[2 * q + 1]), false, false);
-                x[0][q] = __uint_as_float(r[0]);
-                x[1][q] = __uint_as_float(r[1]);
-            }
+            operands_of(o, x);
             uint32_t mb0, mb1;
             msep::both_halves_u32((flags & MSE_STEP_UNMASKED) ? ((1u << A) - 1u) : mbits, mb0, mb1);
             const uint64_t t = policy_t0 + (uint64_t)s;
-            const uint32_t legal[2] = {legal_of(mb0), legal_of(mb1)};
+            const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
             const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
             msep::TileOut p[2];
             if (kPipelinedActor) msep::actor_tiles_pipelined<NR>(wl, lane, x, A, legal, deterministic != 0, words, p);
             else msep::actor_tiles<NR, true, 2>(wl, lane, x, A, legal, deterministic != 0, words, p);
-            const int a = h ? p[1].action : p[0].action; // lane l is env l: tile l >> 5, column l & 31
-            const float logp = h ? p[1].logp : p[0].logp;
+            const int a = tile_pick<2>(h, p[0].action, p[1].action);
+            const float logp = tile_pick<2>(h, p[0].logp, p[1].logp);
             MSE_TLB(e.tl, 0); // actor network and sampling
             Snap sn;
             note.begin_step();
@@ -1686,7 +1640,7 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
         MSE_TLB(ctl, 2); // row stores
         float v[2];
         msep::value_tiles<true, 2>(wl, lane, x, v);
-        if (live && value_out != nullptr) __builtin_nontemporal_store(h ? v[1] : v[0], &value_out[(long long)s * P.n + i]);
+        if (live && value_out != nullptr) __builtin_nontemporal_store(tile_pick<2>(h, v[0], v[1]), &value_out[(long long)s * P.n + i]);
         MSE_TLB(ctl, 3); // value network
     }
 #ifdef MSE_TIMELINE
@@ -1703,7 +1657,7 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
         }
         if (last_value_out != nullptr) {
             msep::value_tiles<true, 2>(wl, lane, x, v);
-            if (live) last_value_out[i] = h ? v[1] : v[0];
+            if (live) last_value_out[i] = tile_pick<2>(h, v[0], v[1]);
         }
     }
 }
@@ -1765,25 +1719,8 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
     Env e;
     load_env<3, NOISE>(e, planes, P, i);
     Rng32 srt, prs; // rng_sorting (seed+2), rng_pressing (seed+3): the fallback draws (k_model_actions)
-    if (!SORT_AG && wave_active) {
-        const uint4 a = planes[(long long)PL_SORTRNG_STATE * P.n_pad + i], b = planes[(long long)PL_SORTRNG_INC * P.n_pad + i];
-        const uint4 x = planes[(long long)PL_SORTRNG_AUX * P.n_pad + i];
-        srt.g.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
-        srt.g.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
-        srt.g.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
-        srt.g.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
-        srt.uinteger = x.x;
-        srt.has = (int)x.y;
-    }
-    if (!PRESS_AG && wave_active) { // the 32-bit buffer came with PL_MISC2 (load_env)
-        const uint4 a = planes[(long long)PL_PRESS_STATE * P.n_pad + i], b = planes[(long long)PL_PRESS_INC * P.n_pad + i];
-        prs.g.s_lo = (uint64_t)a.x | ((uint64_t)a.y << 32);
-        prs.g.s_hi = (uint64_t)a.z | ((uint64_t)a.w << 32);
-        prs.g.i_lo = (uint64_t)b.x | ((uint64_t)b.y << 32);
-        prs.g.i_hi = (uint64_t)b.z | ((uint64_t)b.w << 32);
-        prs.uinteger = e.press_uint;
-        prs.has = e.press_has;
-    }
+    if (!SORT_AG && wave_active) srt.load_sortrng(planes, P, i);
+    if (!PRESS_AG && wave_active) prs.load_press(planes, P, i, e);
     __syncthreads();
     if (!wave_active) return;
     __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
@@ -1796,21 +1733,6 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
     const int h = lane >> 5;
     int kcur[4]; // container purities of the current state (the sorting view needs them)
     container_purity_k(e, kcur);
-
-    // press_action_masks() bits of env -> bit r: the action of accumulator register r of half h is legal
-    auto legal_of = [&](uint32_t env_bits) -> uint32_t {
-        const uint32_t t = env_bits >> (4 * h);
-        return (t & 0xFu) | ((t >> 4) & 0xF0u) | ((t >> 8) & 0xF00u) | ((t >> 12) & 0xF000u);
-    };
-    // swap(o[2q], o[2q+1]) = {tile 0's k-step q operand, tile 1's} (k_rollout_policy)
-    auto operands_of = [&](const float *ob, float (*x)[16]) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(ob[2 * q]), __float_as_uint(ob[2 * q + 1]), false, false);
-            x[0][q] = __uint_as_float(r[0]);
-            x[1][q] = __uint_as_float(r[1]);
-        }
-    };
 
     float *ltile = reinterpret_cast<float *>(lwave);
     const uint32_t lrow_obs = lds_row_address(ltile + src_lane * D);
@@ -1840,7 +1762,7 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
             operands_of(so, sx);
             int sa[2];
             msep::actor_argmax2_tiles<true, TILES>(wl_sort, lane, sx, sa);
-            sm = (TILES == 2 && h) ? sa[1] : sa[0];
+            sm = tile_pick<TILES>(h, sa[0], sa[1]);
         } else {
             sm = (int)srt.lemire(2u); // rng_sorting.choice([0, 1])
         }
@@ -1851,11 +1773,11 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
             operands_of(po, px);
             uint32_t pb0, pb1;
             msep::both_halves_u32(agent_masked ? pbits : 0x7FFu, pb0, pb1);
-            const uint32_t legal[2] = {legal_of(pb0), legal_of(pb1)};
+            const uint32_t legal[2] = {legal_of(pb0, h), legal_of(pb1, h)};
             const uint32_t words[2] = {0u, 0u};
             msep::TileOut p[2];
             msep::actor_tiles<NR, true, TILES>(wl_press, lane, px, 11, legal, true, words, p);
-            pa = (TILES == 2 && h) ? p[1].action : p[0].action;
+            pa = tile_pick<TILES>(h, p[0].action, p[1].action);
         } else if (unmasked_draw) {
             pa = (int)prs.lemire(11u); // rng_pressing.choice(11)
         } else {
@@ -1884,11 +1806,8 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
         e.press_has = prs.has;
     }
     if (live) store_env<3, NOISE>(e, planes, P, i, false);
-    if (live && !SORT_AG) {
-        planes[(long long)PL_SORTRNG_STATE * P.n_pad + i] = pack_u64x2(srt.g.s_lo, srt.g.s_hi);
-        planes[(long long)PL_SORTRNG_AUX * P.n_pad + i] = make_uint4(srt.uinteger, (uint32_t)srt.has, 0, 0);
-    }
-    if (live && !PRESS_AG) planes[(long long)PL_PRESS_STATE * P.n_pad + i] = pack_u64x2(prs.g.s_lo, prs.g.s_hi);
+    if (live && !SORT_AG) srt.store_sortrng(planes, P, i);
+    if (live && !PRESS_AG) prs.store_press_state(planes, P, i);
     if (P.track_bales && live) {
 #pragma unroll
         for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
@@ -2073,9 +1992,8 @@ __global__ __launch_bounds__(kBlock) void k_model_actions(Params P, uint4 *__res
         press_action = select_kth_bit(bits, (int)prs.lemire((uint32_t)__popc(bits)));
     }
     action_out[i] = P.env_kind == 1 ? sort_mode : (P.env_kind == 2 ? press_action : sort_mode * 11 + press_action);
-    planes[(long long)PL_SORTRNG_STATE * P.n_pad + i] = pack_u64x2(srt.g.s_lo, srt.g.s_hi);
-    planes[(long long)PL_SORTRNG_AUX * P.n_pad + i] = make_uint4(srt.uinteger, (uint32_t)srt.has, 0, 0);
-    planes[(long long)PL_PRESS_STATE * P.n_pad + i] = pack_u64x2(prs.g.s_lo, prs.g.s_hi);
+    srt.store_sortrng(planes, P, i);
+    prs.store_press_state(planes, P, i);
     // rng_pressing's 32-bit buffer lives in PL_MISC2 {.w = uinteger, flag bit in .x}
     uint4 m2 = planes[(long long)PL_MISC2 * P.n_pad + i];
     m2.w = prs.uinteger;
