@@ -10,7 +10,7 @@
 // Instruction-count discipline (the kernel is VALU-issue bound at one wave per SIMD, see
 // DESIGN.md "Kernel"): every quotient of small integers that the reference evaluates per step
 // (levels/700, timers/12, belt shares, purity differences ...) is a lookup in tables that the host
-// fills with the reference's literal fp64 expression (mse_lib.hip build_tables), staged in LDS;
+// fills with the reference's literal fp64 expression (mse_tables.h compile_config), staged in LDS;
 // the stage vectors are carried as seasonal-pattern ids; the sort_material draw decides
 // Generator.choice with integer compares on the PCG64 output and falls back to the literal fp64
 // cdf only within a hair of a tie.
@@ -20,11 +20,11 @@
 #include <stdint.h>
 
 #include "mse_exact.h"
+#include "mse_params.h" // Params and the table image's shape, shared with the host (mse_tables.h)
 #include "mse_policy_stream.h"
 
 namespace mse {
 
-constexpr int kBlock = 256;             // threads per workgroup = 4 wavefronts of 64
 constexpr int kGeneratorPeriod = 20;    // SeasonalInputGenerator default steps_per_pattern
                                         // (utils/input_generator.py:15; reset() uses it: env_super.py:375)
 
@@ -57,55 +57,6 @@ enum Plane : int {
 constexpr uint32_t FL_LAST_PRESS_STARTED = 1u;
 constexpr uint32_t FL_GEN_FIRST_IS_2 = 2u;
 constexpr uint32_t FL_PRESS_HAS_U32 = 4u;
-
-constexpr int kPdiffStride = 102; // purity hundredths 0..100, [101] = empty container
-// per-stage-id record in the LDS table image (12 words, 16-byte aligned):
-//   [0] packed counts  [1] belt_occupancy f32  [2] sorting_rules() mode  [3] pad
-//   [4..7] belt proportions f32   [8..11] sorting[m]/stage_capacity f32
-constexpr int kPatStride = 12;
-
-// fp64 constants kept in the LDS table image (Tables::cst)
-enum Cst : int { CST_PEN_CAT = 0, CST_PEN_SEV, CST_PEN_MILD, CST_MAX_STATE, CST_OVERFLOW_PEN, CST_REM_THR, CST_BOOST,
-                 CST_NOISE, CST_BASE_ACC0, CST_BASE_ACC1, CST_BASE_ACC2, CST_BASE_ACC3, CST_COUNT };
-
-struct Params {
-    long long n;            // envs in this handle
-    long long n_pad;        // plane stride (multiple of kBlock)
-    long long index_offset; // global index of env 0 (sharded runs)
-    int env_kind, max_steps, auto_reset, track_bales;
-    int balesize, capacity, stage_capacity, batch;
-    int press_time[2];
-    int press_time0, press_time1; // the same as two scalars: selected per lane with v_cndmask, never indexed
-    float inv_balesize;           // 1.0f / bale_standard_size (quotient estimate, fixed up exactly)
-    double max_state_reward;      // used every step: stays a kernel argument (SGPR pair)
-    double sr_den, sr_inv;        // 5 * capacity and its reciprocal (state_ratio)
-    int sr_exact_max;             // state_ratio's reciprocal form is proven for 0 <= total_level <= this
-    // stage vectors are one of three words: id 0 = empty (after reset), 1 / 2 = seasonal pattern
-    uint32_t pat_word[3];   // packed u8x4 counts A..D (load/store conversion)
-    uint32_t pat_word1, pat_word2; // the same as two scalars: a per-lane choice between them is two v_cndmask on
-                                   // SGPRs (indexing the array per lane would be a global load)
-    int thr_sev, thr_mild;  // levels above these have fill_ratio > 0.95 / > 0.90 (literal fp64 scan on the host)
-    int sev_negative, mild_negative; // overflow_penalty_severe / _mild < 0 (then that bracket returns early)
-    int k_thr[4];           // hundredths of python round(quality_threshold, 2): purity of an empty container
-    // offsets (in 4-byte words) into the table image; see build_tables
-    int off_lvl, off_pdiff, off_timer0, off_timer1, off_tanh, off_eff, off_pat, off_acc, off_bonus, off_ptime, off_cst, off_jump, off_back, table_words;
-    uint32_t qi_down[4]; // bit q set: int((q / 100.0) * 100.0) == q - 1  (press_bale's stored quality)
-    int rem_thr_units;   // floor(bale_standard_size * bale_remainder_threshold)
-    int ring_worst; // most sort_material draws one step can make with this config (k_rollout_ring flow control)
-    // the LCG's jump FORWARD by ring_worst steps, s' = A s + G inc (A_lo, A_hi, G_lo, G_hi): the two halves of the
-    // ring's priming are that far apart (k_rollout_ring); kernel arguments because the observer lanes need them
-    // before the table image is in LDS
-    uint64_t ring_fwd[4];
-    // General generator mode (utils/input_generator.py:46-61 with a floor() remainder, e.g. input_batch_size 90): the stage
-    // vectors are carried as their packed counts instead of pattern ids, the generator's private stream runs on the
-    // device (remainder draws + the shuffle's draws), and only the one-lane kernels serve the handle.
-    int gen_mode;
-    int gen_rem[3];            // units left after the floor()s, per pattern key (index 1 | 2)
-    uint32_t occ_nonempty;     // f32 bits of clip(float(round(batch / 100, 2))): occupancy of a stage that holds a batch
-    int off_gprop, off_gfrac;  // tables by count: clip(float(k / batch)), clip(float(k / stage_capacity)), k = 0..255
-    double acc_floor[4]; // lowest accuracy_belt[m] the config can produce: clip(baseline [+ boost] - noise).  ring_worst
-                         // is derived from it, so mse_set_state counts anything below as an error (mse_error_count)
-};
 
 // ------------------------------------------------------------------------------------------
 // numpy PCG64 (pcg64.h): 128-bit LCG, XSL-RR output of the NEW state
@@ -715,10 +666,9 @@ __device__ __forceinline__ int choice4_literal(uint32_t C, uint64_t r64)
 // where sort_material's PCG64 outputs come from
 // ------------------------------------------------------------------------------------------
 // 128-bit LCG jump-ahead: n steps of s' = M s + inc are s_n = A_n s + G_n inc with A_n = M^n and
-// G_n = 1 + M + ... + M^(n-1); the host tabulates (A, G) for n = 2^j (build_tables) and a jump multiplies
+// G_n = 1 + M + ... + M^(n-1); the host tabulates (A, G) for n = 2^j (mse_tables.h) and a jump multiplies
 // the set bits of n together.  Used only off the hot path (final stream state of a ring rollout, and the
 // full 64-bit output of a draw that needs the literal cdf).
-constexpr int kJumpBits = 24;
 __device__ __forceinline__ void mul128(uint64_t a_lo, uint64_t a_hi, uint64_t b_lo, uint64_t b_hi, uint64_t &r_lo,
                                        uint64_t &r_hi)
 {
@@ -744,7 +694,6 @@ __device__ __forceinline__ void pcg_jump(Pcg &g, uint32_t n, const uint64_t *jum
 // one table entry per d = 0..32, so going back d <= 32 steps is two 128-bit multiplies whatever d is.  The RNG waves
 // of k_rollout_ring end a launch at most 64 (usually < `worst`) outputs ahead of what the env consumed and hand the
 // stream back this way.
-constexpr int kRingBackSteps = 33;
 // s' = A s + G inc (mod 2^128): any number of LCG steps, forward or back, in two 128-bit multiplies
 __device__ __forceinline__ void pcg_affine(Pcg &g, uint64_t a_lo, uint64_t a_hi, uint64_t g_lo, uint64_t g_hi)
 {

@@ -18,9 +18,8 @@
 #include <string>
 
 #include "mse.h"
+#include "mse_host.h"
 #include "mse_episode_math.h"
-
-int mse_internal_fail(int status, const char *msg); // mse_lib.hip: sets mse_last_error()
 
 namespace {
 
@@ -117,14 +116,6 @@ __global__ __launch_bounds__(kLanes) void k_episode_summary(long long n, int slo
     tq.sum_return = q; // thread 0 has read the partials of pass 1 before the barrier above
     const Totals gq = group_reduce(tq);
     if (threadIdx.x == 0) summary_finish(g, mean, gq.sum_return, summary);
-}
-
-int cu_count()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return cus;
 }
 
 // the argument rules of both scan entry points; nullptr if they hold

@@ -1,7 +1,7 @@
 // mse_exact.h -- cheap forms of two quotients the step evaluates in fp64, each proven equal to the reference's literal
 // expression over the range where it is used.  Shared by the kernels (mse_device.h), the host-side
-// proof at mse_create (mse_lib.hip) and the exhaustive CPU proof (tests/test_exact_int_forms.py, which compiles this
-// header on the host).
+// proof at mse_create (compile_config, mse_tables.h) and the exhaustive CPU proof (tests/test_exact_int_forms.py,
+// which compiles this header on the host).
 //
 //   purity  round(tru / total, 2) in hundredths = rint(fl(fl(tru / total) * 100)): exact integer rounding of
 //           100 tru / total from an f32 reciprocal estimate; exact ties and totals above kPurityExactMax take the

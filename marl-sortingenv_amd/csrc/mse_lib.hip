@@ -4,8 +4,10 @@
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared -Iinclude \
 //         marl-sortingenv_amd/csrc/mse_lib.hip -o marl-sortingenv_amd/libmse_hip.so
 #include "mse_device.h"
+#include "mse_host.h"
 #include "mse_plan.h"
 #include "mse_policy_device.h"
+#include "mse_tables.h"
 
 #include "mse.h"
 
@@ -49,7 +51,7 @@ __device__ __forceinline__ void lds_barrier_all()
 
 // Table image -> LDS in 16-byte pieces, every load of a thread issued before its first LDS write (a word-by-word
 // loop is one global round trip per iteration: 12 of them with 256 threads).  issue() / commit() are separate so a
-// kernel can put other loads in flight between them.  `words` is a multiple of 4 (build_tables pads).
+// kernel can put other loads in flight between them.  `words` is a multiple of 4 (compile_config pads).
 template <int THREADS, int U>
 struct TableCopy {
     uint4 x[U];
@@ -2153,7 +2155,7 @@ struct mse_env {
     Params P;
     mse_config cfg;
     uint4 *planes;
-    uint32_t *tables;            // device image of the lookup tables (build_tables)
+    uint32_t *tables;            // device image of the lookup tables (compile_config)
     unsigned long long *err_count;
     int device;
     bool seeded;
@@ -2184,207 +2186,6 @@ static int fail(int status, const std::string &msg)
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-
-// ------------------------------------------------------------------------------------------
-// Lookup tables and per-pattern constants.  Every entry is the reference's own fp64 expression
-// evaluated on the host for each possible integer argument (this translation unit is compiled
-// with -ffp-contract=off), so a device lookup returns exactly what the reference computes.
-// ------------------------------------------------------------------------------------------
-static inline double host_round2(double x) { return std::nearbyint(x * 100.0) / 100.0; } // round(np.float64, 2)
-// Python's round(float, 2): correctly rounded on the exact binary value, ties to even (glibc's printf rounds the same
-// way) - what the reference computes where the operand is a plain Python float read from config.yml
-static inline double host_round2_py(double x)
-{
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%.2f", x);
-    return std::strtod(buf, nullptr);
-}
-static inline float host_clip_f(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-static int build_tables(const mse_config &c, Params &P, std::vector<uint32_t> &image, std::string &why)
-{
-    const int cap = c.container_capacity, S = c.bale_standard_size;
-    uint32_t pat_rec[3][kPatStride];
-    for (int k = 0; k < 3; ++k) {
-        uint32_t w = 0;
-        int sum = 0;
-        for (int m = 0; m < 4; ++m) {
-            // utils/input_generator.py:47: int(np.floor(ratio * batchsize)); id 0 = the empty stage after reset
-            int cnt = k == 0 ? 0 : (int)std::floor(c.pattern_ratio[k - 1][m] * (double)c.input_batch_size);
-            w |= (uint32_t)cnt << (8 * m);
-            sum += cnt;
-        }
-        // utils/input_generator.py:49-55: units the floor()s leave over go to random materials - general generator mode
-        P.gen_rem[k] = k > 0 ? c.input_batch_size - sum : 0;
-        if (P.gen_rem[k] != 0) P.gen_mode = 1;
-        P.pat_word[k] = w;
-        auto f32_bits = [](float v) {
-            uint32_t u;
-            std::memcpy(&u, &v, 4);
-            return u;
-        };
-        pat_rec[k][0] = w;
-        // env_super.py:456 input_occupancy = round(sum/100, 2); get_sort_obs casts to f32 and clips to [-1,1]
-        pat_rec[k][1] = f32_bits(host_clip_f((float)((double)sum / 100.0), -1.0f, 1.0f));
-        pat_rec[k][3] = 0;
-        double pr[4];
-        for (int m = 0; m < 4; ++m) {
-            int cnt = (int)((w >> (8 * m)) & 0xFFu);
-            pr[m] = sum > 0 ? (double)cnt / (double)sum : 0.0;                                   // env_super.py:199-210
-            pat_rec[k][4 + m] = f32_bits(host_clip_f((float)pr[m], -1.0f, 1.0f));
-            pat_rec[k][8 + m] = f32_bits(host_clip_f((float)((double)cnt / (double)c.stage_capacity), 0.0f, 1.0f)); // :351
-        }
-        pat_rec[k][2] = (pr[0] + pr[2] > pr[1] + pr[3]) ? 0u : 1u;                               // env_super.py:479-482
-    }
-    P.pat_word1 = P.pat_word[1];
-    P.pat_word2 = P.pat_word[2];
-    {
-        const float occ = host_clip_f((float)((double)c.input_batch_size / 100.0), -1.0f, 1.0f); // env_super.py:456, :318
-        std::memcpy(&P.occ_nonempty, &occ, 4);
-    }
-    if (!P.gen_mode && (P.pat_word[1] == P.pat_word[2] || P.pat_word[1] == 0 || P.pat_word[2] == 0)) {
-        why = "the two seasonal patterns must give distinct, non-empty material counts";
-        return MSE_ERR_UNSUPPORTED_CONFIG;
-    }
-    // fill_ratio thresholds of calculate_press_reward as integer levels (env_super.py:1020-1027)
-    P.sev_negative = c.overflow_penalty_severe < 0.0 ? 1 : 0;
-    P.mild_negative = c.overflow_penalty_mild < 0.0 ? 1 : 0;
-    P.thr_sev = P.thr_mild = cap;
-    for (int L = cap; L >= 0; --L) {
-        double fill = (double)L / (double)cap;
-        if (fill > 0.95) P.thr_sev = L - 1;
-        if (fill > 0.90) P.thr_mild = L - 1;
-    }
-    double acc_rows[3][4]; // np.clip(acc + 0, 0, 1) for mode 0, mode 1, any other mode (env_super.py:499-509)
-    for (int m = 0; m < 4; ++m) {
-        P.k_thr[m] = (int)std::nearbyint(c.quality_threshold_r2[m] * 100.0);
-        if (P.k_thr[m] < 0 || P.k_thr[m] > 100) {
-            why = "quality thresholds must lie in [0, 1]";
-            return MSE_ERR_UNSUPPORTED_CONFIG;
-        }
-        const double lo = c.baseline_accuracy[m], hi = c.baseline_accuracy[m] + c.boost;
-        const double lo_c = lo < 0.0 ? 0.0 : (lo > 1.0 ? 1.0 : lo), hi_c = hi < 0.0 ? 0.0 : (hi > 1.0 ? 1.0 : hi);
-        acc_rows[0][m] = (m == 0 || m == 2) ? hi_c : lo_c;
-        acc_rows[1][m] = (m == 1 || m == 3) ? hi_c : lo_c;
-        acc_rows[2][m] = lo_c;
-    }
-    const double peaks[4] = {0.0, 1.0 / 3.0, 2.0 / 3.0, 1.0}; // env_super.py:1065
-    auto put_f32 = [&](float v) {
-        uint32_t u;
-        std::memcpy(&u, &v, 4);
-        image.push_back(u);
-    };
-    auto put_f64 = [&](double v) {
-        uint64_t u;
-        std::memcpy(&u, &v, 8);
-        image.push_back((uint32_t)u);
-        image.push_back((uint32_t)(u >> 32));
-    };
-    image.clear();
-    P.off_lvl = (int)image.size(); // env_super.py:339-344,359
-    for (int L = 0; L <= cap; ++L) put_f32(host_clip_f((float)((double)L / (double)cap), 0.0f, 1.0f));
-    P.off_pdiff = (int)image.size(); // env_super.py:212-227, 771-791, 325
-    for (int m = 0; m < 4; ++m) {
-        for (int k = 0; k <= 101; ++k) {
-            // a container's purity is an np.float64 quotient (numpy's round); an EMPTY container's is the threshold, a
-            // Python float, and so is its difference (Python's round): env_super.py:212-227, 786-789
-            const double diff = k <= 100 ? host_round2((double)k / 100.0 - c.quality_threshold[m])
-                                         : host_round2_py(c.quality_threshold_r2[m] - c.quality_threshold[m]);
-            put_f32(host_clip_f((float)diff, -1.0f, 1.0f));
-        }
-    }
-    P.off_timer0 = (int)image.size(); // env_super.py:354-356
-    for (int t = 0; t <= c.press_time[0]; ++t) put_f32(host_clip_f((float)((double)t / (double)c.press_time[0]), 0.0f, 1.0f));
-    P.off_timer1 = (int)image.size();
-    for (int t = 0; t <= c.press_time[1]; ++t) put_f32(host_clip_f((float)((double)t / (double)c.press_time[1]), 0.0f, 1.0f));
-    if (image.size() & 1u) image.push_back(0u); // 8-byte alignment of the f64 tables
-    P.off_tanh = (int)image.size(); // env_super.py:963-1003 by the sum s of the four purity hundredths
-    for (int s = 0; s <= 400; ++s) {
-        long double total = (long double)s / 100.0L - 4.0L * (long double)c.purity_threshold_theta;
-        double state_based = (double)((total / 4.0L) * 2.0L);
-        put_f64(std::tanh(state_based / c.tanh_temperature));
-    }
-    P.off_eff = (int)image.size(); // env_super.py:1058-1062
-    for (int d = 0; d <= S / 2; ++d) put_f64((1.0 - 4.0 * ((double)d / (double)S)) * c.bale_efficiency_factor);
-    P.off_acc = (int)image.size();
-    for (int r = 0; r < 3; ++r)
-        for (int m = 0; m < 4; ++m) put_f64(acc_rows[r][m]);
-    P.off_bonus = (int)image.size(); // env_super.py:1065-1069
-    for (int b = 0; b < 4; ++b) put_f64(peaks[b] - c.bale_efficiency_factor);
-    while (image.size() & 3u) image.push_back(0u); // 16-byte alignment of the per-stage records (read as float4)
-    P.off_pat = (int)image.size();
-    for (int k = 0; k < 3; ++k)
-        for (int w = 0; w < kPatStride; ++w) image.push_back(pat_rec[k][w]);
-    P.off_ptime = (int)image.size();
-    image.push_back((uint32_t)c.press_time[0]);
-    image.push_back((uint32_t)c.press_time[1]);
-    for (int w = 0; w < 4; ++w) image.push_back(P.qi_down[w]); // bale_quality_int's mask (set by mse_create before this)
-    P.off_cst = (int)image.size(); // even: every section so far has an even word count after off_tanh
-    {
-        double cst[CST_COUNT] = {};
-        cst[CST_PEN_CAT] = c.overflow_penalty_catastrophic;
-        cst[CST_PEN_SEV] = c.overflow_penalty_severe;
-        cst[CST_PEN_MILD] = c.overflow_penalty_mild;
-        cst[CST_MAX_STATE] = c.max_state_reward;
-        cst[CST_OVERFLOW_PEN] = c.overflow_termination_penalty;
-        cst[CST_REM_THR] = c.bale_remainder_threshold;
-        cst[CST_BOOST] = c.boost;
-        cst[CST_NOISE] = c.noise;
-        for (int m = 0; m < 4; ++m) cst[CST_BASE_ACC0 + m] = c.baseline_accuracy[m];
-        for (int k = 0; k < CST_COUNT; ++k) put_f64(cst[k]);
-    }
-    while (image.size() & 3u) image.push_back(0u); // the one-lane rollout kernel copies [0, off_jump) in 16-byte pieces
-    P.off_jump = (int)image.size();
-    {
-        // LCG jump-ahead by 2^j steps: A = M^(2^j), G = 1 + M + ... + M^(2^j - 1)  (mod 2^128)
-        typedef unsigned __int128 u128;
-        u128 A = (((u128)0x2360ED051FC65DA4ull) << 64) | (u128)0x4385DF649FCCF645ull, G = 1;
-        for (int j = 0; j < kJumpBits; ++j) {
-            uint64_t w4[4] = {(uint64_t)A, (uint64_t)(A >> 64), (uint64_t)G, (uint64_t)(G >> 64)};
-            for (int q = 0; q < 4; ++q) {
-                image.push_back((uint32_t)w4[q]);
-                image.push_back((uint32_t)(w4[q] >> 32));
-            }
-            G = G * (A + 1); // G_{2n} = G_n (A_n + 1)
-            A = A * A;
-        }
-    }
-    P.off_back = (int)image.size(); // even
-    {
-        // jump back by d steps (pcg_step_back): A_{-d} = M^{-d}, G_{-d} = -M^{-d} G_d
-        typedef unsigned __int128 u128;
-        const u128 M = (((u128)0x2360ED051FC65DA4ull) << 64) | (u128)0x4385DF649FCCF645ull;
-        u128 Minv = M; // Newton: x <- x (2 - M x) doubles the correct low bits; M * M = 1 mod 8 gives 3 to start
-        for (int it = 0; it < 7; ++it) Minv = Minv * (2 - M * Minv);
-        u128 Ainv = 1, Gd = 0, Ad = 1; // d = 0
-        for (int d = 0; d < kRingBackSteps; ++d) {
-            const u128 Gneg = (u128)0 - Ainv * Gd;
-            const uint64_t w4[4] = {(uint64_t)Ainv, (uint64_t)(Ainv >> 64), (uint64_t)Gneg, (uint64_t)(Gneg >> 64)};
-            for (int q = 0; q < 4; ++q) {
-                image.push_back((uint32_t)w4[q]);
-                image.push_back((uint32_t)(w4[q] >> 32));
-            }
-            Gd = Gd + Ad; // G_{d+1} = G_d + M^d
-            Ad = Ad * M;
-            Ainv = Ainv * Minv;
-        }
-    }
-    P.off_gprop = P.off_gfrac = 0;
-    if (P.gen_mode) { // per-count tables: every batch holds input_batch_size units, so a share is a function of the count
-        P.off_gprop = (int)image.size();
-        for (int k = 0; k < 256; ++k)
-            put_f32(host_clip_f((float)((double)k / (double)c.input_batch_size), -1.0f, 1.0f));
-        P.off_gfrac = (int)image.size();
-        for (int k = 0; k < 256; ++k) put_f32(host_clip_f((float)((double)k / (double)c.stage_capacity), 0.0f, 1.0f));
-    }
-    while (image.size() & 3u) image.push_back(0u); // copied to LDS in 16-byte pieces
-    P.table_words = (int)image.size();
-    if (P.table_words > 16384) {
-        why = "container_capacity / bale_standard_size too large for the LDS-resident tables (64 KiB)";
-        return MSE_ERR_UNSUPPORTED_CONFIG;
-    }
-    return MSE_OK;
-}
 
 template <int KIND>
 static size_t lds_bytes_step(const mse_env *h)
@@ -2470,23 +2271,6 @@ static bool ring_kernels_static_lds_free()
     return lds_free;
 }
 static_assert(kPlanRingMaxPerStep == kRingMaxPerStep && kRoundEnvs == kPoEnvs, "mse_plan.h restates these");
-
-// Params::ring_fwd: s_{n+d} = M^d s_n + (1 + M + ... + M^{d-1}) inc for d = ring_worst, the distance between the two
-// halves of the ring's priming (k_rollout_ring)
-static void set_ring_forward_jump(Params &P)
-{
-    typedef unsigned __int128 u128;
-    const u128 M = (((u128)0x2360ED051FC65DA4ull) << 64) | (u128)0x4385DF649FCCF645ull;
-    u128 A = 1, G = 0;
-    for (int d = 0; d < P.ring_worst; ++d) {
-        G = G + A;
-        A = A * M;
-    }
-    P.ring_fwd[0] = (uint64_t)A;
-    P.ring_fwd[1] = (uint64_t)(A >> 64);
-    P.ring_fwd[2] = (uint64_t)G;
-    P.ring_fwd[3] = (uint64_t)(G >> 64);
-}
 
 template <int KIND>
 static void launch_rollout(mse_env *h, hipStream_t s, int k_steps, uint64_t policy_seed, const int32_t *sort_mode,
@@ -2612,7 +2396,7 @@ int mse_debug_timeline(unsigned long long *out32)
 
 const char *mse_last_error(void) { return g_last_error.c_str(); }
 } // extern "C"
-int mse_internal_fail(int status, const char *msg) { return fail(status, msg); } // for the library's other translation units
+int mse_internal_fail(int status, const char *msg) { return fail(status, msg); } // mse_host.h
 extern "C" {
 
 const char *mse_status_string(int status)
@@ -2680,17 +2464,8 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     if (cfg->struct_size != sizeof(mse_config))
         return fail(MSE_ERR_INVALID_ARGUMENT, "mse_config.struct_size mismatch (ABI)");
     if (n_envs <= 0) return fail(MSE_ERR_INVALID_ARGUMENT, "n_envs must be positive");
-    if (cfg->env_kind < MSE_ENV_SORT || cfg->env_kind > MSE_ENV_MONO)
-        return fail(MSE_ERR_INVALID_ARGUMENT, "env_kind must be 1 (sort), 2 (press) or 3 (mono)");
-    if (cfg->max_steps < 1 || cfg->max_steps > 65535)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "max_steps must be in [1, 65535]");
-    if (cfg->input_batch_size < 1 || cfg->input_batch_size > 255)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "input_batch_size must be in [1, 255]");
-    if (cfg->press_time[0] < 1 || cfg->press_time[0] > 255 || cfg->press_time[1] < 1 || cfg->press_time[1] > 255)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "press_times must be in [1, 255]");
-    if (cfg->bale_standard_size < 1 || cfg->container_capacity < 1 || cfg->stage_capacity < 1)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "bale_standard_size / container_capacity / stage_capacity must be positive");
-    if (!(cfg->noise >= 0.0)) return fail(MSE_ERR_UNSUPPORTED_CONFIG, "noise must be >= 0");
+    const char *range_why = nullptr;
+    if (const int rc = config_in_range(*cfg, range_why); rc != MSE_OK) return fail(rc, range_why);
 
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -2704,43 +2479,14 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
     h->cfg = *cfg;
     h->device = device_id;
     h->trace_env = -1;
-    h->noise_on = cfg->noise != 0.0;
-    Params &P = h->P;
-    std::memset(&P, 0, sizeof(P));
-    P.n = n_envs;
-    P.n_pad = (n_envs + kBlock - 1) / kBlock * kBlock;
-    P.index_offset = index_offset;
-    P.env_kind = cfg->env_kind;
-    P.max_steps = cfg->max_steps;
-    P.auto_reset = cfg->auto_reset ? 1 : 0;
-    P.track_bales = cfg->track_bales ? 1 : 0;
-    P.balesize = cfg->bale_standard_size;
-    P.capacity = cfg->container_capacity;
-    P.stage_capacity = cfg->stage_capacity;
-    P.batch = cfg->input_batch_size;
-    P.press_time[0] = P.press_time0 = cfg->press_time[0];
-    P.press_time[1] = P.press_time1 = cfg->press_time[1];
-    P.inv_balesize = 1.0f / (float)cfg->bale_standard_size;
-    for (int q = 0; q <= 100; ++q) { // env_super.py:664-666 with the literal expressions
-        const double qd = (double)q / 100.0;
-        const int qi = (int)(qd * 100.0);
-        if (qi != q) P.qi_down[q >> 5] |= 1u << (q & 31);
-        if (qi != q && qi != q - 1) return fail(MSE_ERR_UNSUPPORTED_CONFIG, "int(q*100) is not q or q-1");
-    }
-    P.rem_thr_units = (int)std::floor((double)cfg->bale_standard_size * cfg->bale_remainder_threshold);
-    P.max_state_reward = cfg->max_state_reward;
-    // state_ratio: the reciprocal form up to the first total level where it differs from the literal division, checked
-    // over every total a stepped env can hold (no container above capacity + one batch: the overflow ends the
-    // episode); a lane beyond that bound divides
-    P.sr_den = (double)(5 * P.capacity);
-    P.sr_inv = 1.0 / P.sr_den;
-    P.sr_exact_max = ratio_exact_upto(P.sr_den, P.sr_inv, 5 * (P.capacity + 255));
-    std::vector<uint32_t> image;
+    CompiledConfig cc; // Params, the table image and the two flags: mse_tables.h
     std::string why;
-    int trc = build_tables(*cfg, P, image, why);
-    if (trc != MSE_OK) return fail(trc, why);
-    // the byte-packed integer draw needs every prefix sum below 128; larger batches draw in literal fp64
-    h->literal = cfg->literal_choice != 0 || cfg->input_batch_size > 127;
+    if (const int rc = compile_config(*cfg, n_envs, index_offset, cc, why); rc != MSE_OK) return fail(rc, why);
+    h->P = cc.P;
+    h->noise_on = cc.noise_on;
+    h->literal = cc.literal;
+    const Params &P = h->P;
+    const std::vector<uint32_t> &image = cc.image;
     int cus = 256;
     {
         hipDeviceProp_t prop;
@@ -2748,13 +2494,6 @@ int mse_create_indexed(mse_env **out, const mse_config *cfg, int64_t n_envs, int
             cus = prop.multiProcessorCount;
     }
     h->cus = cus;
-    for (int m = 0; m < 4; ++m) { // the lowest accuracy each belt can have: clip(baseline [+ boost] - noise)
-        const double lo = cfg->baseline_accuracy[m] - cfg->noise, hi = cfg->baseline_accuracy[m] + cfg->boost - cfg->noise;
-        const double lo_c = lo < 0.0 ? 0.0 : (lo > 1.0 ? 1.0 : lo), hi_c = hi < 0.0 ? 0.0 : (hi > 1.0 ? 1.0 : hi);
-        P.acc_floor[m] = lo_c < hi_c ? lo_c : hi_c;
-    }
-    P.ring_worst = max_draws_per_step(cfg->baseline_accuracy, cfg->boost, cfg->noise, P.pat_word, cfg->env_kind);
-    set_ring_forward_jump(P);
     const size_t ring_lds = with_kind(P.env_kind, [&](auto KIND) {
         return h->noise_on ? lds_with_tables<RingLayout<KIND, true>>(P) : lds_with_tables<RingLayout<KIND, false>>(P);
     });

@@ -13,11 +13,10 @@
 #include <vector>
 
 #include "mse.h"
+#include "mse_host.h"
 #include "mse_policy_device.h"
 #include "mse_policy_pack.h"
 #include "mse_policy_stream.h"
-
-int mse_internal_fail(int status, const char *msg); // mse_lib.hip: sets mse_last_error()
 
 namespace {
 

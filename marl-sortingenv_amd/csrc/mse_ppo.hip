@@ -20,9 +20,8 @@
 #include <string>
 
 #include "mse.h"
+#include "mse_host.h"
 #include "mse_ppo_math.h"
-
-int mse_internal_fail(int status, const char *msg); // mse_lib.hip: sets mse_last_error()
 
 namespace {
 
@@ -469,14 +468,6 @@ const char *shuffle_args_error(int64_t total, int64_t first, int64_t count, cons
     if (first < 0 || count < 0 || first > total || count > total - first) return "need 0 <= first, 0 <= count, first + count <= total";
     if (count > 0 && rows_out == nullptr) return "null output";
     return nullptr;
-}
-
-int cu_count()
-{
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    return cus;
 }
 
 template <int DP, int AP>

@@ -245,7 +245,7 @@ def test_model_plan_matches_the_old_rule(lib, cus):
 
 
 def _pat_words(ratio, batch):
-    """Params::pat_word as build_tables packs it: floor(ratio * batch) per material, one byte each"""
+    """Params::pat_word as compile_config (mse_tables.h) packs it: floor(ratio * batch) per material, one byte each"""
     words = [0]
     for r in ratio:
         w = 0
