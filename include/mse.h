@@ -444,6 +444,26 @@ int mse_ppo_adam_step_gated(int64_t n_weights, float *weights, const float *grad
                             double beta1, double beta2, double eps, double max_grad_norm, float *grad_norm_out, void *stream,
                             const int32_t *control_dev);
 
+/* mse_ppo_loss_grad / mse_ppo_loss_grad_gated with the gradient launch on the f32 matrix cores (k_ppo_grad_matrix:
+ * v_mfma_f32_32x32x2_f32, f32 operands and f32 accumulation).  Same arguments, same checks in the same order before any
+ * device call, same status codes, same workspace, same meaning of every output; control_dev may be NULL: no gate, and
+ * target_kl is not read.  With a control block it behaves as mse_ppo_loss_grad_gated does (a closed gate writes neither
+ * grad_out nor stats_out; the lane that writes stats_out counts the minibatch and sets stopped on
+ * (double)stats_out[4] > 1.5 * target_kl).
+ * What differs from mse_ppo_loss_grad is the ORDER in which the sums of products are formed, nothing else: the forward
+ * layers, the back-propagations and the weight gradients run as matrix products (a weight's input index, or the tile's
+ * rows, in the k order of the instruction), the per-row arithmetic (tanh, the masked softmax and its terms, the value
+ * error, the advantage normalisation, the clamping of rows and actions) is the same code.  The results therefore agree
+ * with mse_ppo_loss_grad within rounding, not bit for bit; stats_out[6..7] (from the launches around the gradient, which
+ * are the same) are bit-equal.  Equal inputs still give bit-equal outputs: no atomics, fixed orders.
+ * Grid rule: a workgroup takes 128 minibatch rows per pass (two tiles of 64) and writes one slab; there are
+ * min(ceil(batch / 128), 2 * CUs, 512) workgroups, so past 128 * min(2 * CUs, 512) rows a workgroup makes a second pass. */
+int mse_ppo_loss_grad_matrix(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                             int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions,
+                             const float *old_logp, const float *advantages, const float *returns,
+                             const mse_ppo_params *params, float *grad_out, float *stats_out, void *workspace,
+                             void *stream, double target_kl, int32_t *control_dev /* NULL: no gate, target_kl unread */);
+
 /* The learner's minibatch shuffle: rows_out[j] = perm(seed, epoch, total, first + j) for j < count, where perm(seed, epoch,
  * total, .) is a bijection of [0, total) computed per element from its arguments alone (a keyed Feistel network with
  * cycle walking, 32-bit integer arithmetic; csrc/mse_ppo_math.h specifies it completely).  No generator and no state:

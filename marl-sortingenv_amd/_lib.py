@@ -27,6 +27,7 @@ EXPORTS = [
     "mse_policy_set_weights_device", "mse_policy_sync", "mse_policy_image_floats", "mse_policy_pack_host",
     "mse_policy_read_image", "mse_policy_get_weights", "mse_ppo_loss_grad_gated", "mse_ppo_adam_step_gated",
     "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
+    "mse_ppo_loss_grad_matrix",
 ]
 
 _other_libs: dict = {}
@@ -146,6 +147,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_adam_step.argtypes = [i64, vp, vp, vp, vp, i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     L.mse_ppo_loss_grad_gated.argtypes = L.mse_ppo_loss_grad.argtypes + [C.c_double, vp]
     L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
+    L.mse_ppo_loss_grad_matrix.argtypes = L.mse_ppo_loss_grad_gated.argtypes
     L.mse_ppo_shuffle.argtypes = [i64, u64, u64, i64, i64, vp, vp]
     L.mse_ppo_shuffle_host.argtypes = [i64, u64, u64, i64, i64, vp]
     L.mse_episode_workspace_bytes.argtypes = []

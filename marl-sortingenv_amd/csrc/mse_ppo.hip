@@ -22,6 +22,7 @@
 #include "mse.h"
 #include "mse_host.h"
 #include "mse_ppo_math.h"
+#include "mse_ppo_matrix.h"
 
 namespace {
 
@@ -481,11 +482,12 @@ int launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weig
     return 0;
 }
 
-// mse_ppo_loss_grad (control == NULL) and mse_ppo_loss_grad_gated; `who` names the entry point in messages
+// mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated and mse_ppo_loss_grad_matrix (matrix: the gradient launch is
+// k_ppo_grad_matrix of mse_ppo_matrix.hip, the launches around it are the same); `who` names the entry point in messages
 int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
               int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
               const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out, float *stats_out,
-              void *workspace, void *stream, Gate gate)
+              void *workspace, void *stream, Gate gate, bool matrix = false)
 {
     auto fail = [who](int status, const char *why) { return mse_internal_fail(status, (std::string(who) + ": " + why).c_str()); };
     if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
@@ -514,6 +516,18 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
         G.n_adv_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
         hipLaunchKernelGGL(k_ppo_adv_partial, dim3((unsigned)G.n_adv_partial), dim3(256), 0, s, (long long)batch, (long long)n_rows, rows,
                            advantages, adv_partial, gate.control);
+    }
+    if (matrix) {
+        const long long groups = mse_ppo_matrix_groups(batch, cus, kMaxSlabs);
+        const int w_total = flat_layout(obs_dim, n_actions).total;
+        const MsePpoMatrixArgs M{obs_dim, n_actions, (long long)n_rows, (long long)batch, G.n_adv_partial, G.P, slab_stride(w_total), kGateCell};
+        if (mse_ppo_launch_grad_matrix(M, (int)groups, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns,
+                                       adv_partial, slabs, gate.control) != hipSuccess)
+            return fail(MSE_ERR_HIP, "kernel launch failed");
+        hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)groups, w_total, slabs, rows,
+                           advantages, adv_partial, grad_out, stats_out, gate);
+        if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+        return MSE_OK;
     }
     const long long tiles = (batch + 63) / 64;
     long long n_slabs = (tiles + 1) / 2;
@@ -595,6 +609,18 @@ int mse_ppo_loss_grad_gated(int obs_dim, int n_actions, const float *weights_dev
     if (target_kl != target_kl) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_gated: target_kl is NaN");
     return loss_grad("mse_ppo_loss_grad_gated", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
                      advantages, returns, params, grad_out, stats_out, workspace, stream, Gate{control_dev, 1.5 * target_kl});
+}
+
+int mse_ppo_loss_grad_matrix(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                             int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                             const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                             float *stats_out, void *workspace, void *stream, double target_kl, int32_t *control_dev)
+{
+    if (control_dev != nullptr && target_kl != target_kl)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_matrix: target_kl is NaN");
+    return loss_grad("mse_ppo_loss_grad_matrix", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
+                     advantages, returns, params, grad_out, stats_out, workspace, stream,
+                     control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, true);
 }
 
 int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,

@@ -151,6 +151,61 @@ MSE_PPO_HD void grad_shape_dims(GradShape s, int &dp, int &ap)
     default: break;                                            \
     }
 
+// ---- the weight image of the matrix-core gradient kernel (mse_ppo_matrix.hip) --------------------------------------------
+// Every 32 x 32 weight block is kept as the A operands of v_mfma_f32_32x32x2_f32: lane (half h, m) supplies, at k-step s,
+// the element (m, k) with k = mat_row_of(s, h) - the row an accumulator register s holds in half h, so that an accumulator
+// tile is the next product's B operand as it stands.  A block is [4 groups][64 lanes][4 slots] floats, k-step s = 4 group +
+// slot: one 16-byte read per lane and group.  Forward blocks have m = output unit, k = input; the blocks the
+// back-propagation reads are the transposes (m = input, k = output).  Rows and columns a shape does not have stay zero.
+// After the eight blocks come the vectors in natural order, 32 floats each: pi_b1, pi_b2, act_b, vf_b1, vf_b2, val_w, then
+// val_b.  The image does not depend on a padded shape.
+constexpr int kMatBlockFloats = 32 * 32;
+enum MatBlock { kMatPiW1 = 0, kMatPiW2, kMatActW, kMatPiW2T, kMatActWT, kMatVfW1, kMatVfW2, kMatVfW2T, kMatBlocks };
+constexpr int kMatPiB1 = kMatBlocks * kMatBlockFloats;
+constexpr int kMatPiB2 = kMatPiB1 + 32;
+constexpr int kMatActB = kMatPiB2 + 32;
+constexpr int kMatVfB1 = kMatActB + 32;
+constexpr int kMatVfB2 = kMatVfB1 + 32;
+constexpr int kMatValW = kMatVfB2 + 32;
+constexpr int kMatValB = kMatValW + 32;
+constexpr int kMatTotal = kMatValB + 4;
+
+MSE_PPO_HD int mat_row_of(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; } // = msep::row_of
+// element (m, k) of a block -> its cell in the image
+MSE_PPO_HD int mat_cell(int block, int m, int k)
+{
+    const int h = (k >> 2) & 1, s = (k & 3) + 4 * (k >> 3); // k = mat_row_of(s, h)
+    return block * kMatBlockFloats + (s >> 2) * 256 + (32 * h + m) * 4 + (s & 3);
+}
+
+// flat index (0 <= f < flat_layout(D, A).total) -> the cell of the image every weight has
+MSE_PPO_HD int matrix_index(int f, int D, int A)
+{
+    const Flat F = flat_layout(D, A);
+    if (f < F.pi_b1) return mat_cell(kMatPiW1, f / D, f % D);
+    if (f < F.pi_w2) return kMatPiB1 + (f - F.pi_b1);
+    if (f < F.pi_b2) return mat_cell(kMatPiW2, (f - F.pi_w2) / kH, (f - F.pi_w2) % kH);
+    if (f < F.act_w) return kMatPiB2 + (f - F.pi_b2);
+    if (f < F.act_b) return mat_cell(kMatActW, (f - F.act_w) / kH, (f - F.act_w) % kH);
+    if (f < F.vf_w1) return kMatActB + (f - F.act_b);
+    if (f < F.vf_b1) return mat_cell(kMatVfW1, (f - F.vf_w1) / D, (f - F.vf_w1) % D);
+    if (f < F.vf_w2) return kMatVfB1 + (f - F.vf_b1);
+    if (f < F.vf_b2) return mat_cell(kMatVfW2, (f - F.vf_w2) / kH, (f - F.vf_w2) % kH);
+    if (f < F.val_w) return kMatVfB2 + (f - F.vf_b2);
+    if (f < F.val_b) return kMatValW + (f - F.val_w);
+    return kMatValB;
+}
+
+// ... -> the cell of its transposed copy (pi_w2, act_w, vf_w2: what the back-propagation multiplies by), -1 for the rest
+MSE_PPO_HD int matrix_index_transposed(int f, int D, int A)
+{
+    const Flat F = flat_layout(D, A);
+    if (f >= F.pi_w2 && f < F.pi_b2) return mat_cell(kMatPiW2T, (f - F.pi_w2) % kH, (f - F.pi_w2) / kH);
+    if (f >= F.act_w && f < F.act_b) return mat_cell(kMatActWT, (f - F.act_w) % kH, (f - F.act_w) / kH);
+    if (f >= F.vf_w2 && f < F.vf_b2) return mat_cell(kMatVfW2T, (f - F.vf_w2) % kH, (f - F.vf_w2) / kH);
+    return -1;
+}
+
 // tanh without branches (a lane-divergent libm call would run every path).  Below 0.625: x (1 + u P(u)), u = x^2, P a
 // degree-5 least-squares fit of (tanh(x) / x - 1) / u on Chebyshev nodes (error < 1e-10 in exact arithmetic, 4e-8 as
 // evaluated in float32).  Above: 1 - 2 q with q = 1 / (e^(2|x|) + 1) <= 0.223, so q's few ulp of relative error stay

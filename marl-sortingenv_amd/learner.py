@@ -76,17 +76,25 @@ class PPOLearner:
     `target_kl` (SB3's; None = off): after a minibatch whose approx_kl exceeds 1.5 * target_kl that minibatch takes no
     optimiser step and no later minibatch of the update runs.  The decision is taken on the device: `update()` still
     enqueues every minibatch, the ones after the stop exit at once, and the result says what ran.  `step` counts the
-    Adam steps actually taken; `epochs_done` advances by the epochs ENQUEUED (n_epochs per update), run or not."""
+    Adam steps actually taken; `epochs_done` advances by the epochs ENQUEUED (n_epochs per update), run or not.
+
+    `arithmetic="fma"` (the default) forms the gradient's products as fmaf chains on the vector unit
+    (`mse_ppo_loss_grad`); `"matrix"` forms them on the f32 matrix cores (`mse_ppo_loss_grad_matrix`): the same per-row
+    arithmetic, sums in another order, so the two agree within rounding and each is reproducible bit for bit."""
 
     def __init__(self, policy: MlpPolicy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
                  gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: float = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
-                 seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None):
+                 seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None,
+                 arithmetic: str = "fma"):
         if shuffle not in ("cpu", "device"):
             raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
         if weight_sync not in ("host", "device"):
             raise ValueError(f"weight_sync must be 'host' or 'device', not {weight_sync!r}")
+        if arithmetic not in ("fma", "matrix"):
+            raise ValueError(f"arithmetic must be 'fma' or 'matrix', not {arithmetic!r}")
         self.weight_sync = weight_sync
+        self.arithmetic = arithmetic
         self.target_kl = None if target_kl is None else float(target_kl)
         self.policy, self.L = policy, policy.L
         self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
@@ -121,7 +129,8 @@ class PPOLearner:
                   control: Optional[torch.Tensor] = None, target_kl: float = 0.0) -> torch.Tensor:
         """One `mse_ppo_loss_grad` on the flattened rollout in `data` (which holds advantages / returns); returns the
         gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1.
-        control: i32[2] device tensor {stopped, minibatches_run}: `mse_ppo_loss_grad_gated` with `target_kl` instead."""
+        control: i32[2] device tensor {stopped, minibatches_run}: `mse_ppo_loss_grad_gated` with `target_kl` instead.
+        With `arithmetic="matrix"` both go to `mse_ppo_loss_grad_matrix`."""
         p = self.policy
         obs = data["observations"]
         n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
@@ -135,7 +144,9 @@ class PPOLearner:
                 _ptr(data["log_probs"]), _ptr(data["advantages"]), _ptr(data["returns"]), C.byref(self.params), _ptr(g),
                 _ptr(stats_out), _ptr(self.workspace), _stream(self.device))
         with torch.cuda.device(self.device):
-            if control is None:
+            if self.arithmetic == "matrix":
+                check(self.L.mse_ppo_loss_grad_matrix(*args, float(target_kl), _ptr(control)))
+            elif control is None:
                 check(self.L.mse_ppo_loss_grad(*args))
             else:
                 check(self.L.mse_ppo_loss_grad_gated(*args, float(target_kl), _ptr(control)))

@@ -8,6 +8,9 @@
                                                           # update() with shuffle="cpu" and shuffle="device"; then the weight
                                                           # hand-over alone and inside update(), host against device
     python tools/train_ppo.py --kind mono --weight-sync device --target-kl 0.03   # repack on the device; SB3's early stop
+    python tools/train_ppo.py --kind mono --arithmetic matrix   # the gradient's products on the f32 matrix cores
+    python tools/train_ppo.py --kind mono --time --time-section arithmetic   # only the last block of --time: loss_grad and
+                                                          # update() with arithmetic="fma" against "matrix"
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -151,6 +154,47 @@ def time_weight_sync(args):
                 + (" us" if group is loads else " ms") for name, ts in times.items()))
 
 
+def time_arithmetic(args):
+    """arithmetic="fma" against "matrix" at 4 096, 65 536 and 2^20 rows: `loss_grad` alone (rows_dev = NULL, back-to-back
+    calls ending in one synchronise, the time per call) and one update() (10 epochs x 4 minibatches, shuffle="device",
+    weight_sync="device").  One process, the two forms alternating, one warm-up each, then three timed repetitions each."""
+    D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
+    K = 16
+    forms = ("fma", "matrix")
+    for rows in (4096, 65536, 2 ** 20):
+        n = rows // K
+        pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+        env = M.BatchedSortingEnv(kind=args.kind, num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+        col = M.FusedPolicyRollout(env, pol, K, seed=args.seed)
+        data = M.compute_gae(col.collect())
+        stats = torch.zeros(8, device="cuda")
+        calls = 20 if rows <= 65536 else 5
+        learners = {f: M.PPOLearner(pol, ent_coef=0.05, arithmetic=f) for f in forms}
+        updaters = {f: M.PPOLearner(pol, ent_coef=0.05, shuffle="device", weight_sync="device", arithmetic=f) for f in forms}
+
+        def loss_grads(lrn):
+            for _ in range(calls):
+                lrn.loss_grad(data, None, rows, stats)
+
+        for what, group, per in (("loss_grad", {f: (lambda lrn=lrn: loss_grads(lrn)) for f, lrn in learners.items()}, calls),
+                                 ("update", {f: (lambda lrn=lrn: lrn.update(data)) for f, lrn in updaters.items()}, 1)):
+            times = {f: [] for f in forms}
+            for r in range(4):
+                for f, fn in group.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    torch.cuda.synchronize()
+                    if r > 0:
+                        times[f].append((time.perf_counter() - t0) / per)
+            unit, name = (1e6, "us") if what == "loss_grad" else (1e3, "ms")
+            worst = min(times["fma"]) / max(times["matrix"])
+            best = max(times["fma"]) / min(times["matrix"])
+            print(f"{args.kind} rows={rows}: {what} " + ", ".join(
+                f"arithmetic={f} " + " / ".join(f"{t * unit:.1f}" if unit == 1e6 else f"{t * unit:.2f}" for t in ts) + f" {name}"
+                for f, ts in times.items()) + f"; fma / matrix {worst:.2f} .. {best:.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=sorted(KINDS), default="mono")
@@ -173,21 +217,28 @@ def main():
                     help="print the episodes that ended in each rollout with their mean return and length (SB3's ep_rew_mean)")
     ap.add_argument("--eval-every", type=int, default=0,
                     help="every this many iterations evaluate_policy (10 deterministic episodes) and keep the best weights")
+    ap.add_argument("--arithmetic", choices=("fma", "matrix"), default="fma",
+                    help="how the gradient's products are formed: fmaf chains on the vector unit, or the f32 matrix cores")
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic"), default="all",
+                    help="with --time: run one block of the timings only")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
     if args.time:
-        time_loss_grad(args)
-        return time_weight_sync(args)
+        for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic)):
+            if args.time_section in ("all", name):
+                fn(args)
+        return
     D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
     env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
     learner = M.PPOLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
-                           seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl)
+                           seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
+                           arithmetic=args.arithmetic)
     print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
-          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}")
+          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}")
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
