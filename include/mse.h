@@ -402,7 +402,10 @@ int mse_gae(int32_t k_steps, int64_t n, const float *rewards, const float *value
  *   stats_out    f32[8]: loss, policy_loss, value_loss, entropy_loss, approx_kl = mean((ratio - 1) - log ratio),
  *                clip_fraction, and the advantage mean and std that were used (0 and 1 when not normalised)
  *   workspace    mse_ppo_workspace_bytes(D, A) bytes, 16-byte aligned; contents need not survive between calls
- * Three launches; sums are formed in a fixed order without atomics, so equal inputs give bit-equal outputs. */
+ * Three launches; sums are formed in a fixed order without atomics, so equal inputs give bit-equal outputs.
+ * Grid rule of the gradient launch: a workgroup takes 128 minibatch rows per pass (two tiles of 64) and writes one slab;
+ * there are min(ceil(batch / 128), 2 * CUs, 512) workgroups, so past 128 * min(2 * CUs, 512) rows a workgroup makes a
+ * second pass. */
 typedef struct mse_ppo_params {
     uint32_t struct_size; /* = sizeof(mse_ppo_params) */
     float    clip_range;
@@ -455,9 +458,8 @@ int mse_ppo_adam_step_gated(int64_t n_weights, float *weights, const float *grad
  * rows, in the k order of the instruction), the per-row arithmetic (tanh, the masked softmax and its terms, the value
  * error, the advantage normalisation, the clamping of rows and actions) is the same code.  The results therefore agree
  * with mse_ppo_loss_grad within rounding, not bit for bit; stats_out[6..7] (from the launches around the gradient, which
- * are the same) are bit-equal.  Equal inputs still give bit-equal outputs: no atomics, fixed orders.
- * Grid rule: a workgroup takes 128 minibatch rows per pass (two tiles of 64) and writes one slab; there are
- * min(ceil(batch / 128), 2 * CUs, 512) workgroups, so past 128 * min(2 * CUs, 512) rows a workgroup makes a second pass. */
+ * are the same) are bit-equal.  Equal inputs still give bit-equal outputs: no atomics, fixed orders.  The grid rule is
+ * mse_ppo_loss_grad's. */
 int mse_ppo_loss_grad_matrix(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
                              int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions,
                              const float *old_logp, const float *advantages, const float *returns,

@@ -21,34 +21,22 @@
 
 #include "mse.h"
 #include "mse_host.h"
+#include "mse_ppo_grad.h"
 #include "mse_ppo_math.h"
-#include "mse_ppo_matrix.h"
 
 namespace {
 
 using namespace mseppo;
 
-constexpr int kMaxSlabs = 512;       // workgroups of k_ppo_grad at most (two per CU on 256 CUs)
 constexpr int kMaxAdvPartials = 256; // workgroups of k_ppo_adv_partial at most
-constexpr int kStatFloats = 8;       // per slab: surrogate, squared error, entropy, kl, clipped sums
 constexpr int kStageStride = 68;     // floats per staged row: 32 deltas + 32 activations + 4 (16-byte rows, spread banks)
 constexpr int kStageFloats = 32 * kStageStride;
-constexpr int kMiscFloats = 20;        // advantage mean / std, the waves' loss sums
 
-__host__ __device__ constexpr long long slab_stride(long long w) { return (w + kStatFloats + 3) / 4 * 4; }
-
-// ---- the target_kl gate ------------------------------------------------------------------------------------------------
-// control = {stopped, minibatches_run} (caller-owned, NULL: no gate).  Only the lane of k_ppo_reduce that writes stats_out
-// ever writes it, so a kernel that reads `stopped` at entry reads what an EARLIER launch of the stream left: the load
-// is uniform over the whole grid.  k_ppo_reduce itself cannot read it that way (its other workgroups may start after
-// that lane has stored), so workgroup 0 of k_ppo_grad, one launch earlier, leaves the value it saw in float 5 of slab 0's
-// statistics (a cell no sum reads; 0 when there is no gate, as it always was) and k_ppo_reduce gates on that.
-constexpr int kGateCell = 5;
+// ---- the target_kl gate (mse_ppo_grad.h: kGateCell) -----------------------------------------------------------------------
 struct Gate {
     int *control;    // NULL: no gate
     double kl_limit; // 1.5 * target_kl; <= 0: the flag is honoured and the count kept, but never set
 };
-__device__ __forceinline__ bool gate_closed(const int *control) { return control != nullptr && control[0] != 0; }
 
 // ---- GAE ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_gae(int k_steps, long long n, const float *__restrict__ rewards,
@@ -61,13 +49,6 @@ __global__ __launch_bounds__(256) void k_gae(int k_steps, long long n, const flo
 }
 
 // ---- advantage mean / std: partial sums of d = a - pivot and d^2 in double, one pair per workgroup -------------------
-__device__ __forceinline__ long long row_at(const long long *rows, long long b, long long n_rows)
-{
-    long long r = rows == nullptr ? b : rows[b];
-    r = r < 0 ? 0 : r;
-    return r >= n_rows ? n_rows - 1 : r; // an index outside the rollout is clamped, never followed
-}
-
 __global__ __launch_bounds__(256) void k_ppo_adv_partial(long long batch, long long n_rows, const long long *__restrict__ rows,
                                                          const float *__restrict__ adv, double *__restrict__ partial,
                                                          const int *__restrict__ control)
@@ -97,34 +78,7 @@ __global__ __launch_bounds__(256) void k_ppo_adv_partial(long long batch, long l
     }
 }
 
-// mean and unbiased std from the partials, summed in index order (every caller gets the same bits)
-__device__ __forceinline__ void adv_mean_std(const double *partial, int n_partial, double pivot, long long batch, float &mean, float &std)
-{
-    double s = 0.0, q = 0.0;
-    for (int g = 0; g < n_partial; ++g) {
-        s += partial[2 * g];
-        q += partial[2 * g + 1];
-    }
-    const double var = (q - s * s / (double)batch) / (double)(batch - 1);
-    mean = (float)(pivot + s / (double)batch);
-    std = (float)sqrt(var > 0.0 ? var : 0.0);
-}
-
 // ---- the gradient kernel ------------------------------------------------------------------------------------------------
-struct GradArgs {
-    int D, A;
-    long long n_rows, batch;
-    int n_adv_partial; // 0: advantages are used as they are
-    Params P;
-};
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 template <int N>
 __device__ __forceinline__ float padded_at(const float (&v)[N], int i) // i is a compile-time constant after unrolling
 {
@@ -170,13 +124,6 @@ struct LayerAcc {
     float w[16], b[4];
 };
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64); // fixed butterfly
-    return v;
-}
-
 // one layer's accumulators -> the flat gradient: out[w_off + o * ld + i] (o < n_out, i < n_in), out[b_off + o]
 __device__ __forceinline__ void store_layer(float *out, const LayerAcc &L, int lane, int w_off, int b_off, int n_out, int n_in, int ld)
 {
@@ -203,32 +150,23 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
 {
     typedef Padded<DP, AP> PW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (gate_closed(control)) { // grid-uniform; the mark for k_ppo_reduce is all a closed gate writes
-        if (blockIdx.x == 0 && threadIdx.x == 0) slabs[flat_layout(G.D, G.A).total + kGateCell] = 1.0f;
+    if (gate_closed(control)) { // grid-uniform
+        mark_gate_closed(flat_layout(G.D, G.A).total, slabs);
         return;
     }
     float *wl0 = lds;                     // PW::total floats: the padded weights
     float *strips = lds + PW::total;      // 4 x kStageFloats: one staging strip per wave
-    // (no static __shared__: it would shift the dynamic base off its 16-byte alignment)
-    float *sh_mean_std = strips + 4 * kStageFloats;                       // [2]
-    float(*sh_stats)[4] = reinterpret_cast<float(*)[4]>(sh_mean_std + 4); // [4 waves][4]
+    float *misc = strips + 4 * kStageFloats; // kMiscFloats
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int D = G.D, A = G.A;
     const Flat F = flat_layout(D, A);
     for (int i = tid; i < PW::total; i += 256) wl0[i] = 0.0f;
     __syncthreads();
     for (int f = tid; f < F.total; f += 256) wl0[padded_index<DP, AP>(f, D, A)] = weights[f];
-    if (wave == 0) { // every lane sums the same partials in the same order
-        float mean = 0.0f, std = 1.0f;
-        if (G.n_adv_partial > 0) adv_mean_std(adv_partial, G.n_adv_partial, (double)adv[row_at(rows, 0, G.n_rows)], G.batch, mean, std);
-        if (lane == 0) {
-            sh_mean_std[0] = mean;
-            sh_mean_std[1] = std;
-        }
-    }
+    publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
     __syncthreads();
     const bool normalize = G.n_adv_partial > 0;
-    const float mean = sh_mean_std[0], std = sh_mean_std[1];
+    const float mean = misc[0], std = misc[1];
     const float inv_b_all = 1.0f / (float)G.batch;
     const bool critic = (wave & 1) != 0;
     float *strip = strips + wave * kStageFloats;
@@ -259,8 +197,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
                 const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
                 legal |= (ok ? 1u : 0u) << a;
             }
-            int action = actions[row];
-            action = action < 0 ? 0 : (action >= A ? A - 1 : action);
+            const int action = clamped_action(actions[row], A);
             const float a_raw = adv[row];
             const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
             hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
@@ -312,12 +249,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
             xch[(56 + k) * 64 + lane] = L3.b[k];
         }
     }
-    if (lane == 0) {
-        sh_stats[wave][0] = st0;
-        sh_stats[wave][1] = st1;
-        sh_stats[wave][2] = st2;
-        sh_stats[wave][3] = st3;
-    }
+    publish_loss_sums(misc, wave, lane, st0, st1, st2, st3);
     __syncthreads();
     float *slab = slabs + (long long)blockIdx.x * slab_stride(F.total);
     if (wave < 2) {
@@ -343,15 +275,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
             store_layer(slab, L3, lane, F.val_w, F.val_b, 1, kH, kH);
         }
     }
-    if (tid == 0) {
-        float *s = slab + F.total;
-        s[0] = sh_stats[0][0] + sh_stats[2][0]; // surrogate
-        s[1] = sh_stats[1][0] + sh_stats[3][0]; // squared value error
-        s[2] = sh_stats[0][1] + sh_stats[2][1]; // entropy
-        s[3] = sh_stats[0][2] + sh_stats[2][2]; // kl
-        s[4] = sh_stats[0][3] + sh_stats[2][3]; // clipped
-        s[5] = s[6] = s[7] = 0.0f;
-    }
+    if (tid == 0) store_slab_stats(slab + F.total, misc);
 }
 
 // grad_out[i] = sum over slabs, in slab order, in double; the last workgroup turns the loss sums into stats_out
@@ -372,7 +296,7 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
         return;
     }
     __shared__ double sums[kStatFloats];
-    if (threadIdx.x < 5) {
+    if (threadIdx.x < kStatSums) {
         double s = 0.0;
 #pragma unroll 8
         for (int g = 0; g < n_slabs; ++g) s += (double)slabs[(long long)g * stride + w_total + threadIdx.x];
@@ -471,19 +395,19 @@ const char *shuffle_args_error(int64_t total, int64_t first, int64_t count, cons
     return nullptr;
 }
 
+// enqueues k_ppo_grad; a failed launch shows in hipGetLastError after k_ppo_reduce's
 template <int DP, int AP>
-int launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
-                const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
-                const double *adv_partial, float *slabs, const int *control)
+void launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                 const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
+                 const double *adv_partial, float *slabs, const int *control)
 {
     const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
     hipLaunchKernelGGL((k_ppo_grad<DP, AP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
                        old_logp, adv, ret, adv_partial, slabs, control);
-    return 0;
 }
 
 // mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated and mse_ppo_loss_grad_matrix (matrix: the gradient launch is
-// k_ppo_grad_matrix of mse_ppo_matrix.hip, the launches around it are the same); `who` names the entry point in messages
+// k_ppo_grad_matrix of mse_ppo_matrix.hip; everything around it is the same); `who` names the entry point in messages
 int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
               int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
               const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out, float *stats_out,
@@ -517,31 +441,25 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
         hipLaunchKernelGGL(k_ppo_adv_partial, dim3((unsigned)G.n_adv_partial), dim3(256), 0, s, (long long)batch, (long long)n_rows, rows,
                            advantages, adv_partial, gate.control);
     }
+    const int n_slabs = (int)grad_groups(batch, cus);
+    hipError_t e = hipSuccess;
     if (matrix) {
-        const long long groups = mse_ppo_matrix_groups(batch, cus, kMaxSlabs);
-        const int w_total = flat_layout(obs_dim, n_actions).total;
-        const MsePpoMatrixArgs M{obs_dim, n_actions, (long long)n_rows, (long long)batch, G.n_adv_partial, G.P, slab_stride(w_total), kGateCell};
-        if (mse_ppo_launch_grad_matrix(M, (int)groups, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns,
-                                       adv_partial, slabs, gate.control) != hipSuccess)
-            return fail(MSE_ERR_HIP, "kernel launch failed");
-        hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)groups, w_total, slabs, rows,
-                           advantages, adv_partial, grad_out, stats_out, gate);
-        if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
-        return MSE_OK;
-    }
-    const long long tiles = (batch + 63) / 64;
-    long long n_slabs = (tiles + 1) / 2;
-    const long long cap = 2LL * cus < kMaxSlabs ? 2LL * cus : kMaxSlabs;
-    if (n_slabs > cap) n_slabs = cap;
-    // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
+        e = mse_ppo_launch_grad_matrix(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial,
+                                       slabs, gate.control);
+    } else {
+        // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
 #define MSE_PPO_LAUNCH(DP, AP) \
-    launch_grad<DP, AP>(G, (int)n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, gate.control)
-    MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
+    launch_grad<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, gate.control)
+        MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
 #undef MSE_PPO_LAUNCH
-    const int w_total = flat_layout(obs_dim, n_actions).total;
-    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, (int)n_slabs, w_total, slabs, rows,
-                       advantages, adv_partial, grad_out, stats_out, gate);
-    if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    }
+    if (e == hipSuccess) {
+        const int w_total = flat_layout(obs_dim, n_actions).total;
+        hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, n_slabs, w_total, slabs, rows,
+                           advantages, adv_partial, grad_out, stats_out, gate);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
     return MSE_OK;
 }
 

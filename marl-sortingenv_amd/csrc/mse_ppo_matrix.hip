@@ -23,8 +23,8 @@
 #include <atomic>
 #include <cstdint>
 
+#include "mse_ppo_grad.h"
 #include "mse_ppo_math.h"
-#include "mse_ppo_matrix.h"
 
 namespace {
 
@@ -35,7 +35,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kStripStride = 36;                  // floats per staged row: 9 16-byte slots, odd, so 16 rows hit 16 slots
 constexpr int kStripFloats = 64 * kStripStride;   // [64 rows][36] logits, or 2 x [32 units][36] transposed operands
 constexpr int kTransposedFloats = 32 * kStripStride;
-constexpr int kMiscFloats = 20;                   // advantage mean / std, the waves' loss sums
 constexpr int kLdsFloats = kMatTotal + 4 * kStripFloats + kMiscFloats;
 constexpr int kExchangeFloats = 51 * 64;          // per network: 3 x 16 accumulators + 3 bias sums of 64 lanes
 static_assert(2 * kExchangeFloats <= 4 * kStripFloats, "the exchange reuses the strips");
@@ -47,42 +46,6 @@ constexpr int ksteps_for(int n)
     for (int r = 0; r < 16; ++r)
         if ((r & 3) + 8 * (r >> 2) < n) k = r + 1;
     return k;
-}
-
-// as in mse_ppo.hip (k_ppo_adv_partial and k_ppo_reduce, which run around this kernel, use the same three)
-__device__ __forceinline__ bool gate_closed(const int *control) { return control != nullptr && control[0] != 0; }
-
-__device__ __forceinline__ long long row_at(const long long *rows, long long b, long long n_rows)
-{
-    long long r = rows == nullptr ? b : rows[b];
-    r = r < 0 ? 0 : r;
-    return r >= n_rows ? n_rows - 1 : r; // an index outside the rollout is clamped, never followed
-}
-
-__device__ __forceinline__ void adv_mean_std(const double *partial, int n_partial, double pivot, long long batch, float &mean, float &std)
-{
-    double s = 0.0, q = 0.0;
-    for (int g = 0; g < n_partial; ++g) {
-        s += partial[2 * g];
-        q += partial[2 * g + 1];
-    }
-    const double var = (q - s * s / (double)batch) / (double)(batch - 1);
-    mean = (float)(pivot + s / (double)batch);
-    std = (float)sqrt(var > 0.0 ? var : 0.0);
-}
-
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64); // fixed butterfly
-    return v;
 }
 
 // the value of the other half's lane j, added to this one's in the fixed order half 0 + half 1
@@ -192,7 +155,7 @@ __device__ __forceinline__ void store_value_head(float *out, const LayerGrad &L,
 }
 
 template <int DP, int AP>
-__global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, const float *__restrict__ weights,
+__global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float *__restrict__ weights,
                                                          const long long *__restrict__ rows, const float *__restrict__ obs,
                                                          const uint8_t *__restrict__ mask, const int *__restrict__ actions,
                                                          const float *__restrict__ old_logp, const float *__restrict__ adv,
@@ -204,14 +167,13 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, con
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int D = G.D, A = G.A;
     const Flat F = flat_layout(D, A);
-    if (gate_closed(control)) { // grid-uniform; the mark for k_ppo_reduce is all a closed gate writes
-        if (blockIdx.x == 0 && threadIdx.x == 0) slabs[F.total + G.gate_cell] = 1.0f;
+    if (gate_closed(control)) { // grid-uniform
+        mark_gate_closed(F.total, slabs);
         return;
     }
     float *wl0 = lds;                       // kMatTotal floats: the operand image
     float *strips = lds + kMatTotal;        // 4 x kStripFloats: one staging strip per wave
-    float *sh_mean_std = strips + 4 * kStripFloats;                       // [2]
-    float(*sh_stats)[4] = reinterpret_cast<float(*)[4]>(sh_mean_std + 4); // [4 waves][4]
+    float *misc = strips + 4 * kStripFloats; // kMiscFloats
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, j = lane & 31;
     for (int i = tid; i < kMatTotal; i += 256) wl0[i] = 0.0f;
@@ -222,17 +184,10 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, con
         const int tr = matrix_index_transposed(f, D, A);
         if (tr >= 0) wl0[tr] = w;
     }
-    if (wave == 0) { // every lane sums the same partials in the same order
-        float mean = 0.0f, std = 1.0f;
-        if (G.n_adv_partial > 0) adv_mean_std(adv_partial, G.n_adv_partial, (double)adv[row_at(rows, 0, G.n_rows)], G.batch, mean, std);
-        if (lane == 0) {
-            sh_mean_std[0] = mean;
-            sh_mean_std[1] = std;
-        }
-    }
+    publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
     __syncthreads();
     const bool normalize = G.n_adv_partial > 0;
-    const float mean = sh_mean_std[0], std = sh_mean_std[1];
+    const float mean = misc[0], std = misc[1];
     const float inv_b_all = 1.0f / (float)G.batch;
     const bool critic = (wave & 1) != 0;
     float *strip = strips + wave * kStripFloats;
@@ -319,8 +274,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, con
                 const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
                 legal |= (ok ? 1u : 0u) << a;
             }
-            int action = actions[row];
-            action = action < 0 ? 0 : (action >= A ? A - 1 : action);
+            const int action = clamped_action(actions[row], A);
             const float a_raw = adv[row];
             const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
             const PolicyTerms pt = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
@@ -415,14 +369,9 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, con
         xch[49 * 64 + lane] = L2.b;
         xch[50 * 64 + lane] = L3.b;
     }
-    if (lane == 0) {
-        sh_stats[wave][0] = st0;
-        sh_stats[wave][1] = st1;
-        sh_stats[wave][2] = st2;
-        sh_stats[wave][3] = st3;
-    }
+    publish_loss_sums(misc, wave, lane, st0, st1, st2, st3);
     __syncthreads();
-    float *slab = slabs + (long long)blockIdx.x * G.slab_stride;
+    float *slab = slabs + (long long)blockIdx.x * slab_stride(F.total);
     if (wave < 2) {
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
@@ -443,19 +392,11 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(MsePpoMatrixArgs G, con
             store_value_head(slab, L3, lane, F.val_w, F.val_b);
         }
     }
-    if (tid == 0) {
-        float *s = slab + F.total;
-        s[0] = sh_stats[0][0] + sh_stats[2][0]; // surrogate
-        s[1] = sh_stats[1][0] + sh_stats[3][0]; // squared value error
-        s[2] = sh_stats[0][1] + sh_stats[2][1]; // entropy
-        s[3] = sh_stats[0][2] + sh_stats[2][2]; // kl
-        s[4] = sh_stats[0][3] + sh_stats[2][3]; // clipped
-        s[5] = s[6] = s[7] = 0.0f;
-    }
+    if (tid == 0) store_slab_stats(slab + F.total, misc);
 }
 
 template <int DP, int AP>
-hipError_t launch(const MsePpoMatrixArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
                   const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
                   const double *adv_partial, float *slabs, const int *control)
 {
@@ -477,7 +418,7 @@ hipError_t launch(const MsePpoMatrixArgs &G, int n_slabs, hipStream_t s, const f
 
 } // namespace
 
-hipError_t mse_ppo_launch_grad_matrix(const MsePpoMatrixArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+hipError_t mse_ppo_launch_grad_matrix(const GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                       const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
                                       float *slabs, const int *control)

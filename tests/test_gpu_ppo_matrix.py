@@ -1,201 +1,79 @@
 """GPU: the matrix-core form of the PPO gradient (PPOLearner(arithmetic="matrix") -> mse_ppo_loss_grad_matrix ->
-k_ppo_grad_matrix) under the rule every other form is held to: float64 autograd from tests/ppo_reference.py, 4 x the error
-of torch's own float32 CPU evaluation recomputed each run, `stats_bound` for the statistics, bit-equal repeat calls
-(tests/ppo_checks.py: check_loss_grad).  Synthetic rows except where a rollout is named."""
+k_ppo_grad_matrix).  Section 0 names the cases both forms must satisfy (every shape and option, tile edges, the grid cap,
+index semantics, writes nothing else), whose bodies and parametrize lists tests/ppo_checks.py defines once; the rest is particular to this form: against
+the fma form, its gate, rollouts, update() and the default.  Synthetic rows except where a rollout is named."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+from tests import ppo_checks as P
 from tests import ppo_reference as R
-from tests.ppo_checks import DIM_MATRIX, DIMS, HP, check_loss_grad, cpu_rows, device_rows, make_policy
+from tests.ppo_checks import (DIMS, HP, ROWS_PER_GROUP, bits, check_loss_grad, cpu_rows, device_rows, group_cap, make_learner,
+                              make_policy, same_bits)
 
 pytestmark = pytest.mark.gpu
 
 MONO = DIMS["mono"]
-ROWS_PER_GROUP = 128  # include/mse.h, mse_ppo_loss_grad_matrix: a workgroup takes two tiles of 64 rows per pass
+FORM = "matrix"
 
 
-def _group_cap():
-    """include/mse.h, mse_ppo_loss_grad_matrix: min(ceil(batch / 128), 2 * CUs, 512) workgroups"""
-    import torch
-
-    return min(2 * torch.cuda.get_device_properties(0).multi_processor_count, 512)
-
-
-def _learner(D, A, seed, saturating=False, normalize=True, arithmetic="matrix"):
-    import marl_sortingenv_amd as M
-
-    pol, flat = make_policy(D, A, seed, saturating=saturating, precision="f32")
-    learner = M.PPOLearner(pol, normalize_advantage=normalize, arithmetic=arithmetic, **HP)
-    assert learner.arithmetic == arithmetic
-    return learner, flat
-
-
-def _bits(t):
-    import torch
-
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(a, b):
-    import torch
-
-    return torch.equal(_bits(a), _bits(b))
-
-
-# ---- 1. every shape and option --------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("saturating", [False, True])
-@pytest.mark.parametrize("normalize", [True, False])
-@pytest.mark.parametrize("masked", [True, False])
-@pytest.mark.parametrize("D,A", DIM_MATRIX)
+# ---- 0. what both forms must satisfy (tests/ppo_checks.py; tests/test_gpu_ppo_shapes.py runs the same with "fma") ---------
+@P.CASES_EVERY_SHAPE
 def test_every_shape_and_option(D, A, masked, normalize, saturating):
-    learner, flat = _learner(D, A, D * 100 + A, saturating=saturating, normalize=normalize)
-    obs, mask, mk, *rest = R.make_rows(D, A, 300, seed=11, flat=flat, masked=masked)  # four full tiles and a 44-row tail
-    _, _, stats = check_loss_grad(D, A, flat, learner, device_rows(obs, mk, *rest), None,
-                                  f"matrix {D}->{A} masked={masked} normalize={normalize} sat={saturating} B=300", normalize=normalize)
-    if not normalize:
-        assert stats[6:].tolist() == [0.0, 1.0]
+    P.every_shape_and_option(FORM, D, A, masked, normalize, saturating)
 
 
-# ---- 2. tile edges: both 32-row halves of a tile, a tail in each, an idle tile slot, a wave with no tile ---------------------
-@pytest.mark.parametrize("B", [1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 193])
-@pytest.mark.parametrize("D,A", [MONO, (32, 32)])
+@P.CASES_BATCH_EDGES
 def test_tile_edges(D, A, B):
-    import torch
-
-    learner, flat = _learner(D, A, 41)
-    n_rows = 321
-    obs, mask, mk, *rest = R.make_rows(D, A, n_rows, seed=B, flat=flat, masked=True)
-    data = device_rows(obs, mk, *rest)
-    perm = torch.randperm(n_rows, generator=torch.Generator().manual_seed(B))
-    for rows, name in ((None, "rows_dev=NULL"), (perm[:B], "permuted rows_dev")):
-        yard = None
-        if B <= 2:  # the largest float32 error over 64 evaluations on other rows is the yardstick
-            others = torch.arange(B, B + 64 * B) if rows is None else perm[B:B + 64 * B]
-            yard = others.reshape(64, B)
-        check_loss_grad(D, A, flat, learner, data, rows, f"matrix {D}->{A} B={B} {name}", yardstick_rows=yard, batch=B)
+    P.batch_edges(FORM, D, A, B)
 
 
-# ---- 3. the grid cap ----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def many_rows():
     D, A = MONO
     flat = R.random_flat(D, A, 43)
-    return flat, R.make_rows(D, A, ROWS_PER_GROUP * _group_cap() + 65, seed=5, flat=flat, masked=True)
+    return flat, R.make_rows(D, A, ROWS_PER_GROUP * group_cap() + 65, seed=5, flat=flat, masked=True)
 
 
-# B0 rows: every tile slot of the capped grid has one tile; one row more and the first wave takes a second tile with its
-# accumulators carried over, 65 more and both slots of workgroup 0 do
-@pytest.mark.parametrize("off", [-1, 0, 1, 65])
+@pytest.mark.parametrize("off", P.SLAB_CAP_OFFSETS)
 def test_grid_cap(many_rows, off):
-    D, A = MONO
-    flat, (obs, mask, mk, *rest) = many_rows
-    B = ROWS_PER_GROUP * _group_cap() + off
-    assert 0 < B <= obs.shape[0]
-    learner, _ = _learner(D, A, 43)
-    data = device_rows(obs[:B], mk[:B], *[t[:B] for t in rest])
-    check_loss_grad(D, A, flat, learner, data, None, f"matrix mono B={B} (B0{off:+d}, cap {_group_cap()})")
+    P.grid_cap(FORM, many_rows, ROWS_PER_GROUP * group_cap() + off, f"B0{off:+d}")
 
 
-# ---- 4. index semantics -------------------------------------------------------------------------------------------------------
-def _index_case(D, A, n_rows, seed):
-    learner, flat = _learner(D, A, 47)
-    obs, mask, mk, *rest = R.make_rows(D, A, n_rows, seed=seed, flat=flat, masked=True)
-    return learner, flat, [obs, mk, *rest]
-
-
-@pytest.mark.parametrize("D,A", [MONO, (32, 32)])
+@P.CASES_ROWS_REPEAT
 def test_rows_may_repeat_and_batch_may_exceed_n_rows(D, A):
-    import torch
-
-    n_rows = 100
-    learner, flat, cpu = _index_case(D, A, n_rows, 1)
-    rows = torch.randint(0, n_rows, (3 * n_rows,), generator=torch.Generator().manual_seed(2))
-    rows[:4] = 7
-    assert rows.unique().numel() < n_rows
-    check_loss_grad(D, A, flat, learner, device_rows(*cpu), rows, f"matrix {D}->{A} repeated rows, batch = 3 n_rows")
+    P.rows_may_repeat(FORM, D, A)
 
 
-@pytest.mark.parametrize("first", ["in range", "clamped pivot"])
-def test_rows_outside_the_rollout_are_clamped(first):
-    import torch
-
-    D, A = MONO
-    n_rows = 100
-    learner, flat, cpu = _index_case(D, A, n_rows, 3)
-    rows = torch.randperm(n_rows, generator=torch.Generator().manual_seed(4))[:80]
-    rows[[5, 17, 40, 79]] = torch.tensor([-5, n_rows, n_rows + 10 ** 9, -2 ** 62])
-    if first == "clamped pivot":  # rows[0] is the pivot of the advantage statistics
-        rows[0] = n_rows + 10 ** 9
-    clamped = rows.clamp(0, n_rows - 1)
-    check_loss_grad(D, A, flat, learner, device_rows(*cpu), rows, f"matrix rows outside [0, n_rows), first {first}",
-                    ref_args=[t[clamped] for t in cpu])
+@P.CASES_ROWS_OUTSIDE
+def test_rows_outside_the_rollout_are_clamped(D, A, first):
+    P.rows_outside_are_clamped(FORM, D, A, first)
 
 
-def test_actions_outside_the_head_are_clamped():
-    import torch
-
-    D, A = MONO
-    n_rows = 300
-    learner, flat, cpu = _index_case(D, A, n_rows, 5)
-    obs, mk, actions, *rest = cpu
-    mk = mk.clone()
-    bad = actions.clone()
-    bad[[3, 70, 150]] = -1
-    bad[[4, 71, 299]] = A + 3
-    bad[200] = 2 ** 31 - 1
-    bad[201] = -2 ** 31
-    clamped = bad.clamp(0, A - 1)
-    mk[torch.arange(n_rows), clamped.long()] = True  # the action clamped to is legal: the illegal ones have their own test
-    check_loss_grad(D, A, flat, learner, device_rows(obs, mk, bad, *rest), None, "matrix actions outside [0, A)",
-                    ref_args=[obs, mk, clamped, *rest])
+@P.CASES_ACTIONS_OUTSIDE
+def test_actions_outside_the_head_are_clamped(D, A):
+    P.actions_outside_are_clamped(FORM, D, A)
 
 
-def test_an_action_whose_mask_bit_is_zero():
-    """The reference is R.forward as it is: the logit is -1e8, so is the log-probability, the ratio is 0."""
-    import torch
-
-    D, A = MONO
-    n_rows = 300
-    learner, flat, cpu = _index_case(D, A, n_rows, 7)
-    obs, mk, actions, *rest = cpu
-    mk = mk.clone()
-    picked = [int(r) for r in torch.nonzero(actions != 0).squeeze(1)[[2, 9, 30]]]  # action 0 stays legal in every row
-    for r in picked:
-        mk[r, int(actions[r])] = False
-    _, _, stats = check_loss_grad(D, A, flat, learner, device_rows(obs, mk, actions, *rest), None,
-                                  f"matrix {len(picked)} rows with an illegal action")
-    assert float(stats[4]) > 1e5  # approx_kl carries the -1e8
+@P.CASES_ILLEGAL_ACTION
+def test_an_action_whose_mask_bit_is_zero(D, A):
+    P.illegal_action(FORM, D, A)
 
 
-# ---- 5. outputs and nothing else -----------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D,A", [MONO, (1, 1)])
+@P.CASES_BANDED
 def test_writes_its_outputs_and_nothing_else(D, A):
-    import torch
-
-    learner, flat = _learner(D, A, 53)
-    obs, mask, mk, *rest = R.make_rows(D, A, 300, seed=9, flat=flat, masked=True)
-    W, band, sentinel = flat.numel(), 64, 12345.0
-    gbuf = torch.full((W + 2 * band,), sentinel, device="cuda")
-    sbuf = torch.full((8 + 2 * band,), sentinel, device="cuda")
-    gbuf[band:band + W] = float("nan")
-    sbuf[band:band + 8] = float("nan")
-    check_loss_grad(D, A, flat, learner, device_rows(obs, mk, *rest), None, f"matrix {D}->{A} into banded buffers",
-                    grad_out=gbuf[band:band + W], stats_out=sbuf[band:band + 8])
-    for buf, n in ((gbuf, W), (sbuf, 8)):
-        assert bool((buf[:band] == sentinel).all()) and bool((buf[band + n:] == sentinel).all())
-        assert int(torch.isfinite(buf[band:band + n]).sum()) == n
+    P.writes_nothing_else(FORM, D, A)
 
 
-# ---- 6. against the "fma" form ------------------------------------------------------------------------------------------------
+# ---- 1. against the "fma" form ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["sort", "press", "mono"])
 def test_against_the_fma_form(kind):
     import torch
 
     D, A = DIMS[kind]
-    matrix, flat = _learner(D, A, 61)
-    fma, _ = _learner(D, A, 61, arithmetic="fma")
+    matrix, flat = make_learner(D, A, 61, arithmetic="matrix")
+    fma, _ = make_learner(D, A, 61, arithmetic="fma")
     obs, mask, mk, *rest = R.make_rows(D, A, 300, seed=21, flat=flat, masked=True)
     data = device_rows(obs, mk, *rest)
     out = {}
@@ -205,7 +83,7 @@ def test_against_the_fma_form(kind):
         out[name] = (g, stats)
     torch.cuda.synchronize()
     # the launches around the gradient are the same two kernels
-    assert _same_bits(out["matrix"][1][6:8], out["fma"][1][6:8])
+    assert same_bits(out["matrix"][1][6:8], out["fma"][1][6:8])
     # each form is within `allowed` of float64, so the two are within twice that of each other
     tail = (HP["clip_range"], HP["ent_coef"], HP["vf_coef"], True)
     g64, _ = R.loss_and_grad(flat, torch.float64, D, A, obs, mk, *rest, *tail)
@@ -216,12 +94,12 @@ def test_against_the_fma_form(kind):
     assert diff <= 2 * allowed
 
 
-# ---- 7. the gate ----------------------------------------------------------------------------------------------------------------
+# ---- 2. the gate ----------------------------------------------------------------------------------------------------------------
 def test_gate():
     import torch
 
     D, A = MONO
-    learner, flat = _learner(D, A, 67)
+    learner, flat = make_learner(D, A, 67, arithmetic="matrix")
     obs, mask, mk, *rest = R.make_rows(D, A, 300, seed=23, flat=flat, masked=True)
     data = device_rows(obs, mk, *rest)
     w = flat.cuda()
@@ -245,15 +123,15 @@ def test_gate():
     control = torch.zeros(2, dtype=torch.int32, device="cuda")
     g, s = call(control, 0.5 * kl / 1.5)
     assert control.tolist() == [1, 1]
-    assert _same_bits(g, g0) and _same_bits(s, s0)
+    assert same_bits(g, g0) and same_bits(s, s0)
     # open, a threshold above it: counted, not stopped
     control = torch.zeros(2, dtype=torch.int32, device="cuda")
     g, s = call(control, 2.0 * kl / 1.5)
     assert control.tolist() == [0, 1]
-    assert _same_bits(g, g0) and _same_bits(s, s0)
+    assert same_bits(g, g0) and same_bits(s, s0)
 
 
-# ---- 8. rollouts ---------------------------------------------------------------------------------------------------------------
+# ---- 3. rollouts ---------------------------------------------------------------------------------------------------------------
 def _rollout(kind, pol, n=256, K=4, seed=21):
     import marl_sortingenv_amd as M
 
@@ -278,7 +156,7 @@ def test_on_a_rollout(kind):
     check_loss_grad(D, A, flat, learner, data, perm, f"matrix {kind} rollout, 400 permuted rows")
 
 
-# ---- 9. update() ---------------------------------------------------------------------------------------------------------------
+# ---- 4. update() ---------------------------------------------------------------------------------------------------------------
 N_ENVS, K_STEPS, EPOCHS, BS, SEED = 256, 4, 2, 400, 5
 TOTAL = N_ENVS * K_STEPS
 M_UPDATE = EPOCHS * -(-TOTAL // BS)  # six minibatches: 400, 400, 224 rows per epoch
@@ -320,7 +198,7 @@ def _update_by_hand(hand, data, target_kl=None):
 
 def _assert_same_learner(a, b, label):
     for name in ("weights", "m", "v"):
-        assert _same_bits(getattr(a, name), getattr(b, name)), (label, name)
+        assert same_bits(getattr(a, name), getattr(b, name)), (label, name)
     assert a.step == b.step, label
 
 
@@ -343,7 +221,7 @@ def test_update_equals_the_hand_loop_and_follows_float64(update_rollout):
     torch.cuda.synchronize()
     assert (run, stopped) == (M_UPDATE, False) and learner.step == M_UPDATE
     _assert_same_learner(learner, hand, "update")
-    assert _same_bits(out["stats"], want_stats)
+    assert same_bits(out["stats"], want_stats)
     assert np.array_equal(pol.flat_weights(), learner.weights.cpu().numpy())
     # the float64 update on the same permutations, by test_update_end_to_end's rule
     cfg = dict(kind="mono", batch_size=BS, learning_rate=1e-3)
@@ -376,13 +254,13 @@ def test_update_with_target_kl_stops_where_the_hand_loop_stops(update_rollout):
     assert out["stopped"] is True and out["minibatches_run"] == j + 1
     _assert_same_learner(gated, hand, "gated update")
     assert gated.step == j  # Adam steps taken: the stopping minibatch took none
-    assert _same_bits(out["stats"][:j + 1], want_stats[:j + 1])
-    assert torch.count_nonzero(_bits(out["stats"][j + 1:])) == 0
+    assert same_bits(out["stats"][:j + 1], want_stats[:j + 1])
+    assert torch.count_nonzero(bits(out["stats"][j + 1:])) == 0
     assert gated.epochs_done == EPOCHS
     assert np.array_equal(pol.flat_weights().view(np.uint32), gated.weights.cpu().numpy().view(np.uint32))
 
 
-# ---- 10. the default -----------------------------------------------------------------------------------------------------------
+# ---- 5. the default -----------------------------------------------------------------------------------------------------------
 def test_the_default_is_the_fma_form():
     import torch
 
@@ -404,5 +282,5 @@ def test_the_default_is_the_fma_form():
                                          C.c_void_p(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     assert status == 0
-    assert _same_bits(g, want) and _same_bits(stats, want_stats)
+    assert same_bits(g, want) and same_bits(stats, want_stats)
     assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0.0
