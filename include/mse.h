@@ -466,6 +466,50 @@ int mse_ppo_loss_grad_matrix(int obs_dim, int n_actions, const float *weights_de
                              const mse_ppo_params *params, float *grad_out, float *stats_out, void *workspace,
                              void *stream, double target_kl, int32_t *control_dev /* NULL: no gate, target_kl unread */);
 
+/* SB3's clip_range_vf, and the one entry point that covers every form above: either arithmetic, gated or not, with or
+ * without value clipping.  The first 17 arguments are mse_ppo_loss_grad's; target_kl and control_dev are
+ * mse_ppo_loss_grad_matrix's (NULL: no gate, target_kl unread).
+ *   arithmetic     0: fmaf chains (k_ppo_grad), 1: matrix cores (k_ppo_grad_matrix)
+ *   old_values     f32[n_rows] or NULL: the value predictions the rollout was collected with, read at the rows `returns`
+ *                  is read at
+ *   clip_range_vf  read only with old_values; then it must be finite and > 0, also once rounded to float32
+ * old_values == NULL: no value clipping; the call is mse_ppo_loss_grad (arithmetic 0, no control block),
+ * mse_ppo_loss_grad_gated (0, control block) or mse_ppo_loss_grad_matrix (1): the same launches, the same bits.
+ * old_values != NULL: the critic's loss is that of the clipped prediction (PPO.train), float32, every operation rounded
+ * separately, c = (float)clip_range_vf:
+ *   d = value - old_value;  dc = min(max(d, -c), c);  vp = old_value + dc;  e = vp - returns
+ *   value_loss = mean(e^2) (stats_out[2], and the value term of stats_out[0]: of the clipped prediction, as SB3 logs them)
+ *   d loss / d value = vf_coef * 2 * e / batch where d == dc (torch.clamp passes the gradient on its closed range), else 0
+ * Nothing else differs: the policy network's gradient and stats_out[1], [3] .. [7] are bit-equal with and without
+ * old_values.  The gradient launch is a separate instantiation of the same kernel, so the unclipped launch is unchanged.
+ * Checks, all before any device call, in this order: a NaN target_kl beside a control block; then mse_ppo_loss_grad's
+ * (null arguments, dimensions, struct_size, batch, coefficients, workspace alignment); then arithmetic outside {0, 1};
+ * then, with old_values, a clip_range_vf that is not finite and > 0.  Each is MSE_ERR_INVALID_ARGUMENT
+ * (MSE_ERR_ALIGNMENT for the workspace).  Same workspace, same grid rule, equal inputs give bit-equal outputs. */
+int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                            float *stats_out, void *workspace, void *stream, double target_kl,
+                            int32_t *control_dev /* NULL: no gate */, int arithmetic /* 0 fma, 1 matrix */,
+                            const float *old_values /* f32[n_rows] or NULL */, double clip_range_vf);
+
+/* SB3's train/explained_variance: 1 - var(returns - values) / var(returns) over n rows (all K * N of a rollout), population
+ * variances, NaN when var(returns) is 0 (n = 1, constant returns).  csrc/mse_ppo_math.h specifies the arithmetic
+ * completely; in short: the differences returns - values are formed in double from the f32 inputs; sums and sums of
+ * squares are taken in double about a pivot (element 0) by min(256, ceil(n / 1024)) groups of 256 lanes, a fixed tree
+ * inside a group, the groups' partials added in index order; variances and their ratio in double; ONE rounding to f32 at
+ * the store.  No atomics: equal inputs give equal bits, and the host twin adds the same numbers in the same order, so
+ * device and host agree bit for bit.  values == returns gives exactly 1.
+ *   out_dev      f32[1], the only thing written beside the workspace
+ *   workspace    mse_explained_variance_workspace_bytes() bytes (8 KiB), 8-byte aligned, contents need not survive; a
+ *                workspace of mse_ppo_workspace_bytes is large enough and may be passed between two gradient calls
+ * Two small launches on `stream` (the partials, then one lane that adds them); nothing allocates or synchronises; the
+ * arguments (non-null, n >= 1, alignment) are checked before any device call.  The host form needs no device. */
+int64_t mse_explained_variance_workspace_bytes(void);
+int mse_explained_variance(int64_t n, const float *values, const float *returns, float *out_dev /* f32[1] */, void *workspace,
+                           void *stream);
+int mse_explained_variance_host(int64_t n, const float *values, const float *returns, float *out);
+
 /* The learner's minibatch shuffle: rows_out[j] = perm(seed, epoch, total, first + j) for j < count, where perm(seed, epoch,
  * total, .) is a bijection of [0, total) computed per element from its arguments alone (a keyed Feistel network with
  * cycle walking, 32-bit integer arithmetic; csrc/mse_ppo_math.h specifies it completely).  No generator and no state:

@@ -28,6 +28,7 @@ EXPORTS = [
     "mse_policy_read_image", "mse_policy_get_weights", "mse_ppo_loss_grad_gated", "mse_ppo_adam_step_gated",
     "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
     "mse_ppo_loss_grad_matrix",
+    "mse_ppo_loss_grad_vclip", "mse_explained_variance_workspace_bytes", "mse_explained_variance", "mse_explained_variance_host",
 ]
 
 _other_libs: dict = {}
@@ -148,6 +149,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_loss_grad_gated.argtypes = L.mse_ppo_loss_grad.argtypes + [C.c_double, vp]
     L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
     L.mse_ppo_loss_grad_matrix.argtypes = L.mse_ppo_loss_grad_gated.argtypes
+    L.mse_ppo_loss_grad_vclip.argtypes = L.mse_ppo_loss_grad_gated.argtypes + [C.c_int, vp, C.c_double]
+    L.mse_explained_variance_workspace_bytes.argtypes = []
+    L.mse_explained_variance_workspace_bytes.restype = i64
+    L.mse_explained_variance.argtypes = [i64, vp, vp, vp, vp, vp]
+    L.mse_explained_variance_host.argtypes = [i64, vp, vp, vp]
     L.mse_ppo_shuffle.argtypes = [i64, u64, u64, i64, i64, vp, vp]
     L.mse_ppo_shuffle_host.argtypes = [i64, u64, u64, i64, i64, vp]
     L.mse_episode_workspace_bytes.argtypes = []

@@ -1,6 +1,7 @@
 // The second half of PPO on the device: returns and advantages (mse_gae), the clipped-surrogate loss of one minibatch
-// with its gradient w.r.t. all weights (mse_ppo_loss_grad), clip_grad_norm_ + Adam (mse_ppo_adam_step) and the
-// counter-based permutation that orders an epoch's rows into minibatches (mse_ppo_shuffle, and its host twin).  The
+// with its gradient w.r.t. all weights (mse_ppo_loss_grad; with SB3's clip_range_vf, mse_ppo_loss_grad_vclip), clip_grad_norm_
+// + Adam (mse_ppo_adam_step), the counter-based permutation that orders an epoch's rows into minibatches (mse_ppo_shuffle, and
+// its host twin) and SB3's train/explained_variance of a rollout (mse_explained_variance, and its host twin).  The
 // per-row arithmetic lives in mse_ppo_math.h (host + device); this file holds the kernels and the C ABI.  gfx950 only.
 //
 // Gradient kernel (k_ppo_grad), DESIGN.md 4.12.  A workgroup is four waves: wave w works on the actor (w & 1 == 0) or
@@ -18,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "mse.h"
 #include "mse_host.h"
@@ -46,6 +48,48 @@ __global__ __launch_bounds__(256) void k_gae(int k_steps, long long n, const flo
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) gae_column(k_steps, n, i, rewards, values, episode_starts, last_values, last_dones, g, gl, adv_out, ret_out);
+}
+
+// ---- explained variance (mse_ppo_math.h specifies the sums and their order) ------------------------------------------------
+// partial[4 g + k]: sum k of group g.  Every lane reads element 0 for the pivots (one broadcast line).
+__global__ __launch_bounds__(256) void k_explained_variance_partial(long long n, const float *__restrict__ values,
+                                                                    const float *__restrict__ returns, double *__restrict__ partial)
+{
+    __shared__ double sh[4][kEvLanes];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    ev_lane_sums(n, (long long)blockIdx.x * kEvLanes + threadIdx.x, (long long)gridDim.x * kEvLanes, values, returns, acc);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int w = kEvLanes / 2; w > 0; w >>= 1) { // fixed tree
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) partial[4 * blockIdx.x + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// one lane adds the partials in index order and stores the one f32
+__global__ __launch_bounds__(64) void k_explained_variance_finish(long long n, int groups, const double *__restrict__ partial,
+                                                                  float *__restrict__ out)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int g = 0; g < groups; ++g) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sums[k] += partial[4 * g + k];
+    }
+    out[0] = (float)ev_from_sums(sums, n);
+}
+
+// the argument rules of both entry points; nullptr if they hold
+const char *explained_variance_args_error(int64_t n, const float *values, const float *returns, const float *out)
+{
+    if (values == nullptr || returns == nullptr || out == nullptr) return "null argument";
+    if (n < 1) return "n must be positive";
+    return nullptr;
 }
 
 // ---- advantage mean / std: partial sums of d = a - pivot and d^2 in double, one pair per workgroup -------------------
@@ -140,13 +184,14 @@ __device__ __forceinline__ void store_layer(float *out, const LayerAcc &L, int l
     }
 }
 
-template <int DP, int AP>
+// VCLIP: SB3's clip_range_vf (value_head_terms_clipped on old_values[row]); false never reads old_values
+template <int DP, int AP, bool VCLIP>
 __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__restrict__ weights, const long long *__restrict__ rows,
                                                   const float *__restrict__ obs, const uint8_t *__restrict__ mask,
                                                   const int *__restrict__ actions, const float *__restrict__ old_logp,
                                                   const float *__restrict__ adv, const float *__restrict__ ret,
                                                   const double *__restrict__ adv_partial, float *__restrict__ slabs,
-                                                  const int *__restrict__ control)
+                                                  const int *__restrict__ control, const float *__restrict__ old_values)
 {
     typedef Padded<DP, AP> PW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -217,7 +262,11 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
             float v[1];
             head_forward<1>(wl + PW::val_w, wl + PW::val_b, h2, v);
             float dv[1];
-            const float sq = value_head_terms(v[0], ret[row], G.P, inv_b, dv[0]);
+            float sq;
+            if constexpr (VCLIP)
+                sq = value_head_terms_clipped(v[0], old_values[row], ret[row], G.P, inv_b, dv[0]);
+            else
+                sq = value_head_terms(v[0], ret[row], G.P, inv_b, dv[0]);
             if (valid) st0 += sq;
             accumulate_layer(strip, lane, dv, h2, L3.w, L3.b);
             backprop<1>(wl + PW::val_w, dv, h2, dz);
@@ -399,19 +448,26 @@ const char *shuffle_args_error(int64_t total, int64_t first, int64_t count, cons
 template <int DP, int AP>
 void launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
                  const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
-                 const double *adv_partial, float *slabs, const int *control)
+                 const double *adv_partial, float *slabs, const int *control, const float *old_values)
 {
     const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
-    hipLaunchKernelGGL((k_ppo_grad<DP, AP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
-                       old_logp, adv, ret, adv_partial, slabs, control);
+    if (old_values != nullptr)
+        hipLaunchKernelGGL((k_ppo_grad<DP, AP, true>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                           old_logp, adv, ret, adv_partial, slabs, control, old_values);
+    else
+        hipLaunchKernelGGL((k_ppo_grad<DP, AP, false>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                           old_logp, adv, ret, adv_partial, slabs, control, old_values);
 }
 
-// mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated and mse_ppo_loss_grad_matrix (matrix: the gradient launch is
-// k_ppo_grad_matrix of mse_ppo_matrix.hip; everything around it is the same); `who` names the entry point in messages
+// mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated, mse_ppo_loss_grad_matrix (matrix: the gradient launch is
+// k_ppo_grad_matrix of mse_ppo_matrix.hip; everything around it is the same) and mse_ppo_loss_grad_vclip (old_values != NULL:
+// the gradient launch is the VCLIP instantiation with clip_range_vf, which the entry point has checked); `who` names the
+// entry point in messages
 int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
               int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
               const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out, float *stats_out,
-              void *workspace, void *stream, Gate gate, bool matrix = false)
+              void *workspace, void *stream, Gate gate, int arithmetic = 0, const float *old_values = nullptr,
+              double clip_range_vf = 0.0)
 {
     auto fail = [who](int status, const char *why) { return mse_internal_fail(status, (std::string(who) + ": " + why).c_str()); };
     if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
@@ -427,6 +483,11 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
         return fail(MSE_ERR_INVALID_ARGUMENT, "bad clip_range / ent_coef / vf_coef");
     if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
         return fail(MSE_ERR_ALIGNMENT, "workspace must be 16-byte aligned");
+    // what only mse_ppo_loss_grad_vclip can get wrong, after everything above: the arithmetic, then the clipping range
+    if (arithmetic != 0 && arithmetic != 1) return fail(MSE_ERR_INVALID_ARGUMENT, "arithmetic must be 0 (fma) or 1 (matrix)");
+    const float c_vf = old_values != nullptr ? (float)clip_range_vf : 0.0f; // without old_values clip_range_vf is not read
+    if (old_values != nullptr && !(std::isfinite(clip_range_vf) && c_vf > 0.0f && std::isfinite(c_vf)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "clip_range_vf must be finite and > 0 (as a float32) with old_values");
     const int cus = cu_count();
     if (cus <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -434,7 +495,7 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
     float *slabs = reinterpret_cast<float *>(adv_partial + 2 * kMaxAdvPartials);
     const long long *rows = reinterpret_cast<const long long *>(rows_dev);
     GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch, 0,
-               Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage}};
+               Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage, c_vf}};
     if (params->normalize_advantage != 0 && batch > 1) {
         long long g1 = (batch + 1023) / 1024;
         G.n_adv_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
@@ -443,13 +504,14 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
     }
     const int n_slabs = (int)grad_groups(batch, cus);
     hipError_t e = hipSuccess;
-    if (matrix) {
+    if (arithmetic == 1) {
         e = mse_ppo_launch_grad_matrix(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial,
-                                       slabs, gate.control);
+                                       slabs, gate.control, old_values);
     } else {
         // four shapes, chosen in mse_ppo_math.h: Env_1 (13 -> 2), Env_2 (16 -> 11), Env_3 (29 -> 22) and the general one
-#define MSE_PPO_LAUNCH(DP, AP) \
-    launch_grad<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, gate.control)
+#define MSE_PPO_LAUNCH(DP, AP)                                                                                                     \
+    launch_grad<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, \
+                        gate.control, old_values)
         MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH);
 #undef MSE_PPO_LAUNCH
     }
@@ -538,7 +600,63 @@ int mse_ppo_loss_grad_matrix(int obs_dim, int n_actions, const float *weights_de
         return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_matrix: target_kl is NaN");
     return loss_grad("mse_ppo_loss_grad_matrix", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
                      advantages, returns, params, grad_out, stats_out, workspace, stream,
-                     control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, true);
+                     control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, 1);
+}
+
+int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                            float *stats_out, void *workspace, void *stream, double target_kl, int32_t *control_dev, int arithmetic,
+                            const float *old_values, double clip_range_vf)
+{
+    if (control_dev != nullptr && target_kl != target_kl)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_loss_grad_vclip: target_kl is NaN");
+    return loss_grad("mse_ppo_loss_grad_vclip", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
+                     advantages, returns, params, grad_out, stats_out, workspace, stream,
+                     control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, arithmetic, old_values,
+                     clip_range_vf);
+}
+
+int64_t mse_explained_variance_workspace_bytes(void) { return (int64_t)(kEvMaxGroups * 4 * sizeof(double)); }
+
+int mse_explained_variance(int64_t n, const float *values, const float *returns, float *out_dev, void *workspace, void *stream)
+{
+    if (const char *why = explained_variance_args_error(n, values, returns, out_dev))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, (std::string("mse_explained_variance: ") + why).c_str());
+    if (workspace == nullptr) return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_explained_variance: null workspace");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 7u) != 0)
+        return mse_internal_fail(MSE_ERR_ALIGNMENT, "mse_explained_variance: workspace must be 8-byte aligned");
+    if (cu_count() <= 0)
+        return mse_internal_fail(MSE_ERR_NO_DEVICE, "mse_explained_variance: no HIP device (mse_explained_variance_host runs on the CPU)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *partial = static_cast<double *>(workspace);
+    const int groups = ev_groups((long long)n);
+    hipLaunchKernelGGL(k_explained_variance_partial, dim3((unsigned)groups), dim3(kEvLanes), 0, s, (long long)n, values, returns, partial);
+    hipLaunchKernelGGL(k_explained_variance_finish, dim3(1), dim3(64), 0, s, (long long)n, groups, partial, out_dev);
+    if (hipGetLastError() != hipSuccess) return mse_internal_fail(MSE_ERR_HIP, "mse_explained_variance: kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_explained_variance_host(int64_t n, const float *values, const float *returns, float *out)
+{
+    if (const char *why = explained_variance_args_error(n, values, returns, out))
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, (std::string("mse_explained_variance_host: ") + why).c_str());
+    const int groups = ev_groups((long long)n);
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};
+    std::vector<double> lanes(4 * kEvLanes);
+    for (int g = 0; g < groups; ++g) { // the kernel's order: a lane's elements, the tree over the lanes, the groups in index order
+        for (int t = 0; t < kEvLanes; ++t) {
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            ev_lane_sums((long long)n, (long long)g * kEvLanes + t, (long long)groups * kEvLanes, values, returns, acc);
+            for (int k = 0; k < 4; ++k) lanes[k * kEvLanes + t] = acc[k];
+        }
+        for (int w = kEvLanes / 2; w > 0; w >>= 1)
+            for (int t = 0; t < w; ++t)
+                for (int k = 0; k < 4; ++k) lanes[k * kEvLanes + t] += lanes[k * kEvLanes + t + w];
+        for (int k = 0; k < 4; ++k) sums[k] += lanes[k * kEvLanes];
+    }
+    out[0] = (float)ev_from_sums(sums, (long long)n);
+    return MSE_OK;
 }
 
 int mse_ppo_adam_step(int64_t n_weights, float *weights, const float *grad, float *m, float *v, int64_t step, double lr,

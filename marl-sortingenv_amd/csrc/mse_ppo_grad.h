@@ -146,7 +146,10 @@ __device__ __forceinline__ void store_slab_stats(float *s, const float *misc)
 
 // mse_ppo_matrix.hip: enqueues k_ppo_grad_matrix on `n_slabs` workgroups; it writes what k_ppo_grad writes.  Returns
 // hipSuccess or the error that kept the kernel from being launched.
+// old_values (f32[n_rows] or NULL), here and in launch_grad of mse_ppo.hip: non-NULL launches the VCLIP = true instantiation
+// of the kernel, whose critic reads old_values at the row it reads `ret` at and calls value_head_terms_clipped with
+// G.P.clip_range_vf; NULL launches VCLIP = false, which never reads the argument and is the kernel as it was without it.
 hipError_t mse_ppo_launch_grad_matrix(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                       const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
-                                      float *slabs, const int *control);
+                                      float *slabs, const int *control, const float *old_values);

@@ -7,6 +7,8 @@
 //   policy_head_terms   MaskableCategorical (illegal logits at -1e8), log-prob / entropy, the clipped surrogate of
 //                       MaskablePPO.train and the gradient of  policy_loss + ent_coef * entropy_loss  w.r.t. the logits
 //   value_head_terms    F.mse_loss(returns, values) and its gradient
+//   value_head_terms_clipped   the same for PPO.train's clip_range_vf: values clipped to within c of the rollout's
+//   ev_groups / ev_lane_sums / ev_from_sums   explained_variance(values, returns), the sums and their order in full
 //   hidden_forward / head_forward / backprop            the 2 x 32 tanh MLP and the deltas of its layers
 // and, restating nothing (SB3 shuffles with numpy's generator):
 //   shuffle_key / shuffle_index   the counter-based permutation of an epoch's rows, specified in full where it is defined
@@ -32,6 +34,7 @@ constexpr float kMaskedLogit = -1e8f; // sb3_contrib MaskableCategorical / mse_p
 struct Params {
     float clip_range, ent_coef, vf_coef;
     int normalize_advantage;
+    float clip_range_vf; // trailing, so Params{clip, ent, vf, norm} leaves it 0 = off; read by value_head_terms_clipped only
 };
 
 // ---- GAE ------------------------------------------------------------------------------------------------------------
@@ -355,6 +358,69 @@ MSE_PPO_HD float value_head_terms(float value, float ret, const Params &P, float
     const float e = value - ret;
     dv = P.vf_coef * 2.0f * e * inv_b;
     return e * e;
+}
+
+// SB3's clip_range_vf (PPO.train: values_pred = old_values + clamp(values - old_values, -c, c), then F.mse_loss(returns,
+// values_pred)), c = P.clip_range_vf > 0, every operation rounded separately:
+//   d = value - old_value;  dc = min(max(d, -c), c);  vp = old_value + dc;  e = vp - returns
+// -> e * e, the squared error of the CLIPPED prediction; dv = d/d value of vf_coef * e^2 * inv_b, which is that of
+// value_head_terms where the clamp passes the gradient (d == dc: torch.clamp's closed range) and 0 where it clips.
+MSE_PPO_HD float value_head_terms_clipped(float value, float old_value, float ret, const Params &P, float inv_b, float &dv)
+{
+    const float c = P.clip_range_vf;
+    const float d = value - old_value;
+    const float dc = fminf(fmaxf(d, -c), c);
+    const float vp = old_value + dc;
+    const float e = vp - ret;
+    dv = d == dc ? P.vf_coef * 2.0f * e * inv_b : 0.0f;
+    return e * e;
+}
+
+// ---- explained variance: SB3's explained_variance(values, returns) = 1 - var(returns - values) / var(returns) -----------
+// Population variances over all n rows, NaN when var(returns) is 0 (n = 1, constant returns).  Specified in full, so that the
+// kernels (mse_ppo.hip: k_explained_variance_partial, k_explained_variance_finish) and mse_explained_variance_host add the same
+// numbers in the same order and agree bit for bit.  All arithmetic is in double, every operation rounded separately:
+//   r_i = (double)returns[i],  d_i = (double)returns[i] - (double)values[i]           (formed in double from the f32 inputs)
+//   pivots  pr = r_0,  pd = d_0;   a_i = r_i - pr,  b_i = d_i - pd
+//   groups  G = ev_groups(n) = min(kEvMaxGroups, ceil(n / 1024)), each of kEvLanes = 256 lanes;  lane t of group g adds, in
+//           ascending i, the elements  i = 256 g + t + 256 G k  (k = 0, 1, ..):  four sums  sum a, sum a^2, sum b, sum b^2
+//   tree    within a group, for w = 128, 64, .. 1:  lane t < w adds lane t + w's four sums to its own; lane 0 holds partial g
+//   finish  the G partials are added in index order g = 0 .. G - 1, starting from 0  ->  Sa, Qa, Sb, Qb
+//           var_r = (Qa - Sa * Sa / n) / n,  var_d = (Qb - Sb * Sb / n) / n          (n converted to double)
+//           ev = var_r > 0 ? 1 - var_d / var_r : NaN;   the ONE rounding to f32 is the store of (float)ev
+// The pivots keep the sums of squares small beside a mean offset; values == returns gives b_i = 0 and exactly 1.
+constexpr int kEvLanes = 256;
+constexpr int kEvMaxGroups = 256;
+constexpr int kEvRowsPerGroup = 1024; // rows per group below the cap: four trips of a lane
+
+MSE_PPO_HD int ev_groups(long long n)
+{
+    const long long g = (n + kEvRowsPerGroup - 1) / kEvRowsPerGroup;
+    return (int)(g > kEvMaxGroups ? kEvMaxGroups : g);
+}
+
+// one lane's four sums: acc[0..3] += over i = first, first + stride, .. < n
+MSE_PPO_HD void ev_lane_sums(long long n, long long first, long long stride, const float *values, const float *returns, double (&acc)[4])
+{
+    const double pr = (double)returns[0], pd = (double)returns[0] - (double)values[0];
+    for (long long i = first; i < n; i += stride) {
+        const double r = (double)returns[i];
+        const double a = r - pr;
+        const double b = (r - (double)values[i]) - pd;
+        acc[0] += a;
+        acc[1] += a * a;
+        acc[2] += b;
+        acc[3] += b * b;
+    }
+}
+
+// sums[0..3] = Sa, Qa, Sb, Qb -> the explained variance in double
+MSE_PPO_HD double ev_from_sums(const double (&sums)[4], long long n)
+{
+    const double dn = (double)n;
+    const double var_r = (sums[1] - sums[0] * sums[0] / dn) / dn;
+    const double var_d = (sums[3] - sums[2] * sums[2] / dn) / dn;
+    return var_r > 0.0 ? 1.0 - var_d / var_r : (double)NAN;
 }
 
 MSE_PPO_HD float normalized_advantage(float a, float mean, float std) { return (a - mean) / (std + 1e-8f); }

@@ -154,13 +154,15 @@ __device__ __forceinline__ void store_value_head(float *out, const LayerGrad &L,
     if (lane == 0) out[b_off] = b;
 }
 
-template <int DP, int AP>
+// VCLIP: SB3's clip_range_vf (value_head_terms_clipped on old_values[row]); false never reads old_values
+template <int DP, int AP, bool VCLIP>
 __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float *__restrict__ weights,
                                                          const long long *__restrict__ rows, const float *__restrict__ obs,
                                                          const uint8_t *__restrict__ mask, const int *__restrict__ actions,
                                                          const float *__restrict__ old_logp, const float *__restrict__ adv,
                                                          const float *__restrict__ ret, const double *__restrict__ adv_partial,
-                                                         float *__restrict__ slabs, const int *__restrict__ control)
+                                                         float *__restrict__ slabs, const int *__restrict__ control,
+                                                         const float *__restrict__ old_values)
 {
     constexpr int KS1 = DP / 2;          // k-steps of the first layer: units 0 .. DP - 1
     constexpr int KSA = ksteps_for(AP);  // k-steps of the head's back-propagation: actions 0 .. AP - 1
@@ -329,7 +331,11 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
 #pragma unroll
                 for (int r = 0; r < 16; ++r) part = fmaf(vw[r], h2[t][r], part);
                 const float value = halves_sum(part) + vb;
-                const float sq = value_head_terms(value, ret[row_t[t]], G.P, inv_b_t[t], dv[t]);
+                float sq;
+                if constexpr (VCLIP)
+                    sq = value_head_terms_clipped(value, old_values[row_t[t]], ret[row_t[t]], G.P, inv_b_t[t], dv[t]);
+                else
+                    sq = value_head_terms(value, ret[row_t[t]], G.P, inv_b_t[t], dv[t]);
                 if (valid_t[t] && h == t) st0 += sq; // both halves hold the row: half t counts it
                 // the head's weight gradient, one output wide, stays here too: L3.w[r] is this lane's share (column j of
                 // both column tiles) of d loss / d val_w[mat_row_of(r, h)], summed over the half's lanes at the end
@@ -395,10 +401,10 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
     if (tid == 0) store_slab_stats(slab + F.total, misc);
 }
 
-template <int DP, int AP>
+template <int DP, int AP, bool VCLIP>
 hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
                   const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
-                  const double *adv_partial, float *slabs, const int *control)
+                  const double *adv_partial, float *slabs, const int *control, const float *old_values)
 {
     constexpr size_t lds = (size_t)kLdsFloats * sizeof(float);
     // the image and the four strips take more than the 64 KB a launch gets unasked
@@ -406,13 +412,13 @@ hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *we
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorNoDevice;
     if (dev < 0 || dev >= 64 || !allowed[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad_matrix<DP, AP>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad_matrix<DP, AP, VCLIP>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((k_ppo_grad_matrix<DP, AP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
-                       old_logp, adv, ret, adv_partial, slabs, control);
+    hipLaunchKernelGGL((k_ppo_grad_matrix<DP, AP, VCLIP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
+                       actions, old_logp, adv, ret, adv_partial, slabs, control, old_values);
     return hipGetLastError();
 }
 
@@ -421,12 +427,16 @@ hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *we
 hipError_t mse_ppo_launch_grad_matrix(const GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                       const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
-                                      float *slabs, const int *control)
+                                      float *slabs, const int *control, const float *old_values)
 {
     hipError_t e = hipErrorInvalidValue;
     // the four padded shapes of k_ppo_grad, chosen by the same function
-#define MSE_PPO_MATRIX_LAUNCH(DP, AP) \
-    e = launch<DP, AP>(G, n_slabs, stream, weights, rows, obs, mask, actions, old_logp, adv, ret, adv_partial, slabs, control)
+#define MSE_PPO_MATRIX_LAUNCH(DP, AP)                                                                                                \
+    e = old_values != nullptr                                                                                                        \
+            ? launch<DP, AP, true>(G, n_slabs, stream, weights, rows, obs, mask, actions, old_logp, adv, ret, adv_partial, slabs,   \
+                                   control, old_values)                                                                              \
+            : launch<DP, AP, false>(G, n_slabs, stream, weights, rows, obs, mask, actions, old_logp, adv, ret, adv_partial, slabs,  \
+                                    control, old_values)
     MSE_PPO_DISPATCH(select_grad_shape(G.D, G.A), MSE_PPO_MATRIX_LAUNCH);
 #undef MSE_PPO_MATRIX_LAUNCH
     return e;

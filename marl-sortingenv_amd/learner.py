@@ -8,13 +8,17 @@ without a host synchronisation; the new weights go back into the policy the roll
 `target_kl` early stop is a flag on the device that the gated entry points read (`mse_ppo_loss_grad_gated`).  PyTorch is plumbing (device memory, the stream, the seeded permutation); no torch op
 computes anything on this path, and there is no CPU fallback.  With `shuffle="device"` the permutation is a kernel too
 (`mse_ppo_shuffle`, a counter-based function of seed and epoch that `PPOLearner.permutation` replays on the host).
+SB3's `clip_range_vf` is a second instantiation of either gradient kernel (`mse_ppo_loss_grad_vclip`), its schedules are
+host arithmetic on `progress_remaining` (`resolve_schedule`), and `train/explained_variance` is one more small kernel per
+update (`mse_explained_variance`).
 `learn` can report the reference's unit, cumulative reward per episode (episodes.py): SB3's `rollout/ep_rew_mean` from an
 `EpisodeStats` over the training rollouts, and `EvalCallback`'s periodic `evaluate_policy` with the best weights kept.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+import math
+from typing import Callable, Optional, Union
 
 import torch
 
@@ -30,6 +34,21 @@ def _ptr(x):
 
 def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+Schedule = Union[float, Callable[[float], float]]
+
+
+def resolve_schedule(value: Schedule, progress_remaining: float, name: str = "value", allow_zero: bool = False) -> float:
+    """SB3's schedule convention, with no device in it: `value` is a number, or a function of `progress_remaining` (1 at
+    the start of training, 0 at its end) that is called with it.  -> the value as a Python float.  A result that is not
+    finite or not positive is refused (ValueError naming `name`); allow_zero=True admits 0, which a linear decay of
+    `learning_rate` or `clip_range` reaches in its last update (`clip_range_vf` must stay above 0: 0 would mean "off")."""
+    v = float(value(float(progress_remaining)) if callable(value) else value)
+    if not math.isfinite(v) or v < 0.0 or (v == 0.0 and not allow_zero):
+        raise ValueError(f"{name} must be finite and {'>= 0' if allow_zero else '> 0'}, not {v!r} "
+                         f"(progress_remaining = {float(progress_remaining)!r})")
+    return v
 
 
 def compute_gae(data: dict, gamma: float = 0.99, gae_lambda: float = 0.95) -> dict:
@@ -80,13 +99,24 @@ class PPOLearner:
 
     `arithmetic="fma"` (the default) forms the gradient's products as fmaf chains on the vector unit
     (`mse_ppo_loss_grad`); `"matrix"` forms them on the f32 matrix cores (`mse_ppo_loss_grad_matrix`): the same per-row
-    arithmetic, sums in another order, so the two agree within rounding and each is reproducible bit for bit."""
+    arithmetic, sums in another order, so the two agree within rounding and each is reproducible bit for bit.
 
-    def __init__(self, policy: MlpPolicy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
-                 gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: float = 0.2, ent_coef: float = 0.0,
+    `clip_range_vf` (SB3's; None = off): the value loss is that of `old + clamp(value - old, -c, c)` with `old` the
+    rollout's `data["values"]`; every `loss_grad` then goes through `mse_ppo_loss_grad_vclip`, with either arithmetic,
+    gated or not.  With None `loss_grad` calls exactly what it called without the argument.
+
+    `learning_rate`, `clip_range` and `clip_range_vf` may each be a function of `progress_remaining` (SB3's schedules;
+    `resolve_schedule`).  `progress_remaining` (1.0 until set) is the progress used: `update(data, progress_remaining=p)`
+    sets it, `learn` sets it to `1 - (it + 1) / iterations` before update `it` - SB3's order, in which `num_timesteps`
+    has already counted the rollout about to be trained on, so the last update of a linear schedule runs at 0.  The three
+    are evaluated once at the top of each `update()` into `learning_rate` (the `lr` of the Adam launches), `clip_range`
+    (written into `params`) and `clip_range_vf`.  With plain numbers nothing is evaluated and nothing changes."""
+
+    def __init__(self, policy: MlpPolicy, learning_rate: Schedule = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
+                 gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: Schedule = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
                  seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None,
-                 arithmetic: str = "fma"):
+                 arithmetic: str = "fma", clip_range_vf: Optional[Schedule] = None):
         if shuffle not in ("cpu", "device"):
             raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
         if weight_sync not in ("host", "device"):
@@ -96,6 +126,16 @@ class PPOLearner:
         self.weight_sync = weight_sync
         self.arithmetic = arithmetic
         self.target_kl = None if target_kl is None else float(target_kl)
+        # a callable is kept as the schedule and evaluated at progress 1 for now; update() re-evaluates it
+        self.progress_remaining = 1.0
+        self.schedules = {name: v for name, v in (("learning_rate", learning_rate), ("clip_range", clip_range),
+                                                  ("clip_range_vf", clip_range_vf)) if callable(v)}
+        if "learning_rate" in self.schedules:
+            learning_rate = resolve_schedule(learning_rate, 1.0, "learning_rate", allow_zero=True)
+        if "clip_range" in self.schedules:
+            clip_range = resolve_schedule(clip_range, 1.0, "clip_range", allow_zero=True)
+        self.clip_range = float(clip_range)
+        self.clip_range_vf = None if clip_range_vf is None else resolve_schedule(clip_range_vf, 1.0, "clip_range_vf")
         self.policy, self.L = policy, policy.L
         self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
@@ -130,7 +170,8 @@ class PPOLearner:
         """One `mse_ppo_loss_grad` on the flattened rollout in `data` (which holds advantages / returns); returns the
         gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1.
         control: i32[2] device tensor {stopped, minibatches_run}: `mse_ppo_loss_grad_gated` with `target_kl` instead.
-        With `arithmetic="matrix"` both go to `mse_ppo_loss_grad_matrix`."""
+        With `arithmetic="matrix"` both go to `mse_ppo_loss_grad_matrix`.  With `clip_range_vf` set, all of them go to
+        `mse_ppo_loss_grad_vclip` with `data["values"]` (f32[K, N], contiguous) as the old values."""
         p = self.policy
         obs = data["observations"]
         n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
@@ -143,8 +184,16 @@ class PPOLearner:
         args = (p.obs_dim, p.n_actions, _ptr(w), n_rows, _ptr(rows), int(batch), _ptr(obs), _ptr(mask), _ptr(data["actions"]),
                 _ptr(data["log_probs"]), _ptr(data["advantages"]), _ptr(data["returns"]), C.byref(self.params), _ptr(g),
                 _ptr(stats_out), _ptr(self.workspace), _stream(self.device))
+        old = None
+        if self.clip_range_vf is not None:
+            old = data["values"]
+            if old.dtype != torch.float32 or not old.is_contiguous() or old.numel() != n_rows or old.device != obs.device:
+                raise ValueError("clip_range_vf needs data['values']: contiguous f32, one per rollout row, on the rollout's device")
         with torch.cuda.device(self.device):
-            if self.arithmetic == "matrix":
+            if old is not None:
+                check(self.L.mse_ppo_loss_grad_vclip(*args, float(target_kl), _ptr(control), 1 if self.arithmetic == "matrix" else 0,
+                                                     _ptr(old), float(self.clip_range_vf)))
+            elif self.arithmetic == "matrix":
                 check(self.L.mse_ppo_loss_grad_matrix(*args, float(target_kl), _ptr(control)))
             elif control is None:
                 check(self.L.mse_ppo_loss_grad(*args))
@@ -187,14 +236,44 @@ class PPOLearner:
         self.epochs_done += 1
         return self._perm
 
-    def update(self, data: dict) -> dict:
+    def _resolve_schedules(self) -> None:
+        """What SB3 does at the top of train(): the scheduled values at `progress_remaining`, once per update."""
+        p = self.progress_remaining
+        if "learning_rate" in self.schedules:
+            self.learning_rate = resolve_schedule(self.schedules["learning_rate"], p, "learning_rate", allow_zero=True)
+        if "clip_range" in self.schedules:
+            self.clip_range = resolve_schedule(self.schedules["clip_range"], p, "clip_range", allow_zero=True)
+            self.params.clip_range = self.clip_range
+        if "clip_range_vf" in self.schedules:
+            self.clip_range_vf = resolve_schedule(self.schedules["clip_range_vf"], p, "clip_range_vf")
+
+    def explained_variance(self, data: dict, out: torch.Tensor) -> None:
+        """One `mse_explained_variance` over all rows of `data["values"]` / `data["returns"]` into `out` (f32[1], device),
+        on the current stream, with the learner's workspace (free between two gradient calls, and large enough)."""
+        dev = data["returns"].device
+        values = data["values"].to(device=dev, dtype=torch.float32).contiguous()
+        returns = data["returns"]
+        if values.numel() != returns.numel() or returns.dtype != torch.float32 or not returns.is_contiguous():
+            raise ValueError("values and returns must be f32 of one size, returns contiguous")
+        with torch.cuda.device(self.device):
+            check(self.L.mse_explained_variance(returns.numel(), _ptr(values), _ptr(returns), _ptr(out), _ptr(self.workspace),
+                                                _stream(self.device)))
+
+    def update(self, data: dict, progress_remaining: Optional[float] = None, explained_variance: bool = False) -> dict:
         """GAE, then n_epochs passes over a permutation of the K * N rows (shuffle="cpu": seeded on the CPU and copied to
         the device once per epoch; shuffle="device": one `mse_ppo_shuffle` launch per epoch; the last minibatch of an
         epoch may be short), one loss_grad + adam_step per minibatch without a host
         synchronisation, then the weights' hand-over to the policy (`weight_sync`).  Returns {"stats":
         f32[n_minibatches, 8] (device; columns STAT_NAMES), "mean": {name: float}}.
         With `target_kl` the result gains "stopped" (bool) and "minibatches_run" (int): "mean" is over the first
-        minibatches_run rows of "stats", the rows after them stay zero."""
+        minibatches_run rows of "stats", the rows after them stay zero.
+        progress_remaining: sets `self.progress_remaining` first; the schedules are then evaluated once, here.
+        explained_variance=True: one `mse_explained_variance` over the rollout's values / returns behind GAE and before
+        the first minibatch; its f32 comes to the host in the copy that brings the statistics, and the result gains
+        "explained_variance" (SB3's train/explained_variance; NaN when the returns are constant)."""
+        if progress_remaining is not None:
+            self.progress_remaining = float(progress_remaining)
+        self._resolve_schedules()
         compute_gae(data, self.gamma, self.gae_lambda)
         K, n = data["rewards"].shape
         total = K * n
@@ -203,9 +282,15 @@ class PPOLearner:
         per_epoch = (total + bs - 1) // bs
         n_mb = self.n_epochs * per_epoch
         gated = self.target_kl is not None
-        if gated:  # statistics and control block in one buffer, so that one copy brings both to the host
-            buf = torch.zeros(n_mb * 8 + 2, dtype=torch.float32, device=self.device)
-            stats, control = buf[:n_mb * 8].view(n_mb, 8), buf[n_mb * 8:].view(torch.int32)
+        ev = None
+        if gated or explained_variance:  # statistics, control block and explained variance in one buffer: one copy brings all
+            n_ctl, n_ev = (2 if gated else 0), (1 if explained_variance else 0)
+            buf = torch.zeros(n_mb * 8 + n_ctl + n_ev, dtype=torch.float32, device=self.device)
+            stats = buf[:n_mb * 8].view(n_mb, 8)
+            control = buf[n_mb * 8:n_mb * 8 + n_ctl].view(torch.int32) if gated else None
+            if explained_variance:
+                ev = buf[n_mb * 8 + n_ctl:]
+                self.explained_variance(data, ev)
         else:
             stats, control = torch.zeros((n_mb, 8), dtype=torch.float32, device=self.device), None
         step0 = self.step
@@ -225,18 +310,25 @@ class PPOLearner:
                 i += 1
         self._hand_over()
         if not gated:
-            mean = stats.mean(dim=0).cpu().tolist()
+            if ev is None:
+                mean = stats.mean(dim=0).cpu().tolist()
+                self.policy.sync()
+                return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+            host = torch.cat((stats.mean(dim=0), ev)).cpu().tolist()  # still one copy
             self.policy.sync()
-            return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+            return {"stats": stats, "mean": dict(zip(STAT_NAMES, host[:8])), "explained_variance": host[8]}
         host = buf.cpu()
         self.policy.sync()
-        stopped, run = (int(x) for x in host[n_mb * 8:].view(torch.int32))
+        stopped, run = (int(x) for x in host[n_mb * 8:n_mb * 8 + 2].view(torch.int32))
         self.step = step0 + run - (1 if stopped else 0)  # the stopping minibatch took no step, nor did any after it
         mean = host[:n_mb * 8].view(n_mb, 8)[:run].mean(dim=0).tolist()
-        return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean)), "stopped": bool(stopped), "minibatches_run": run}
+        out = {"stats": stats, "mean": dict(zip(STAT_NAMES, mean)), "stopped": bool(stopped), "minibatches_run": run}
+        if ev is not None:
+            out["explained_variance"] = float(host[n_mb * 8 + 2])
+        return out
 
     def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
-              eval_freq: int = 0, n_eval_episodes: int = 10) -> list:
+              eval_freq: int = 0, n_eval_episodes: int = 10, explained_variance: bool = False) -> list:
         """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
         mean reward per env-step under "reward" (and, with `target_kl`, the update's "stopped" and "minibatches_run").
         episode_stats=True: each record gains `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in
@@ -246,7 +338,10 @@ class PPOLearner:
         eval_freq-th iteration gains `eval_mean_reward`, `eval_std_reward` from `evaluate_policy(eval_collector,
         n_eval_episodes)`; the best mean so far is kept in `best_mean_reward` with a device copy of the weights in
         `best_weights` (`restore_best()` loads them back).  With the defaults the records and the device work are
-        what they were without these arguments."""
+        what they were without these arguments.
+        Before update `it` `progress_remaining` becomes `1 - (it + 1) / iterations`.  A record gains `learning_rate` and
+        `clip_range` (the values that update used) when either is a schedule, `clip_range_vf` when it is set, and
+        `explained_variance` with explained_variance=True."""
         from .episodes import EpisodeStats, evaluate_policy
 
         evaluating = eval_collector is not None and int(eval_freq) > 0
@@ -261,10 +356,17 @@ class PPOLearner:
                     self.episode_stats = EpisodeStats(n, self.device)
                 self.episode_stats.reset_totals()
                 self.episode_stats.update(data)
-            out = self.update(data)
+            self.progress_remaining = 1.0 - (it + 1) / int(iterations)
+            out = self.update(data, explained_variance=True) if explained_variance else self.update(data)
             rec = dict(out["mean"], reward=float(data["rewards"].mean()))
             if "stopped" in out:  # target_kl is set
                 rec.update(stopped=out["stopped"], minibatches_run=out["minibatches_run"])
+            if "learning_rate" in self.schedules or "clip_range" in self.schedules:
+                rec.update(learning_rate=self.learning_rate, clip_range=self.clip_range)
+            if self.clip_range_vf is not None:
+                rec.update(clip_range_vf=self.clip_range_vf)
+            if explained_variance:
+                rec.update(explained_variance=out["explained_variance"])
             if episode_stats:
                 t = self.episode_stats.totals()
                 rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])

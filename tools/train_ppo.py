@@ -9,8 +9,12 @@
                                                           # hand-over alone and inside update(), host against device
     python tools/train_ppo.py --kind mono --weight-sync device --target-kl 0.03   # repack on the device; SB3's early stop
     python tools/train_ppo.py --kind mono --arithmetic matrix   # the gradient's products on the f32 matrix cores
-    python tools/train_ppo.py --kind mono --time --time-section arithmetic   # only the last block of --time: loss_grad and
-                                                          # update() with arithmetic="fma" against "matrix"
+    python tools/train_ppo.py --kind mono --time --time-section arithmetic   # only the last block of --time: loss_grad
+                                                          # (with and without value clipping) and update() with
+                                                          # arithmetic="fma" against "matrix"
+    python tools/train_ppo.py --kind mono --clip-range-vf 0.2 --lr-schedule linear --clip-schedule linear --explained-variance
+                                                          # SB3's clip_range_vf, linear decay of the learning rate and the
+                                                          # clip range, train/explained_variance per iteration
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -170,6 +174,8 @@ def time_arithmetic(args):
         stats = torch.zeros(8, device="cuda")
         calls = 20 if rows <= 65536 else 5
         learners = {f: M.PPOLearner(pol, ent_coef=0.05, arithmetic=f) for f in forms}
+        # the same call with value clipping (the VCLIP instantiation of each kernel, through mse_ppo_loss_grad_vclip)
+        learners.update({f + "+vclip": M.PPOLearner(pol, ent_coef=0.05, arithmetic=f, clip_range_vf=0.2) for f in forms})
         updaters = {f: M.PPOLearner(pol, ent_coef=0.05, shuffle="device", weight_sync="device", arithmetic=f) for f in forms}
 
         def loss_grads(lrn):
@@ -178,7 +184,7 @@ def time_arithmetic(args):
 
         for what, group, per in (("loss_grad", {f: (lambda lrn=lrn: loss_grads(lrn)) for f, lrn in learners.items()}, calls),
                                  ("update", {f: (lambda lrn=lrn: lrn.update(data)) for f, lrn in updaters.items()}, 1)):
-            times = {f: [] for f in forms}
+            times = {f: [] for f in group}
             for r in range(4):
                 for f, fn in group.items():
                     torch.cuda.synchronize()
@@ -219,6 +225,14 @@ def main():
                     help="every this many iterations evaluate_policy (10 deterministic episodes) and keep the best weights")
     ap.add_argument("--arithmetic", choices=("fma", "matrix"), default="fma",
                     help="how the gradient's products are formed: fmaf chains on the vector unit, or the f32 matrix cores")
+    ap.add_argument("--clip-range-vf", type=float, default=None,
+                    help="SB3's clip_range_vf: clip the value prediction to this distance from the rollout's (default: off)")
+    ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
+                    help="linear: --lr times progress_remaining, which reaches 0 in the last iteration")
+    ap.add_argument("--clip-schedule", choices=("constant", "linear"), default="constant",
+                    help="linear: the clip range 0.2 times progress_remaining")
+    ap.add_argument("--explained-variance", action="store_true",
+                    help="print SB3's train/explained_variance of each rollout's values against its returns")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic"), default="all",
                     help="with --time: run one block of the timings only")
@@ -234,16 +248,23 @@ def main():
     env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
-    learner = M.PPOLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
+    lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
+    clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
-                           arithmetic=args.arithmetic)
+                           arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
     print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
-          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}")
+          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}, "
+          f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}")
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
               f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
 
+        if "learning_rate" in rec:
+            print(f"       learning_rate {rec['learning_rate']:.3e} clip_range {rec['clip_range']:.4f}")
+        if "explained_variance" in rec:
+            print(f"       explained_variance {rec['explained_variance']:+.4f}")
         if "stopped" in rec:
             print(f"       minibatches run {rec['minibatches_run']}" + (" (stopped on target_kl)" if rec["stopped"] else ""))
         if "episodes" in rec:
@@ -257,7 +278,7 @@ def main():
                                        auto_reset=True)
         eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
     learner.learn(col, args.iterations, callback=show, episode_stats=args.episode_stats, eval_collector=eval_col,
-                  eval_freq=args.eval_every)
+                  eval_freq=args.eval_every, explained_variance=args.explained_variance)
     if eval_col is not None:
         learner.restore_best()
     if args.save:
