@@ -295,6 +295,69 @@ class BatchedSortingEnv:
             check(self.L.mse_reset(self._h, None, _ptr(none), _ptr(self.obs), _ptr(self.mask), self._stream()))
         return self.obs, self.mask
 
+    # ---- checkpoint (checkpoint.py) ------------------------------------------------------------------------------------
+    def fingerprint(self) -> dict:
+        """What must be equal for a state record to mean the same thing on another handle: `kind`, `num_envs`,
+        `max_steps`, `index_offset`, `auto_reset` and the bytes of the compiled config struct (u8 tensor)."""
+        cfg = torch.frombuffer(bytearray(bytes(self._cfg_struct)), dtype=torch.uint8).clone()
+        return {"kind": self.kind, "num_envs": self.num_envs, "max_steps": self.max_steps, "index_offset": self.index_offset,
+                "auto_reset": self.auto_reset, "config": cfg}
+
+    def _refuse_trace(self, what: str) -> None:
+        if self._trace_buf is not None:
+            raise RuntimeError(f"{what} with a trace attached: the trace's step count is not part of the state (trace_end() first)")
+
+    def state_dict(self) -> dict:
+        """CPU copies of the three `get_state()` tensors, `policy_step`, `seeds` and the `fingerprint()`.  `reward`,
+        `done` and `terminal_obs` of the last step are outputs, not state, and are not saved; `obs` and `mask` are
+        functions of the state (`refresh_outputs`).  Refused while a trace is attached."""
+        from .checkpoint import cpu
+
+        self._refuse_trace("state_dict()")
+        ints, dbls, rng = self.get_state()
+        return {"ints": cpu(ints), "dbls": cpu(dbls), "rng": cpu(rng), "policy_step": self.policy_step,
+                "seeds": cpu(self.seeds), "fingerprint": self.fingerprint()}
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError naming every differing fingerprint field (a differing config struct by its members, as
+        `config.<member>`), or a tensor of the wrong shape; nothing is touched."""
+        from .checkpoint import check_tensor, diff_fields, mismatch_message
+
+        self._refuse_trace("load_state_dict()")
+        saved, mine = dict(sd.get("fingerprint") or {}), self.fingerprint()
+        diffs = diff_fields(saved, mine)
+        at = [i for i, d in enumerate(diffs) if d[0] == "config"]
+        if at and isinstance(saved.get("config"), torch.Tensor) and saved["config"].numel() == mine["config"].numel():
+            theirs = _lib.MseConfigStruct.from_buffer_copy(bytes(saved["config"].to(torch.uint8).tolist()))
+
+            def plain(v):
+                return [plain(x) for x in v] if hasattr(v, "__len__") else v
+
+            members = [(f"config.{name}", plain(getattr(theirs, name)), plain(getattr(self._cfg_struct, name)))
+                       for name, *_ in _lib.MseConfigStruct._fields_]
+            members = [m for m in members if m[1] != m[2]]
+            if members:
+                diffs[at[0]:at[0] + 1] = members
+        if diffs:
+            raise ValueError(mismatch_message(f"BatchedSortingEnv({self.kind!r}, num_envs={self.num_envs})", diffs))
+        n = self.num_envs
+        for key, like in (("ints", torch.empty((n, MSE_SNAP_INTS), dtype=torch.int64)),
+                          ("dbls", torch.empty((n, 4), dtype=torch.float64)),
+                          ("rng", torch.empty((n, MSE_SNAP_RNG_WORDS), dtype=torch.int64)),
+                          ("seeds", torch.empty((n,), dtype=torch.int64))):
+            check_tensor(sd, key, like, "BatchedSortingEnv")
+        if isinstance(sd.get("policy_step"), bool) or not isinstance(sd.get("policy_step"), int) or sd["policy_step"] < 0:
+            raise ValueError(f"BatchedSortingEnv: policy_step must be a non-negative int, the checkpoint has {sd.get('policy_step')!r}")
+
+    def load_state_dict(self, sd: dict) -> None:
+        """`check_state_dict`, then `set_state`, `policy_step`, `seeds` and `refresh_outputs()`: `obs` / `mask` are those
+        of the restored state; `reward` / `done` / `terminal_obs` keep whatever the last step here wrote."""
+        self.check_state_dict(sd)
+        self.set_state(sd["ints"], sd["dbls"], sd["rng"])
+        self.policy_step = sd["policy_step"]
+        self.seeds.copy_(sd["seeds"])
+        self.refresh_outputs()
+
     def error_count(self) -> int:
         v = C.c_uint64(0)
         check(self.L.mse_error_count(self._h, C.byref(v)))

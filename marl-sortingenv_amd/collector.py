@@ -27,6 +27,16 @@ from .batched import BatchedSortingEnv
 from .policy import MlpPolicy
 
 
+def _check_collector(col, sd: dict, kind: str) -> None:
+    from .checkpoint import check_fingerprint
+
+    check_fingerprint({k: sd.get(k) for k in ("collector", "seed", "n_steps")},
+                      {"collector": kind, "seed": col.seed, "n_steps": col.n_steps}, type(col).__name__)
+    if not isinstance(sd.get("env"), dict):
+        raise ValueError(f"{type(col).__name__}: the checkpoint has no env state")
+    col.env.check_state_dict(sd["env"])
+
+
 class PolicyRolloutCollector:
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, sort_policy: Optional[MlpPolicy] = None,
                  seed: int = 2024):
@@ -51,6 +61,31 @@ class PolicyRolloutCollector:
         self._last_done = torch.ones((n,), dtype=torch.uint8, device=dev)  # the envs were just reset
         self._out = None
         self._sort_out = None
+
+    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """`seed`, `n_steps`, the policy stream's step `t`, the end marks of the last step (`_last_done`, the next
+        rollout's first `episode_starts`) and the env's state dict."""
+        from .checkpoint import cpu
+
+        return {"collector": "two_launch", "seed": self.seed, "n_steps": self.n_steps, "t": self.t,
+                "last_done": cpu(self._last_done), "env": self.env.state_dict()}
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError, with nothing touched, unless `sd` is this kind of collector's with this `seed` and `n_steps` and
+        the env accepts its part."""
+        from .checkpoint import check_tensor
+
+        _check_collector(self, sd, "two_launch")
+        check_tensor(sd, "last_done", self._last_done, "PolicyRolloutCollector")
+        if isinstance(sd.get("t"), bool) or not isinstance(sd.get("t"), int) or sd["t"] < 0:
+            raise ValueError(f"PolicyRolloutCollector: t must be a non-negative int, the checkpoint has {sd.get('t')!r}")
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.check_state_dict(sd)
+        self.env.load_state_dict(sd["env"])  # refreshes env.obs / env.mask, which the next collect() starts from
+        self.t = sd["t"]
+        self._last_done.copy_(sd["last_done"])
 
     def collect(self, deterministic: bool = False) -> dict:
         """K steps; returns the buffers plus `last_values` f32[N] (the bootstrap value of the state after the last
@@ -107,6 +142,22 @@ class FusedPolicyRollout:
             "last_values": torch.empty((n,), dtype=torch.float32, device=dev),
             "last_dones": torch.empty((n,), dtype=torch.uint8, device=dev),
         }
+
+    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """`seed`, `n_steps` and the env's state dict: the kernel derives `episode_starts` from the env state and reads
+        the step counter from the handle, so the collector itself carries nothing else (`sort_mode`, a constructor
+        argument, is given again at construction like the policies)."""
+        return {"collector": "fused", "seed": self.seed, "n_steps": self.n_steps, "env": self.env.state_dict()}
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError, with nothing touched, unless `sd` is this kind of collector's with this `seed` and `n_steps` and
+        the env accepts its part."""
+        _check_collector(self, sd, "fused")
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.check_state_dict(sd)
+        self.env.load_state_dict(sd["env"])
 
     def collect(self, n_steps: Optional[int] = None, deterministic: bool = False, use_action_masking: bool = True,
                 check_overflow: bool = False) -> dict:

@@ -71,6 +71,44 @@ class EpisodeStats:
         """Starts a new window of the totals; the carry, the counts and the ledger stay."""
         self._totals.zero_()
 
+    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
+    def _state_tensors(self) -> dict:
+        return {"run_return": self.run_return, "run_length": self.run_length, "ep_count": self.ep_count,
+                "ledger_return": self.ledger_return, "ledger_length": self.ledger_length, "totals": self._totals,
+                "targets": self.targets}
+
+    def state_dict(self) -> dict:
+        """CPU copies of the carry, the counts, the ledgers, the totals and the targets (None where there is none), with
+        `num_envs` / `slots` as the fingerprint."""
+        from .checkpoint import cpu
+
+        return dict({k: cpu(t) for k, t in self._state_tensors().items()}, num_envs=self.num_envs, slots=self.slots)
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError, with nothing touched, unless `sd` fits: `num_envs` and `slots` equal, every tensor of this
+        object's dtype and shape, a ledger exactly where this object has one."""
+        from .checkpoint import check_fingerprint, check_tensor
+
+        check_fingerprint({k: sd.get(k) for k in ("num_envs", "slots")}, {"num_envs": self.num_envs, "slots": self.slots},
+                          "EpisodeStats")
+        for key, t in self._state_tensors().items():
+            if key == "targets":
+                if sd.get(key) is not None:
+                    check_tensor(sd, key, torch.empty(self.num_envs, dtype=torch.int32), "EpisodeStats")
+            elif t is None:
+                if sd.get(key) is not None:
+                    raise ValueError(f"EpisodeStats: the checkpoint has a {key}, this object has no ledger")
+            else:
+                check_tensor(sd, key, t, "EpisodeStats")
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.check_state_dict(sd)
+        for key, t in self._state_tensors().items():
+            if key != "targets" and t is not None:
+                t.copy_(sd[key])
+        tg = sd.get("targets")
+        self.targets = None if tg is None else tg.to(device=self.device, dtype=torch.int32).contiguous()
+
     def update(self, data: dict, n_steps: Optional[int] = None) -> None:
         """Accounts one rollout: a collector's dict (`rewards`, `episode_starts`, `last_dones`) or the buffers of
         `BatchedSortingEnv.rollout` (`reward`, `done`).  n_steps: the rows that were filled, if fewer than the buffers

@@ -13,6 +13,8 @@ host arithmetic on `progress_remaining` (`resolve_schedule`), and `train/explain
 update (`mse_explained_variance`).
 `learn` can report the reference's unit, cumulative reward per episode (episodes.py): SB3's `rollout/ep_rew_mean` from an
 `EpisodeStats` over the training rollouts, and `EvalCallback`'s periodic `evaluate_policy` with the best weights kept.
+`state_dict` / `load_state_dict` carry everything of a run that lives here, and `learn(first_iteration=...,
+checkpoint_path=..., checkpoint_freq=...)` writes and continues whole runs (checkpoint.py): a resumed run is the same run.
 """
 from __future__ import annotations
 
@@ -259,6 +261,106 @@ class PPOLearner:
             check(self.L.mse_explained_variance(returns.numel(), _ptr(values), _ptr(returns), _ptr(out), _ptr(self.workspace),
                                                 _stream(self.device)))
 
+    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
+    def hyperparameters(self) -> dict:
+        """Everything the constructor fixes that changes results, as plain data: the dims, the constructor's numbers and
+        modes, `scheduled` (the names of the fields that are schedules) and the plain values of the other ones of
+        `learning_rate`, `clip_range`, `clip_range_vf`.  `ent_coef` / `vf_coef` are read back from `params`, i.e. as the
+        f32 the kernels get."""
+        hp = {"obs_dim": self.policy.obs_dim, "n_actions": self.policy.n_actions, "n_epochs": self.n_epochs,
+              "batch_size": None if self.batch_size is None else int(self.batch_size), "gamma": self.gamma,
+              "gae_lambda": self.gae_lambda, "ent_coef": float(self.params.ent_coef), "vf_coef": float(self.params.vf_coef),
+              "max_grad_norm": self.max_grad_norm, "normalize_advantage": bool(self.params.normalize_advantage),
+              "adam_eps": self.adam_eps, "beta1": self.beta1, "beta2": self.beta2, "seed": self.seed, "shuffle": self.shuffle,
+              "weight_sync": self.weight_sync, "target_kl": self.target_kl, "arithmetic": self.arithmetic,
+              "scheduled": sorted(self.schedules)}
+        for name in ("learning_rate", "clip_range", "clip_range_vf"):
+            if name not in self.schedules:
+                hp[name] = getattr(self, name)
+        return hp
+
+    def state_dict(self) -> dict:
+        """The run state as CPU tensors and plain data: `weights`, `m`, `v`, `step`, `epochs_done`, the CPU generator's
+        state (`generator`, its `get_state()` bytes), `progress_remaining`, the resolved `learning_rate` / `clip_range` /
+        `clip_range_vf`, `best_mean_reward`, `best_weights` and `episode_stats` (its state dict) when there are any, and
+        `hyperparameters()`.  Schedules are callables and are not stored: construct the learner with them again."""
+        from .checkpoint import cpu, generator_state
+
+        sd = {"weights": cpu(self.weights), "m": cpu(self.m), "v": cpu(self.v), "step": int(self.step),
+              "epochs_done": int(self.epochs_done), "generator": generator_state(self.generator),
+              "progress_remaining": float(self.progress_remaining), "learning_rate": self.learning_rate,
+              "clip_range": self.clip_range, "clip_range_vf": self.clip_range_vf,
+              "best_mean_reward": float(self.best_mean_reward), "hyperparameters": self.hyperparameters()}
+        if self.best_weights is not None:
+            sd["best_weights"] = cpu(self.best_weights)
+        if self.episode_stats is not None:
+            sd["episode_stats"] = self.episode_stats.state_dict()
+        return sd
+
+    def check_state_dict(self, sd: dict, strict: bool = True) -> None:
+        """ValueError, with nothing touched, unless `sd` can be loaded: the dims must match always; with strict=True every
+        hyperparameter must (the message names every differing field with both values; a field scheduled on one side only
+        shows under `scheduled` and as a value one side lacks)."""
+        from .checkpoint import check_fingerprint, check_tensor
+
+        saved, mine = dict(sd.get("hyperparameters") or {}), self.hyperparameters()
+        check_fingerprint(saved, mine, "PPOLearner", fields=None if strict else ("obs_dim", "n_actions"))
+        for key in ("weights", "m", "v") + (("best_weights",) if "best_weights" in sd else ()):
+            check_tensor(sd, key, torch.empty(self.n_weights, dtype=torch.float32), "PPOLearner")
+        if not isinstance(sd.get("generator"), torch.Tensor) or sd["generator"].dtype != torch.uint8 \
+                or sd["generator"].shape != self.generator.get_state().shape:
+            raise ValueError("PPOLearner: generator must be the byte tensor of a CPU generator's get_state()")
+        for key in ("step", "epochs_done"):
+            if isinstance(sd.get(key), bool) or not isinstance(sd.get(key), int) or sd[key] < 0:
+                raise ValueError(f"PPOLearner: {key} must be a non-negative int, the checkpoint has {sd.get(key)!r}")
+        if strict:
+            for key in ("learning_rate", "clip_range", "clip_range_vf", "progress_remaining"):
+                if key not in sd:
+                    raise ValueError(f"PPOLearner: the checkpoint has no {key}")
+        es = sd.get("episode_stats")
+        if es is not None and self.episode_stats is not None and (self.episode_stats.num_envs, self.episode_stats.slots) == \
+                (es.get("num_envs"), es.get("slots")):
+            self.episode_stats.check_state_dict(es)
+
+    def load_state_dict(self, sd: dict, strict: bool = True) -> None:
+        """`check_state_dict`, then: the tensors are copied into the existing device tensors, the counters and the
+        generator restored, `episode_stats` created if needed (dropped when the checkpoint has none), and the weights
+        handed to the policy the way `update()` does it (`_hand_over()`, `policy.sync()`).
+        strict=True: the stored `learning_rate` / `clip_range` / `clip_range_vf` come back as they were resolved.
+        strict=False: only the dims must match and the constructor's values are kept - a changed learning rate, say -
+        with this learner's schedules evaluated at the restored `progress_remaining`."""
+        from .checkpoint import set_generator_state
+        from .episodes import EpisodeStats
+
+        self.check_state_dict(sd, strict=strict)
+        es, stats = sd.get("episode_stats"), None
+        if es is not None:  # first: a new EpisodeStats that refuses its part leaves the learner as it was
+            stats = self.episode_stats
+            if stats is None or (stats.num_envs, stats.slots) != (es.get("num_envs"), es.get("slots")):
+                stats = EpisodeStats(es.get("num_envs"), self.device, slots=es.get("slots"))
+            stats.load_state_dict(es)
+        for key in ("weights", "m", "v"):
+            getattr(self, key).copy_(sd[key])
+        self.step, self.epochs_done = int(sd["step"]), int(sd["epochs_done"])
+        set_generator_state(self.generator, sd["generator"])
+        self.progress_remaining = float(sd.get("progress_remaining", 1.0))
+        if strict:
+            self.learning_rate, self.clip_range = float(sd["learning_rate"]), float(sd["clip_range"])
+            self.clip_range_vf = None if sd["clip_range_vf"] is None else float(sd["clip_range_vf"])
+            self.params.clip_range = self.clip_range
+        else:
+            self._resolve_schedules()
+        self.best_mean_reward = float(sd.get("best_mean_reward", float("-inf")))
+        if "best_weights" in sd:
+            if self.best_weights is None:
+                self.best_weights = torch.empty_like(self.weights)
+            self.best_weights.copy_(sd["best_weights"])
+        else:
+            self.best_weights = None
+        self.episode_stats = stats
+        self._hand_over()
+        self.policy.sync()
+
     def update(self, data: dict, progress_remaining: Optional[float] = None, explained_variance: bool = False) -> dict:
         """GAE, then n_epochs passes over a permutation of the K * N rows (shuffle="cpu": seeded on the CPU and copied to
         the device once per epoch; shuffle="device": one `mse_ppo_shuffle` launch per epoch; the last minibatch of an
@@ -328,7 +430,8 @@ class PPOLearner:
         return out
 
     def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
-              eval_freq: int = 0, n_eval_episodes: int = 10, explained_variance: bool = False) -> list:
+              eval_freq: int = 0, n_eval_episodes: int = 10, explained_variance: bool = False, first_iteration: int = 0,
+              checkpoint_path=None, checkpoint_freq: int = 0, history: Optional[list] = None) -> list:
         """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
         mean reward per env-step under "reward" (and, with `target_kl`, the update's "stopped" and "minibatches_run").
         episode_stats=True: each record gains `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in
@@ -341,14 +444,29 @@ class PPOLearner:
         what they were without these arguments.
         Before update `it` `progress_remaining` becomes `1 - (it + 1) / iterations`.  A record gains `learning_rate` and
         `clip_range` (the values that update used) when either is a schedule, `clip_range_vf` when it is set, and
-        `explained_variance` with explained_variance=True."""
+        `explained_variance` with explained_variance=True.
+        first_iteration: the loop runs `it` in range(first_iteration, iterations) with `progress_remaining` as above, so
+        a run resumed from a checkpoint (`load_checkpoint`, then first_iteration = its "iteration") is on the same
+        schedule and, bit for bit, the same run.  history: the records of the iterations already done (a checkpoint's
+        "history"); the returned list then starts with them, else it holds the records of this call alone.
+        checkpoint_freq > 0: after every checkpoint_freq-th iteration - the record appended, `callback` not yet called -
+        `save_checkpoint(checkpoint_path, ...)` writes this learner, `collector` (with its env), the collector's frozen
+        `sort_policy` if it has one (under policies["sort_policy"]), iteration = it + 1, `iterations` and the history so
+        far; an `{iteration}` field in checkpoint_path is filled in, so earlier files can be kept.  `eval_collector`'s
+        env is not saved and needs no state: `evaluate_policy` resets it every time.  With the defaults nothing is
+        written and the loop is what it was."""
+        from .checkpoint import format_path, save_checkpoint
         from .episodes import EpisodeStats, evaluate_policy
 
         evaluating = eval_collector is not None and int(eval_freq) > 0
         if evaluating and eval_collector.policy is not self.policy:
             raise ValueError("eval_collector must run this learner's policy")
-        history = []
-        for it in range(int(iterations)):
+        if not 0 <= int(first_iteration) <= int(iterations):
+            raise ValueError(f"first_iteration must be in [0, iterations = {int(iterations)}], not {first_iteration!r}")
+        if int(checkpoint_freq) < 0 or (int(checkpoint_freq) > 0 and checkpoint_path is None):
+            raise ValueError("checkpoint_freq must be >= 0, and > 0 needs a checkpoint_path")
+        history = [] if history is None else list(history)
+        for it in range(int(first_iteration), int(iterations)):
             data = collector.collect()
             if episode_stats:
                 n = data["rewards"].shape[1]
@@ -379,6 +497,11 @@ class PPOLearner:
                         self.best_weights = torch.empty_like(self.weights)
                     self.best_weights.copy_(self.weights)  # device to device
             history.append(rec)
+            if int(checkpoint_freq) > 0 and (it + 1) % int(checkpoint_freq) == 0:
+                sort_policy = getattr(collector, "sort_policy", None)
+                save_checkpoint(format_path(checkpoint_path, it + 1), learner=self, collector=collector,
+                                policies=None if sort_policy is None else {"sort_policy": sort_policy}, iteration=it + 1,
+                                iterations=int(iterations), history=history)
             if callback is not None:
                 callback(it, rec)
         return history

@@ -15,6 +15,10 @@
     python tools/train_ppo.py --kind mono --clip-range-vf 0.2 --lr-schedule linear --clip-schedule linear --explained-variance
                                                           # SB3's clip_range_vf, linear decay of the learning rate and the
                                                           # clip range, train/explained_variance per iteration
+    python tools/train_ppo.py --kind mono --iterations 20 --checkpoint run_{iteration}.pt --checkpoint-every 5
+                                                          # one file after every 5th iteration: learner, envs, history
+    python tools/train_ppo.py --kind mono --iterations 20 --resume run_10.pt   # the same command line plus --resume:
+                                                          # iterations 10 .. 19 of the same run, bit for bit
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -236,6 +240,13 @@ def main():
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic"), default="all",
                     help="with --time: run one block of the timings only")
+    ap.add_argument("--checkpoint", default=None, metavar="PATH",
+                    help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N",
+                    help="with --checkpoint: after every N-th iteration (default: once, after the last)")
+    ap.add_argument("--resume", default=None, metavar="PATH",
+                    help="continue the run of a --checkpoint file at its iteration; the other arguments must be the ones it was "
+                         "started with (a differing hyperparameter or env is refused by name)")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
     if args.time:
@@ -277,8 +288,21 @@ def main():
         eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
                                        auto_reset=True)
         eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
+    first, history = 0, None
+    if args.resume:
+        ck = M.load_checkpoint(args.resume, learner=learner, collector=col)
+        first, history = ck["iteration"], ck["history"]
+        if ck["iterations"] is not None and ck["iterations"] != args.iterations:
+            print(f"note: the checkpoint was written by a run of {ck['iterations']} iterations, this one has {args.iterations}: "
+                  f"progress_remaining, and with it any schedule, continues on the new scale")
+        print(f"resuming {args.resume} at iteration {first}; already done:")
+        for it, rec in enumerate(history):
+            show(it, rec)
+        print("continuing:")
+    every = args.checkpoint_every if args.checkpoint_every > 0 else args.iterations
     learner.learn(col, args.iterations, callback=show, episode_stats=args.episode_stats, eval_collector=eval_col,
-                  eval_freq=args.eval_every, explained_variance=args.explained_variance)
+                  eval_freq=args.eval_every, explained_variance=args.explained_variance, first_iteration=first, history=history,
+                  checkpoint_path=args.checkpoint, checkpoint_freq=every if args.checkpoint else 0)
     if eval_col is not None:
         learner.restore_best()
     if args.save:
