@@ -342,6 +342,66 @@ int mse_rollout_policy(mse_env *env, mse_policy *policy, mse_policy *sort_policy
                        int32_t *actions_out, float *logp_out, float *value_out, float *reward_out,
                        uint8_t *episode_start_out, float *last_value_out, uint8_t *last_done_out, void *stream);
 
+/* ---- The modular pair trained in the env it is deployed in: K steps of Env_3_Monolith in ONE launch with the sorting
+ * agent (13 -> 2) and the pressing agent (16 -> 11) acting side by side, each recorded as its own learner needs it.
+ * Per step k and env i:
+ *   1. previews: a copy of the env takes the step's flow update; sort_obs = get_sort_obs() and press_obs =
+ *      get_press_obs() of the copy (mse_sort_agent_obs / mse_press_agent_obs); press_action_masks() is taken from the
+ *      state the decision is made in;
+ *   2. sorting agent: action, log-probability, value = policy(sort_obs), every action legal, drawn with the word of
+ *      (sort_seed, global env index, t + k);
+ *   3. pressing agent: the same on press_obs with the word of (press_seed, global env index, t + k), over
+ *      press_action_masks() with MSE_MODEL_PRESS_AGENT_MASKED, else over all 11 actions;
+ *   4. MSE_MODULAR_SORT_DETERMINISTIC / MSE_MODULAR_PRESS_DETERMINISTIC: that agent takes the argmax
+ *      (predict(deterministic=True)); its log-probability and value are written all the same;
+ *   5. the flat action 11 sort + press is stepped as mse_step steps it without MSE_STEP_UNMASKED (no sanitising,
+ *      env_monolith.py:254-257), MSE_STEP_CHECK_OVERFLOW honoured, auto-reset on termination.
+ * Outputs (mse_modular_buffers, step-major, any pointer may be NULL): the rows the decisions were taken from -
+ * sort_obs f32[K,N,13], press_obs f32[K,N,16], press_masks u8[K,N,11] (always press_action_masks(), whatever the
+ * agent was shown), episode_starts u8[K,N] -, sort_actions / press_actions i32[K,N], sort_log_probs / press_log_probs /
+ * sort_values / press_values f32[K,N], rewards f32[K,N] (the step's reward) and its two parts rewards_sort /
+ * rewards_press f32[K,N] (the arguments of _log_step_data, env_monolith.py:271,282: reward / 2 each on an overflow
+ * termination), and after the last step sort_last_values / press_last_values f32[N] (each critic on its preview of the
+ * state the rollout ends in) and last_dones u8[N].
+ * Bit-identical to K rounds of mse_sort_agent_obs, mse_press_agent_obs, two mse_policy_forward calls (the seeds above,
+ * t = the handle's policy step counter, index_offset = the env's) and mse_step: the same actions, log-probabilities,
+ * values, observations, rewards, flags and final state.  Advances the policy step counter by K; the env's rng_sorting /
+ * rng_pressing streams are neither read nor written (there are no fallback draws).
+ * Refusals: MSE_ERR_INVALID_ARGUMENT - a NULL agent, agent dimensions other than 13 -> 2 / 16 -> 11, sort_seed ==
+ * press_seed (the two agents would draw from one word), k_steps < 1, a flag other than the four above
+ * (MSE_STEP_UNMASKED included), a handle that is not Env_3 or lacks auto_reset=1, an attached trace;
+ * MSE_ERR_UNSUPPORTED_CONFIG - an agent not in the f16x3 form, literal_choice, general generator mode, tables that do
+ * not fit the kernel's LDS image. */
+#define MSE_MODULAR_SORT_DETERMINISTIC  128u
+#define MSE_MODULAR_PRESS_DETERMINISTIC 256u
+typedef struct mse_modular_buffers {
+    uint32_t struct_size; /* = sizeof(mse_modular_buffers); ABI check */
+    uint32_t reserved0;
+    float   *sort_obs;
+    float   *press_obs;
+    uint8_t *press_masks;
+    uint8_t *episode_starts;
+    int32_t *sort_actions;
+    int32_t *press_actions;
+    float   *sort_log_probs;
+    float   *press_log_probs;
+    float   *sort_values;
+    float   *press_values;
+    float   *rewards;
+    float   *rewards_sort;
+    float   *rewards_press;
+    float   *sort_last_values;
+    float   *press_last_values;
+    uint8_t *last_dones;
+} mse_modular_buffers;
+int mse_rollout_modular(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps, uint64_t sort_seed,
+                        uint64_t press_seed, uint32_t flags, const mse_modular_buffers *out, void *stream);
+/* The status mse_rollout_modular would return for these arguments (MSE_OK or one of the refusals above, with its
+ * message in mse_last_error), without launching anything or touching the handle: what a caller that alternates the
+ * single calls itself asks first, so that it serves exactly the handles the kernel serves. */
+int mse_rollout_modular_check(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps,
+                              uint64_t sort_seed, uint64_t press_seed, uint32_t flags);
+
 /* Replaces the device image of `policy` with new weights (same flat order as mse_policy_create), repacked by the same
  * host routine, including the f16 range check: a policy in the "auto" form moves to f32 when a folded weight leaves
  * f16's range and back when all fit again; one pinned to f16x3 refuses such weights (MSE_ERR_UNSUPPORTED_CONFIG, image

@@ -10,6 +10,7 @@ MSE_ENV_SORT, MSE_ENV_PRESS, MSE_ENV_MONO = 1, 2, 3
 MSE_STEP_UNMASKED, MSE_STEP_CHECK_OVERFLOW, MSE_ROLLOUT_RULE_BASED, MSE_STEP_SANITIZE_LATE = 1, 2, 4, 8
 MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_NO_PRESS_DRAW = 16, 32
 MSE_MODEL_PRESS_AGENT_MASKED = 64
+MSE_MODULAR_SORT_DETERMINISTIC, MSE_MODULAR_PRESS_DETERMINISTIC = 128, 256
 MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
@@ -21,7 +22,7 @@ EXPORTS = [
     "mse_error_count", "mse_algorithmic_bytes_per_step", "mse_tie_window",
     "mse_sort_agent_obs", "mse_policy_num_weights", "mse_policy_create", "mse_policy_destroy", "mse_policy_forward",
     "mse_get_policy_step", "mse_set_policy_step", "mse_model_actions", "mse_trace_begin", "mse_trace_end", "mse_press_agent_obs", "mse_rollout_policy", "mse_policy_set_precision", "mse_policy_precision",
-    "mse_rollout_model",
+    "mse_rollout_model", "mse_rollout_modular", "mse_rollout_modular_check",
     "mse_policy_set_weights", "mse_gae", "mse_ppo_workspace_bytes", "mse_ppo_loss_grad", "mse_ppo_adam_step",
     "mse_ppo_shuffle", "mse_ppo_shuffle_host",
     "mse_policy_set_weights_device", "mse_policy_sync", "mse_policy_image_floats", "mse_policy_pack_host",
@@ -64,6 +65,17 @@ class MsePpoParams(C.Structure):
     """struct mse_ppo_params (include/mse.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("clip_range", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float),
                 ("normalize_advantage", C.c_int32)]
+
+
+# the pointer members of struct mse_modular_buffers, in the header's order (= the keys of the collectors' buffer dicts)
+MODULAR_BUFFER_NAMES = ("sort_obs", "press_obs", "press_masks", "episode_starts", "sort_actions", "press_actions",
+                        "sort_log_probs", "press_log_probs", "sort_values", "press_values", "rewards", "rewards_sort",
+                        "rewards_press", "sort_last_values", "press_last_values", "last_dones")
+
+
+class MseModularBuffers(C.Structure):
+    """struct mse_modular_buffers (include/mse.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(name, C.c_void_p) for name in MODULAR_BUFFER_NAMES]
 
 
 _lib = None
@@ -133,6 +145,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_policy_forward.argtypes = [vp, i64, i64, vp, vp, u64, u64, C.c_int, vp, vp, vp, vp, vp]
     L.mse_rollout_policy.argtypes = [vp, vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mse_rollout_modular.argtypes = [vp, vp, vp, i32, u64, u64, u32, C.POINTER(MseModularBuffers), vp]
+    L.mse_rollout_modular_check.argtypes = [vp, vp, vp, i32, u64, u64, u32]
     L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
     L.mse_policy_set_weights_device.argtypes = [vp, vp, vp]
     L.mse_policy_sync.argtypes = [vp]

@@ -16,6 +16,11 @@ policy's MFMA chain.  Its buffers are bit-identical to `PolicyRolloutCollector`'
 several launches per step: the agents' previews, their forwards, the env's own fallback draws, the step.  It is what
 `BatchedSortingEnv.rollout(K, policy="model")` (`mse_rollout_model`, one launch per rollout) is held against, and it
 serves the handles that kernel refuses (literal_choice, general generator mode).
+
+`FusedModularRollout` collects for BOTH modular agents at once in Env_3 (`mse_rollout_modular`, one launch per
+rollout): each agent samples, scores and values its own preview, the flat action is stepped, and the reward is recorded
+whole and in its sorting / pressing parts; `view()` hands a `PPOLearner` one agent's rows.  `ModularRolloutCollector`
+is its multi-launch twin, the yardstick the kernel is tested against.
 """
 from __future__ import annotations
 
@@ -232,4 +237,225 @@ class ModelRolloutCollector:
                            ("sort_obs", sort_obs), ("press_obs", press_obs)):
                 if b.get(key) is not None:
                     b[key][k].copy_(v)
+        return b
+
+
+# ---- the modular pair in the env it is deployed in (mse_rollout_modular) ----------------------------------------------
+def _check_modular(env, sort_agent, press_agent, n_steps, sort_seed, press_seed) -> None:
+    """What both modular collectors refuse before any handle is asked: the kernel's own argument rules."""
+    if getattr(env, "kind", None) != "mono":
+        raise ValueError("the modular rollout exists on Env_3_Monolith only")
+    if sort_agent is None or press_agent is None:
+        raise ValueError("both agents are required")
+    if sort_agent.obs_dim != 13 or sort_agent.n_actions != 2:
+        raise ValueError("the sorting agent must be a 13 -> 2 policy")
+    if press_agent.obs_dim != 16 or press_agent.n_actions != 11:
+        raise ValueError("the pressing agent must be a 16 -> 11 policy")
+    if not env.auto_reset:
+        raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+    if int(n_steps) < 1:
+        raise ValueError("n_steps must be >= 1")
+    if int(sort_seed) == int(press_seed):
+        raise ValueError("sort_seed == press_seed: the two agents would draw from one word")
+
+
+def _modular_buffers(n: int, K: int, dev, parts: bool = True) -> dict:
+    f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+    b = {
+        "sort_obs": torch.empty((K, n, 13), dtype=f32, device=dev),
+        "press_obs": torch.empty((K, n, 16), dtype=f32, device=dev),
+        "press_masks": torch.empty((K, n, 11), dtype=u8, device=dev),
+        "episode_starts": torch.empty((K, n), dtype=u8, device=dev),
+        "sort_actions": torch.empty((K, n), dtype=i32, device=dev),
+        "press_actions": torch.empty((K, n), dtype=i32, device=dev),
+        "sort_log_probs": torch.empty((K, n), dtype=f32, device=dev),
+        "press_log_probs": torch.empty((K, n), dtype=f32, device=dev),
+        "sort_values": torch.empty((K, n), dtype=f32, device=dev),
+        "press_values": torch.empty((K, n), dtype=f32, device=dev),
+        "rewards": torch.empty((K, n), dtype=f32, device=dev),
+        "sort_last_values": torch.empty((n,), dtype=f32, device=dev),
+        "press_last_values": torch.empty((n,), dtype=f32, device=dev),
+        "last_dones": torch.empty((n,), dtype=u8, device=dev),
+    }
+    if parts:
+        b["rewards_sort"] = torch.empty((K, n), dtype=f32, device=dev)
+        b["rewards_press"] = torch.empty((K, n), dtype=f32, device=dev)
+    return b
+
+
+def modular_view(buffers: dict, who: str, reward: str = "own", press_masked: bool = True) -> dict:
+    """One agent's part of a modular collector's buffer dict under `PPOLearner`'s names; every value IS the buffer's
+    tensor (no copy).  who: "sort" | "press".  reward: "own" - that agent's component (`rewards_sort` /
+    `rewards_press`) - or "team", the sum both agents earned (`rewards`).  `action_masks` is None for the sorter, and for
+    the presser when it was not shown its mask."""
+    if who not in ("sort", "press"):
+        raise ValueError(f"who must be 'sort' or 'press', not {who!r}")
+    if reward not in ("own", "team"):
+        raise ValueError(f"reward must be 'own' or 'team', not {reward!r}")
+    rkey = "rewards" if reward == "team" else f"rewards_{who}"
+    if buffers.get(rkey) is None:
+        raise KeyError(f"this collector does not fill {rkey!r} (the multi-launch twin has no reward parts)")
+    return {
+        "observations": buffers[f"{who}_obs"],
+        "action_masks": buffers["press_masks"] if who == "press" and press_masked else None,
+        "actions": buffers[f"{who}_actions"],
+        "log_probs": buffers[f"{who}_log_probs"],
+        "values": buffers[f"{who}_values"],
+        "rewards": buffers[rkey],
+        "episode_starts": buffers["episode_starts"],
+        "last_values": buffers[f"{who}_last_values"],
+        "last_dones": buffers["last_dones"],
+    }
+
+
+class _ModularBase:
+    """Constructor, views and checkpoint surface the fused modular collector and its multi-launch twin share."""
+
+    KIND = "modular"
+    PARTS = True  # fills rewards_sort / rewards_press
+
+    def __init__(self, env: BatchedSortingEnv, sort_agent: MlpPolicy, press_agent: MlpPolicy, n_steps: int,
+                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True):
+        _check_modular(env, sort_agent, press_agent, n_steps, sort_seed, press_seed)
+        self.env, self.sort_agent, self.press_agent = env, sort_agent, press_agent
+        self.n_steps, self.sort_seed, self.press_seed = int(n_steps), int(sort_seed), int(press_seed)
+        self.press_masked = bool(press_masked)
+        self.buffers = _modular_buffers(env.num_envs, self.n_steps, env.device, self.PARTS)
+        self._views: dict = {}
+
+    def view(self, who: str, reward: str = "own") -> dict:
+        """`modular_view` of this collector's buffers.  The dict of a (who, reward) pair is kept, so the advantages and
+        returns `compute_gae` adds to it are allocated once."""
+        key = (who, reward)
+        if key not in self._views:
+            self._views[key] = modular_view(self.buffers, who, reward, self.press_masked)
+        return self._views[key]
+
+    def _check_run(self, n_steps) -> int:
+        K = self.n_steps if n_steps is None else int(n_steps)
+        if not 1 <= K <= self.n_steps:
+            raise ValueError("n_steps must be in [1, the collector's K]")
+        return K
+
+    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """Both seeds, `n_steps` and the env's state dict (which carries the policy step counter): the kernel derives
+        `episode_starts` from the env state, so the collector carries nothing else."""
+        return {"collector": self.KIND, "sort_seed": self.sort_seed, "press_seed": self.press_seed, "n_steps": self.n_steps,
+                "env": self.env.state_dict()}
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError, with nothing touched, unless `sd` is this kind of collector's with these seeds and `n_steps` and
+        the env accepts its part."""
+        from .checkpoint import check_fingerprint
+
+        check_fingerprint({k: sd.get(k) for k in ("collector", "sort_seed", "press_seed", "n_steps")},
+                          {"collector": self.KIND, "sort_seed": self.sort_seed, "press_seed": self.press_seed,
+                           "n_steps": self.n_steps}, type(self).__name__)
+        if not isinstance(sd.get("env"), dict):
+            raise ValueError(f"{type(self).__name__}: the checkpoint has no env state")
+        self.env.check_state_dict(sd["env"])
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.check_state_dict(sd)
+        self.env.load_state_dict(sd["env"])
+
+
+class FusedModularRollout(_ModularBase):
+    """The sorting agent (13 -> 2) and the pressing agent (16 -> 11) acting side by side in Env_3_Monolith, K steps per
+    launch (`mse_rollout_modular`): per agent the rows a `PPOLearner` consumes - observations, actions,
+    log-probabilities, values, the bootstrap value - plus the step's reward whole (`rewards`) and in its two parts
+    (`rewards_sort`, `rewards_press`).  press_masked: the pressing agent is maskable and sees press_action_masks()."""
+
+    def collect(self, n_steps: Optional[int] = None, sort_deterministic: bool = False, press_deterministic: bool = False,
+                check_overflow: bool = False) -> dict:
+        """One launch.  n_steps <= the buffers' K (a shorter rollout fills the first rows).  The env's own obs / mask
+        tensors are not refreshed (the state is; call env.refresh_outputs() to step it by hand afterwards)."""
+        import ctypes as C
+
+        from ._lib import (MODULAR_BUFFER_NAMES, MSE_MODEL_PRESS_AGENT_MASKED, MSE_MODULAR_PRESS_DETERMINISTIC,
+                           MSE_MODULAR_SORT_DETERMINISTIC, MSE_STEP_CHECK_OVERFLOW, MseModularBuffers, check)
+
+        K = self._check_run(n_steps)
+        env, b = self.env, self.buffers
+        flags = (MSE_MODEL_PRESS_AGENT_MASKED if self.press_masked else 0) | (MSE_STEP_CHECK_OVERFLOW if check_overflow else 0) | \
+                (MSE_MODULAR_SORT_DETERMINISTIC if sort_deterministic else 0) | \
+                (MSE_MODULAR_PRESS_DETERMINISTIC if press_deterministic else 0)
+        out = MseModularBuffers(C.sizeof(MseModularBuffers), 0, *(b[name].data_ptr() for name in MODULAR_BUFFER_NAMES))
+        with torch.cuda.device(env.device):
+            check(env.L.mse_rollout_modular(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
+                                            self.press_seed, flags, C.byref(out), env._stream()))
+        return b
+
+
+class ModularRolloutCollector(_ModularBase):
+    """`FusedModularRollout`'s multi-launch twin, built from the sentence in include/mse.h that states what the kernel
+    equals: per step mse_sort_agent_obs, mse_press_agent_obs, two `MlpPolicy.forward` calls (the two seeds, t = the
+    handle's policy step counter, index_offset = the env's) and mse_step.  It fills every buffer except `rewards_sort` /
+    `rewards_press` (mse_step does not return the parts).  The yardstick the kernel is held against, not a fallback: it
+    refuses what the kernel refuses, by asking the library (`mse_rollout_modular_check`) at construction and before every
+    collection.  Like the kernel it reads `episode_starts` off the env state, so it carries nothing between calls and
+    its `state_dict` is the base class's."""
+
+    KIND = "modular_twin"
+    PARTS = False
+    SNAP_CURRENT_STEP = 32  # column of mse_get_state's integer record that holds the env's current_step
+
+    def __init__(self, env: BatchedSortingEnv, sort_agent: MlpPolicy, press_agent: MlpPolicy, n_steps: int,
+                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True):
+        super().__init__(env, sort_agent, press_agent, n_steps, sort_seed, press_seed, press_masked)
+        self._refusal(self.n_steps, 0)  # what mse_rollout_modular would refuse on this handle, with these agents
+        self._last_done = torch.empty((env.num_envs,), dtype=torch.uint8, device=env.device)
+        self._sort_out = self._press_out = None
+
+    def _refusal(self, K: int, flags: int) -> None:
+        """Raises what `FusedModularRollout.collect` would raise for the same arguments (`mse_rollout_modular_check`:
+        the kernel's own checks - the handle, the agents' form, an attached trace, tables that do not fit - and no
+        launch)."""
+        from ._lib import MSE_MODEL_PRESS_AGENT_MASKED, check
+
+        env = self.env
+        check(env.L.mse_rollout_modular_check(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
+                                              self.press_seed, flags | (MSE_MODEL_PRESS_AGENT_MASKED if self.press_masked else 0)))
+
+    def collect(self, n_steps: Optional[int] = None, sort_deterministic: bool = False, press_deterministic: bool = False,
+                check_overflow: bool = False) -> dict:
+        from ._lib import MSE_STEP_CHECK_OVERFLOW
+
+        K = self._check_run(n_steps)
+        env, b = self.env, self.buffers
+        self._refusal(K, MSE_STEP_CHECK_OVERFLOW if check_overflow else 0)
+        env.refresh_outputs()  # env.mask = action_masks() of the current state, whatever ran on the handle before
+        # the first row's episode starts come from the state, as the kernel takes them (current_step == 0): nothing is
+        # carried between calls, so a restored or hand-stepped handle gives the rows the kernel gives
+        self._last_done.copy_(env.get_state()[0][:, self.SNAP_CURRENT_STEP] == 0)
+        for k in range(K):
+            sort_obs, press_obs = env.sort_agent_obs(), env.press_agent_obs()
+            press_mask = env.mask[:, :11]  # press_action_masks()
+            t = env.policy_step
+            self._sort_out = self.sort_agent.forward(sort_obs, None, seed=self.sort_seed, t=t, deterministic=sort_deterministic,
+                                                     index_offset=env.index_offset, out=self._sort_out)
+            self._press_out = self.press_agent.forward(press_obs, press_mask if self.press_masked else None,
+                                                       seed=self.press_seed, t=t, deterministic=press_deterministic,
+                                                       index_offset=env.index_offset, out=self._press_out)
+            b["sort_obs"][k].copy_(sort_obs)
+            b["press_obs"][k].copy_(press_obs)
+            b["press_masks"][k].copy_(press_mask)
+            b["episode_starts"][k].copy_(self._last_done)
+            for who, o in (("sort", self._sort_out), ("press", self._press_out)):
+                b[f"{who}_actions"][k].copy_(o["action"])
+                b[f"{who}_log_probs"][k].copy_(o["logp"])
+                b[f"{who}_values"][k].copy_(o["value"])
+            # applied without sanitising (env_monolith.py:254-257): the masked step
+            _, rew, done, _ = env.step(11 * self._sort_out["action"] + self._press_out["action"], check_overflow=check_overflow)
+            b["rewards"][k].copy_(rew)
+            self._last_done.copy_(done)
+        t = env.policy_step
+        last_s = self.sort_agent.forward(env.sort_agent_obs(), None, seed=self.sort_seed, t=t, deterministic=True,
+                                         index_offset=env.index_offset)
+        last_p = self.press_agent.forward(env.press_agent_obs(), None, seed=self.press_seed, t=t, deterministic=True,
+                                          index_offset=env.index_offset)
+        b["sort_last_values"].copy_(last_s["value"])
+        b["press_last_values"].copy_(last_p["value"])
+        b["last_dones"].copy_(self._last_done)
         return b

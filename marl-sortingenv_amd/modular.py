@@ -1,0 +1,82 @@
+"""Training the modular pair in the env it is deployed in.
+
+The reference trains its sorting agent in Env_1 (random press actions) and its pressing agent in Env_2 (a frozen
+sorter), then judges the pair in Env_3_Monolith.step(mode='model'), which neither saw.  `ModularTrainer` alternates
+one modular collection in Env_3 (`FusedModularRollout`: both agents act side by side, one launch) with one
+`PPOLearner.update` per agent on that agent's view of the rollout - each on its own reward component, or both on the
+team reward.  An agent without a learner is frozen: it acts by argmax and its weights are never touched.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+from .learner import PPOLearner
+
+AGENTS = ("sort", "press")
+
+
+class ModularTrainer:
+    """collector: a `FusedModularRollout` (or its twin, with reward="team").  sort_learner / press_learner: the
+    `PPOLearner` of that agent, or None to freeze it; at least one, and each over the collector's own agent.
+    reward: "own" - each learner trains on its agent's component of the step reward - or "team", both on the sum."""
+
+    def __init__(self, collector, sort_learner: Optional[PPOLearner] = None, press_learner: Optional[PPOLearner] = None,
+                 reward: str = "own"):
+        if sort_learner is None and press_learner is None:
+            raise ValueError("at least one learner is required")
+        if reward not in ("own", "team"):
+            raise ValueError(f"reward must be 'own' or 'team', not {reward!r}")
+        if sort_learner is not None and sort_learner.policy is not collector.sort_agent:
+            raise ValueError("sort_learner must train the collector's sort_agent")
+        if press_learner is not None and press_learner.policy is not collector.press_agent:
+            raise ValueError("press_learner must train the collector's press_agent")
+        self.collector, self.reward = collector, reward
+        self.learners = {"sort": sort_learner, "press": press_learner}
+        self.episode_stats = None  # learn(episode_stats=True): the EpisodeStats whose carry spans the iterations
+
+    def learn(self, iterations: int, callback=None, episode_stats: bool = False, eval_env=None, eval_freq: int = 0,
+              n_eval_episodes: int = 10, first_iteration: int = 0) -> list:
+        """Per iteration one `collect()` (a frozen agent deterministic), then `update(view(...))` on each learner present
+        with `progress_remaining = 1 - (it + 1) / iterations`, as `PPOLearner.learn` sets it.  Returns one record per
+        iteration: {"sort": mean stats, "press": mean stats} for the learners present, "reward" (the team reward per
+        env-step), "reward_sort", "reward_press" (its parts; absent when the collector does not fill them).
+        episode_stats=True: `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in that rollout, on
+        the team reward.  eval_env (an Env_3 handle of its own) with eval_freq > 0: every eval_freq-th record gains
+        `eval_mean_reward` / `eval_std_reward` from `evaluate_rollout(eval_env, "model", ...)` with both agents - the
+        reference's "PPO Modular" scenario."""
+        from .episodes import EpisodeStats, evaluate_rollout
+
+        col = self.collector
+        if not 0 <= int(first_iteration) <= int(iterations):
+            raise ValueError(f"first_iteration must be in [0, iterations = {int(iterations)}], not {first_iteration!r}")
+        evaluating = eval_env is not None and int(eval_freq) > 0
+        history = []
+        for it in range(int(first_iteration), int(iterations)):
+            data = col.collect(sort_deterministic=self.learners["sort"] is None,
+                               press_deterministic=self.learners["press"] is None)
+            if episode_stats:
+                n = data["rewards"].shape[1]
+                if self.episode_stats is None or self.episode_stats.num_envs != n:
+                    self.episode_stats = EpisodeStats(n, col.env.device)
+                self.episode_stats.reset_totals()
+                self.episode_stats.update(data)
+            rec = {"reward": float(data["rewards"].mean())}
+            for who in AGENTS:
+                if data.get(f"rewards_{who}") is not None:
+                    rec[f"reward_{who}"] = float(data[f"rewards_{who}"].mean())
+            progress = 1.0 - (it + 1) / int(iterations)
+            for who in AGENTS:
+                learner = self.learners[who]
+                if learner is not None:
+                    rec[who] = learner.update(col.view(who, self.reward), progress_remaining=progress)["mean"]
+            if episode_stats:
+                t = self.episode_stats.totals()
+                rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
+            if evaluating and (it + 1) % int(eval_freq) == 0:
+                mean, std = evaluate_rollout(eval_env, "model", n_eval_episodes=n_eval_episodes, sort_agent=col.sort_agent,
+                                             press_agent=col.press_agent, press_agent_maskable=col.press_masked)
+                rec.update(eval_mean_reward=mean, eval_std_reward=std)
+            history.append(rec)
+            if callback is not None:
+                callback(it, rec)
+        return history

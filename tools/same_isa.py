@@ -2,8 +2,10 @@
 
     python tools/same_isa.py OLD.s NEW.s
 
-For every kernel it compares the instruction lines (comments and assembler directives stripped, labels kept) and the
-kernel's metadata: VGPR / AGPR / SGPR counts, spill counts, private and group segment sizes.  It prints one summary line
+For every kernel, matched by its mangled name, it compares the instruction lines (comments and assembler directives
+stripped, labels kept - but without the function's ordinal in the listing, which the compiler writes into every local
+label (.LBB17_4, .LJTI17_0): a kernel added in front of others shifts that number and nothing else) and the kernel's
+metadata: VGPR / AGPR / SGPR counts, spill counts, private and group segment sizes.  It prints one summary line
 and, for each kernel that differs, its name and both instruction counts.  Exit status 1 on any difference, a kernel
 present in only one listing included.  A refactor of the device code is checked with this instead of a timing run."""
 import re
@@ -11,6 +13,9 @@ import sys
 
 META = (".agpr_count", ".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr_spill_count",
         ".private_segment_fixed_size", ".group_segment_fixed_size")
+
+
+ORDINAL = re.compile(r"\.L([A-Za-z_]+?)\d+_(\d+)")  # .LBB<function ordinal>_<block> -> .LBB_<block>
 
 
 def kernels(path):
@@ -33,7 +38,8 @@ def kernels(path):
         name = l.split(":")[0]
         if name in meta and l.startswith(name + ":"):
             end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
-            text = [t for t in (b.split(";")[0].strip() for b in lines[i + 1:end]) if t and (t[0] != "." or t.endswith(":"))]
+            text = [ORDINAL.sub(r".L\1_\2", t) for t in (b.split(";")[0].strip() for b in lines[i + 1:end])
+                    if t and (t[0] != "." or t.endswith(":"))]
             out[name] = (text, tuple(meta[name].get(k) for k in META))
     return out
 

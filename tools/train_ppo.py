@@ -19,6 +19,10 @@
                                                           # one file after every 5th iteration: learner, envs, history
     python tools/train_ppo.py --kind mono --iterations 20 --resume run_10.pt   # the same command line plus --resume:
                                                           # iterations 10 .. 19 of the same run, bit for bit
+    python tools/train_ppo.py --kind modular --reward own --eval-every 10   # the sorting (13 -> 2) and the pressing agent
+                                                          # (16 -> 11) side by side in Env_3, each on its own reward
+                                                          # component (--reward team: both on the sum); the evaluation
+                                                          # is the reference's "PPO Modular" scenario
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -205,9 +209,50 @@ def time_arithmetic(args):
                 for f, ts in times.items()) + f"; fma / matrix {worst:.2f} .. {best:.2f}")
 
 
+def train_modular(args):
+    """--kind modular: both agents in Env_3_Monolith, one FusedModularRollout and one PPOLearner each (ModularTrainer)."""
+    if args.time or args.resume or args.checkpoint:
+        raise SystemExit("--kind modular takes neither --time nor --checkpoint / --resume")
+    sort_ag = M.MlpPolicy.random_init(13, 2, seed=args.seed, precision="f16x3")
+    press_ag = M.MlpPolicy.random_init(16, 11, seed=args.seed + 1, precision="f16x3")
+    env = M.BatchedSortingEnv(kind="mono", num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
+                              auto_reset=True)
+    col = M.FusedModularRollout(env, sort_ag, press_ag, args.steps, sort_seed=args.seed, press_seed=args.seed + 1)
+    lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
+    clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    learners = [M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
+                             seed=args.seed + i, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
+                             arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
+                for i, pol in enumerate((sort_ag, press_ag))]
+    print(f"Env_3_Monolith, sorting agent (13 -> 2) + pressing agent (16 -> 11), reward={args.reward}, {args.envs} envs x "
+          f"{args.steps} steps per iteration")
+
+    def show(it, rec):
+        print(f"it {it:3d} reward/step {rec['reward']:+.4f} = sort {rec['reward_sort']:+.4f} + press {rec['reward_press']:+.4f}")
+        for who in ("sort", "press"):
+            r = rec[who]
+            print(f"       {who:5s} loss {r['loss']:+.4f} pg {r['policy_loss']:+.4f} vf {r['value_loss']:.4f} "
+                  f"ent {-r['entropy_loss']:.3f} kl {r['approx_kl']:.4f} clip {r['clip_fraction']:.3f}")
+        if "episodes" in rec:
+            print(f"       episodes {rec['episodes']:6d} ep_rew_mean {rec['ep_rew_mean']:+.3f} ep_len_mean {rec['ep_len_mean']:.1f}")
+        if "eval_mean_reward" in rec:
+            print(f"       eval (mode='model', both agents) {rec['eval_mean_reward']:+.3f} +- {rec['eval_std_reward']:.3f}")
+
+    eval_env = None
+    if args.eval_every > 0:
+        eval_env = M.BatchedSortingEnv(kind="mono", num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
+                                       auto_reset=True)
+    M.ModularTrainer(col, learners[0], learners[1], reward=args.reward).learn(
+        args.iterations, callback=show, episode_stats=args.episode_stats, eval_env=eval_env, eval_freq=args.eval_every)
+    if args.save:
+        torch.save({"sort_agent": sort_ag.state_dict(), "press_agent": press_ag.state_dict()}, args.save)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", choices=sorted(KINDS), default="mono")
+    ap.add_argument("--kind", choices=sorted(KINDS) + ["modular"], default="mono")
+    ap.add_argument("--reward", choices=("own", "team"), default="own",
+                    help="--kind modular: each agent trains on its own component of the step reward, or both on the sum")
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--iterations", type=int, default=20)
@@ -249,6 +294,8 @@ def main():
                          "started with (a differing hyperparameter or env is refused by name)")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
+    if args.kind == "modular":
+        return train_modular(args)
     if args.time:
         for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic)):
             if args.time_section in ("all", name):
