@@ -553,6 +553,39 @@ int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev
                             int32_t *control_dev /* NULL: no gate */, int arithmetic /* 0 fma, 1 matrix */,
                             const float *old_values /* f32[n_rows] or NULL */, double clip_range_vf);
 
+/* Behaviour cloning: the cross-entropy of DEMONSTRATED actions (the rule-based controller's, mse_rule_actions) under the
+ * policy's masked softmax, its statistics and the gradient of its loss, for one minibatch.  weights_dev, n_rows, rows_dev,
+ * batch, obs, mask, grad_out, workspace and stream are mse_ppo_loss_grad's, with its clamping of row indices.
+ *   actions      i32[n_rows]: the demonstrated action of every row, clamped into [0, A)
+ *   returns      f32[n_rows] or NULL.  NULL: actor only - the critic contributes nothing, value_loss is 0 and the
+ *                gradient of every critic weight is exactly 0
+ *   params       ent_coef and vf_coef are read; clip_range and normalize_advantage are ignored
+ *   arithmetic   0: fmaf chains (k_ppo_grad), 1: matrix cores (k_ppo_grad_matrix); each its behaviour-cloning instantiation
+ * Per row, float32 with every operation rounded separately (csrc/mse_ppo_math.h, bc_head_terms): the actor's 2 x 32 tanh
+ * MLP forward; illegal actions at logit -1e8; m = max logit, lse = m + log(sum exp(logit - m)); lp[a] = logit[a] - lse and
+ * p[a] = exp(lp[a]) for legal a, p[a] = 0 otherwise; entropy = -sum p[a] lp[a]; mass = sum p[a]; rest = mass - entropy.
+ * usable = the demonstrated action is legal under the mask:
+ *   ce = usable ? -lp[action] : 0;      g = usable ? -1 / batch : 0
+ *   d loss / d logit[a] = g (onehot(a == action) - p[a]) + ent_coef / batch (p[a] (lp[a] + 1) - p[a] rest)   for legal a, else 0
+ *   hit = usable and argmax of the masked logits == action (ties to the lowest index: the policy head's deterministic rule)
+ * so a row whose demonstrated action the mask forbids adds 0 to the cross-entropy and its gradient and 1 to `unusable`,
+ * and keeps its entropy term.  With returns the critic is mse_ppo_loss_grad's: e = value - returns, value_loss = mean(e^2),
+ * d loss / d value = vf_coef * 2 * e / batch.
+ *   bc_loss = mean(ce) over the batch (unusable rows counting 0);  entropy_loss = -mean(entropy)
+ *   loss = bc_loss + ent_coef entropy_loss + vf_coef value_loss
+ *   stats_out    f32[8]: loss, bc_loss, value_loss, entropy_loss, accuracy = hits / batch, unusable rows / batch, 0, 1
+ * Two launches (the gradient kernel, then mse_ppo_loss_grad's reduction; there is no advantage pass), the grid rule, the
+ * slab sums in a fixed order without atomics: equal inputs give bit-equal outputs.  The two arithmetics agree within
+ * rounding; accuracy and unusable are counts and agree exactly wherever the argmax is not a float32 near-tie.
+ * Checks, all before any device call, in this order: null arguments (weights_dev, obs, actions, params, grad_out,
+ * stats_out, workspace); dimensions outside 1..32; struct_size; n_rows < 1, batch < 1 or batch > n_rows without rows_dev;
+ * ent_coef or vf_coef not finite; workspace not 16-byte aligned (MSE_ERR_ALIGNMENT); arithmetic outside {0, 1}; no device
+ * (MSE_ERR_NO_DEVICE).  The others are MSE_ERR_INVALID_ARGUMENT. */
+int mse_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,
+                     const float *obs, const uint8_t *mask /* or NULL */, const int32_t *actions,
+                     const float *returns /* or NULL: actor only */, const mse_ppo_params *params, float *grad_out,
+                     float *stats_out, void *workspace, void *stream, int arithmetic /* 0 fma, 1 matrix */);
+
 /* SB3's train/explained_variance: 1 - var(returns - values) / var(returns) over n rows (all K * N of a rollout), population
  * variances, NaN when var(returns) is 0 (n = 1, constant returns).  csrc/mse_ppo_math.h specifies the arithmetic
  * completely; in short: the differences returns - values are formed in double from the f32 inputs; sums and sums of

@@ -30,6 +30,7 @@ EXPORTS = [
     "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
     "mse_ppo_loss_grad_matrix",
     "mse_ppo_loss_grad_vclip", "mse_explained_variance_workspace_bytes", "mse_explained_variance", "mse_explained_variance_host",
+    "mse_bc_loss_grad",
 ]
 
 _other_libs: dict = {}
@@ -164,6 +165,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
     L.mse_ppo_loss_grad_matrix.argtypes = L.mse_ppo_loss_grad_gated.argtypes
     L.mse_ppo_loss_grad_vclip.argtypes = L.mse_ppo_loss_grad_gated.argtypes + [C.c_int, vp, C.c_double]
+    L.mse_bc_loss_grad.argtypes = [C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, vp, C.c_int]
     L.mse_explained_variance_workspace_bytes.argtypes = []
     L.mse_explained_variance_workspace_bytes.restype = i64
     L.mse_explained_variance.argtypes = [i64, vp, vp, vp, vp, vp]

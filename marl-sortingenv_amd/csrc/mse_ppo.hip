@@ -1,5 +1,6 @@
 // The second half of PPO on the device: returns and advantages (mse_gae), the clipped-surrogate loss of one minibatch
-// with its gradient w.r.t. all weights (mse_ppo_loss_grad; with SB3's clip_range_vf, mse_ppo_loss_grad_vclip), clip_grad_norm_
+// with its gradient w.r.t. all weights (mse_ppo_loss_grad; with SB3's clip_range_vf, mse_ppo_loss_grad_vclip; the behaviour-
+// cloning loss of demonstrated actions in the same kernels' BC instantiations, mse_bc_loss_grad), clip_grad_norm_
 // + Adam (mse_ppo_adam_step), the counter-based permutation that orders an epoch's rows into minibatches (mse_ppo_shuffle, and
 // its host twin) and SB3's train/explained_variance of a rollout (mse_explained_variance, and its host twin).  The
 // per-row arithmetic lives in mse_ppo_math.h (host + device); this file holds the kernels and the C ABI.  gfx950 only.
@@ -185,7 +186,11 @@ __device__ __forceinline__ void store_layer(float *out, const LayerAcc &L, int l
 }
 
 // VCLIP: SB3's clip_range_vf (value_head_terms_clipped on old_values[row]); false never reads old_values
-template <int DP, int AP, bool VCLIP>
+// BC: behaviour cloning (mse_bc_loss_grad).  The actor's head is bc_head_terms on actions[row], the demonstrated action, and
+// its four sums are ce, entropy, hits, unusable rows (slab cells 0, 2, 3, 4); old_logp, adv and adv_partial are never read
+// (G.n_adv_partial is 0).  The critic is value_head_terms on ret[row], or, with ret == NULL, takes no tile at all: its sums
+// and its half of the slab are the zeros its accumulators start from.  false is the kernel as it was without the flag.
+template <int DP, int AP, bool VCLIP, bool BC = false>
 __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__restrict__ weights, const long long *__restrict__ rows,
                                                   const float *__restrict__ obs, const uint8_t *__restrict__ mask,
                                                   const int *__restrict__ actions, const float *__restrict__ old_logp,
@@ -217,7 +222,8 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
     float *strip = strips + wave * kStageFloats;
     LayerAcc L1 = {}, L2 = {}, L3 = {}; // first, second hidden layer, head
     float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f;
-    const long long n_tiles = (G.batch + 63) / 64;
+    long long n_tiles = (G.batch + 63) / 64;
+    if constexpr (BC) n_tiles = critic && ret == nullptr ? 0 : n_tiles; // wave-uniform: no returns, nothing for the critic
     for (long long tile = (long long)blockIdx.x * 2 + (wave >> 1); tile < n_tiles; tile += (long long)gridDim.x * 2) {
         // the weights are re-read from LDS every tile: an offset the compiler cannot see through keeps it from hoisting
         // ~5 000 wave-uniform values out of the loop into (spilled) scalar registers
@@ -242,18 +248,30 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
                 const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
                 legal |= (ok ? 1u : 0u) << a;
             }
-            const int action = clamped_action(actions[row], A);
-            const float a_raw = adv[row];
-            const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
-            hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
             float dl[AP];
-            head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
-            const PolicyTerms t = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
-            if (valid) {
-                st0 += t.surrogate;
-                st1 += t.entropy;
-                st2 += t.kl;
-                st3 += t.clipped;
+            if constexpr (BC) {
+                hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
+                head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
+                const BcTerms t = bc_head_terms<AP>(dl, A, legal, actions[row], G.P, inv_b);
+                if (valid) {
+                    st0 += t.ce;
+                    st1 += t.entropy;
+                    st2 += t.hit;
+                    st3 += t.unusable;
+                }
+            } else {
+                const int action = clamped_action(actions[row], A);
+                const float a_raw = adv[row];
+                const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
+                hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
+                head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
+                const PolicyTerms t = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
+                if (valid) {
+                    st0 += t.surrogate;
+                    st1 += t.entropy;
+                    st2 += t.kl;
+                    st3 += t.clipped;
+                }
             }
             accumulate_layer(strip, lane, dl, h2, L3.w, L3.b);
             backprop<AP>(wl + PW::act_w, dl, h2, dz);
@@ -459,6 +477,17 @@ void launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *wei
                            old_logp, adv, ret, adv_partial, slabs, control, old_values);
 }
 
+// enqueues the BC instantiation of k_ppo_grad: no old log-probabilities, advantages, gate or old values
+template <int DP, int AP>
+void launch_grad_bc(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                    const uint8_t *mask, const int *actions, const float *ret, float *slabs)
+{
+    const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
+    hipLaunchKernelGGL((k_ppo_grad<DP, AP, false, true>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                       (const float *)nullptr, (const float *)nullptr, ret, (const double *)nullptr, slabs, (const int *)nullptr,
+                       (const float *)nullptr);
+}
+
 // mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated, mse_ppo_loss_grad_matrix (matrix: the gradient launch is
 // k_ppo_grad_matrix of mse_ppo_matrix.hip; everything around it is the same) and mse_ppo_loss_grad_vclip (old_values != NULL:
 // the gradient launch is the VCLIP instantiation with clip_range_vf, which the entry point has checked); `who` names the
@@ -615,6 +644,52 @@ int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev
                      advantages, returns, params, grad_out, stats_out, workspace, stream,
                      control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, arithmetic, old_values,
                      clip_range_vf);
+}
+
+int mse_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,
+                     const float *obs, const uint8_t *mask, const int32_t *actions, const float *returns,
+                     const mse_ppo_params *params, float *grad_out, float *stats_out, void *workspace, void *stream, int arithmetic)
+{
+    auto fail = [](int status, const char *why) { return mse_internal_fail(status, (std::string("mse_bc_loss_grad: ") + why).c_str()); };
+    if (weights_dev == nullptr || obs == nullptr || actions == nullptr || params == nullptr || grad_out == nullptr ||
+        stats_out == nullptr || workspace == nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "obs_dim and n_actions must be in 1..32");
+    if (params->struct_size != sizeof(mse_ppo_params))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_params.struct_size mismatch");
+    if (n_rows < 1 || batch < 1 || (rows_dev == nullptr && batch > n_rows))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need 1 <= batch (<= n_rows without rows_dev)");
+    if (!std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "bad ent_coef / vf_coef");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0)
+        return fail(MSE_ERR_ALIGNMENT, "workspace must be 16-byte aligned");
+    if (arithmetic != 0 && arithmetic != 1) return fail(MSE_ERR_INVALID_ARGUMENT, "arithmetic must be 0 (fma) or 1 (matrix)");
+    const int cus = cu_count();
+    if (cus <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *adv_partial = static_cast<double *>(workspace); // the workspace's layout is mse_ppo_loss_grad's; these are not used
+    float *slabs = reinterpret_cast<float *>(adv_partial + 2 * kMaxAdvPartials);
+    const long long *rows = reinterpret_cast<const long long *>(rows_dev);
+    // clip_range and normalize_advantage are not read; n_adv_partial = 0: k_ppo_reduce writes stats_out[6..7] = 0, 1
+    const GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch, 0, Params{0.0f, params->ent_coef, params->vf_coef, 0, 0.0f}};
+    const int n_slabs = (int)grad_groups(batch, cus);
+    hipError_t e = hipSuccess;
+    if (arithmetic == 1) {
+        e = mse_ppo_launch_grad_matrix_bc(G, n_slabs, s, weights_dev, rows, obs, mask, actions, returns, slabs);
+    } else {
+#define MSE_BC_LAUNCH(DP, AP) launch_grad_bc<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, returns, slabs)
+        MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_BC_LAUNCH);
+#undef MSE_BC_LAUNCH
+    }
+    if (e == hipSuccess) {
+        const int w_total = flat_layout(obs_dim, n_actions).total;
+        hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, n_slabs, w_total, slabs, rows,
+                           (const float *)nullptr, adv_partial, grad_out, stats_out, Gate{nullptr, 0.0});
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
 }
 
 int64_t mse_explained_variance_workspace_bytes(void) { return (int64_t)(kEvMaxGroups * 4 * sizeof(double)); }

@@ -17,7 +17,9 @@ namespace mseppo {
 // A workgroup of a gradient kernel stores ONE slab into the workspace: the W floats of its gradient in the flat order of
 // include/mse.h, then kStatFloats floats of statistics (sums over the workgroup's rows; k_ppo_reduce divides by the batch):
 //   0 surrogate   1 squared value error   2 entropy   3 kl   4 clipped   5 the gate cell (slab 0 only)   6, 7 zero
-// k_ppo_reduce sums the slabs in slab order in double.
+// k_ppo_reduce sums the slabs in slab order in double.  The behaviour-cloning instantiations (BC, mse_bc_loss_grad) keep the
+// protocol and fill the same cells with their own sums, so k_ppo_reduce serves them as it stands:
+//   0 cross-entropy   1 squared value error   2 entropy   3 hits   4 unusable rows   5 the gate cell, always 0   6, 7 zero
 constexpr int kMaxSlabs = 512; // workgroups of a gradient kernel at most (two per CU on 256 CUs)
 constexpr int kStatFloats = 8;
 constexpr int kStatSums = 5; // cells 0 .. 4 are sums
@@ -153,3 +155,8 @@ hipError_t mse_ppo_launch_grad_matrix(const mseppo::GradArgs &G, int n_slabs, hi
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                       const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
                                       float *slabs, const int *control, const float *old_values);
+// ... the BC instantiation of k_ppo_grad_matrix (behaviour cloning: `actions` are the demonstrated ones; ret may be NULL, the
+// critic then takes no tile); it writes what the BC instantiation of k_ppo_grad writes
+hipError_t mse_ppo_launch_grad_matrix_bc(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+                                         const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
+                                         const float *ret, float *slabs);

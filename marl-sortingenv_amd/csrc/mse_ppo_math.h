@@ -6,6 +6,8 @@
 //   gae_column          RolloutBuffer.compute_returns_and_advantage, one env, every operation separately rounded
 //   policy_head_terms   MaskableCategorical (illegal logits at -1e8), log-prob / entropy, the clipped surrogate of
 //                       MaskablePPO.train and the gradient of  policy_loss + ent_coef * entropy_loss  w.r.t. the logits
+//   bc_head_terms       behaviour cloning: the cross-entropy of a demonstrated action under the same masked softmax, its
+//                       accuracy / unusable-row counts and the gradient of  ce + ent_coef * entropy_loss  (restates no SB3 code)
 //   value_head_terms    F.mse_loss(returns, values) and its gradient
 //   value_head_terms_clipped   the same for PPO.train's clip_range_vf: values clipped to within c of the rollout's
 //   ev_groups / ev_lane_sums / ev_from_sums   explained_variance(values, returns), the sums and their order in full
@@ -341,6 +343,71 @@ MSE_PPO_HD PolicyTerms policy_head_terms(float (&logit)[AP], int A, uint32_t leg
     t.kl = (ratio - 1.0f) - log_ratio;
     t.clipped = fabsf(ratio - 1.0f) > P.clip_range ? 1.0f : 0.0f;
     const float g_logp = s1 <= s2 ? -(adv * ratio) * inv_b : 0.0f;
+    const float ge = P.ent_coef * inv_b, rest = mass - ent; // sum over legal a of p (log p + 1)
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float onehot = a == action ? 1.0f : 0.0f;
+        const float d = g_logp * (onehot - p[a]) + ge * (p[a] * (logit[a] + 1.0f) - p[a] * rest);
+        logit[a] = ok ? d : 0.0f;
+    }
+    return t;
+}
+
+// ---- behaviour cloning: the cross-entropy of a demonstrated action under the same masked softmax -----------------------------
+struct BcTerms {
+    float ce;       // -log p(action), 0 where the demonstrated action is illegal under the mask
+    float entropy;  // -sum over legal actions of p log p
+    float hit;      // 1 where the row is usable and the argmax of the masked logits is the demonstrated action
+    float unusable; // 1 where the demonstrated action is illegal under the mask
+};
+
+// logit[a] (a < A real, the rest padding) -> terms; on return logit[] holds
+//   d/d logit of ( ce + ent_coef * (-entropy) ) * inv_b             (0 for illegal actions and for the padding).
+// float32, every operation rounded separately; the softmax, lse, p[a], lp[a], entropy, mass and rest are those of
+// policy_head_terms.  `action` is clamped into [0, A) first (clamped_action's rule).  usable = bit `action` of legal:
+//   ce = usable ? -lp[action] : 0;   g_logp = usable ? -inv_b : 0
+//   logit[a] = g_logp (onehot - p[a]) + ent_coef inv_b (p[a] (lp[a] + 1) - p[a] rest)      for legal a
+// so a row whose demonstrated action the mask forbids teaches nothing, yet keeps its entropy term.  The argmax is over the
+// masked f32 logits, ties to the lowest index: the rule of the policy head's deterministic mode.
+template <int AP>
+MSE_PPO_HD BcTerms bc_head_terms(float (&logit)[AP], int A, uint32_t legal, int action, const Params &P, float inv_b)
+{
+    action = action < 0 ? 0 : (action >= A ? A - 1 : action);
+    float m = -INFINITY;
+    int best = 0;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        if (a < A) {
+            logit[a] = ((legal >> a) & 1u) ? logit[a] : kMaskedLogit;
+            best = logit[a] > m ? a : best;
+            m = fmaxf(m, logit[a]);
+        }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a)
+        if (a < A) s += expf(logit[a] - m);
+    const float lse = m + logf(s);
+    float p[AP];
+    float ent = 0.0f, mass = 0.0f, logp_act = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float lp = logit[a] - lse;
+        p[a] = ok ? expf(lp) : 0.0f;
+        logit[a] = ok ? lp : 0.0f; // now the log-probability
+        ent -= ok ? p[a] * lp : 0.0f;
+        mass += p[a];
+        if (a == action) logp_act = lp;
+    }
+    const bool usable = ((legal >> action) & 1u) != 0;
+    BcTerms t;
+    t.ce = usable ? -logp_act : 0.0f;
+    t.entropy = ent;
+    t.hit = usable && best == action ? 1.0f : 0.0f;
+    t.unusable = usable ? 0.0f : 1.0f;
+    const float g_logp = usable ? -inv_b : 0.0f;
     const float ge = P.ent_coef * inv_b, rest = mass - ent; // sum over legal a of p (log p + 1)
 #pragma unroll
     for (int a = 0; a < AP; ++a) {

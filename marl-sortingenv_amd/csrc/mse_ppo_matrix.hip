@@ -155,7 +155,9 @@ __device__ __forceinline__ void store_value_head(float *out, const LayerGrad &L,
 }
 
 // VCLIP: SB3's clip_range_vf (value_head_terms_clipped on old_values[row]); false never reads old_values
-template <int DP, int AP, bool VCLIP>
+// BC: behaviour cloning, as in k_ppo_grad: bc_head_terms on the demonstrated action with the sums ce, entropy, hits, unusable;
+// old_logp, adv and adv_partial are never read; with ret == NULL the critic's waves take no tile.  false: the kernel as it was.
+template <int DP, int AP, bool VCLIP, bool BC = false>
 __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float *__restrict__ weights,
                                                          const long long *__restrict__ rows, const float *__restrict__ obs,
                                                          const uint8_t *__restrict__ mask, const int *__restrict__ actions,
@@ -198,7 +200,8 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
     for (int r = 0; r < 16; ++r) L1.w[r] = L2.w[r] = L3.w[r] = 0.0f;
     L1.b = L2.b = L3.b = 0.0f;
     float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f;
-    const long long n_tiles = (G.batch + 63) / 64;
+    long long n_tiles = (G.batch + 63) / 64;
+    if constexpr (BC) n_tiles = critic && ret == nullptr ? 0 : n_tiles; // wave-uniform: no returns, nothing for the critic
     for (long long tile = (long long)blockIdx.x * 2 + (wave >> 1); tile < n_tiles; tile += (long long)gridDim.x * 2) {
         // the image is re-read from LDS every tile: an offset the compiler cannot see through keeps it from hoisting the
         // operands of one tile's products out of the loop into registers it does not have
@@ -276,15 +279,25 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
                 const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
                 legal |= (ok ? 1u : 0u) << a;
             }
-            const int action = clamped_action(actions[row], A);
-            const float a_raw = adv[row];
-            const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
-            const PolicyTerms pt = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
-            if (valid) {
-                st0 += pt.surrogate;
-                st1 += pt.entropy;
-                st2 += pt.kl;
-                st3 += pt.clipped;
+            if constexpr (BC) {
+                const BcTerms bt = bc_head_terms<AP>(dl, A, legal, actions[row], G.P, inv_b);
+                if (valid) {
+                    st0 += bt.ce;
+                    st1 += bt.entropy;
+                    st2 += bt.hit;
+                    st3 += bt.unusable;
+                }
+            } else {
+                const int action = clamped_action(actions[row], A);
+                const float a_raw = adv[row];
+                const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
+                const PolicyTerms pt = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
+                if (valid) {
+                    st0 += pt.surrogate;
+                    st1 += pt.entropy;
+                    st2 += pt.kl;
+                    st3 += pt.clipped;
+                }
             }
             // deltas: row layout -> accumulator layout (a lane overwrites the row it read; actions AP .. 31 are zero)
 #pragma unroll
@@ -401,7 +414,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
     if (tid == 0) store_slab_stats(slab + F.total, misc);
 }
 
-template <int DP, int AP, bool VCLIP>
+template <int DP, int AP, bool VCLIP, bool BC = false>
 hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
                   const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
                   const double *adv_partial, float *slabs, const int *control, const float *old_values)
@@ -412,12 +425,12 @@ hipError_t launch(const GradArgs &G, int n_slabs, hipStream_t s, const float *we
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorNoDevice;
     if (dev < 0 || dev >= 64 || !allowed[dev].load(std::memory_order_relaxed)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad_matrix<DP, AP, VCLIP>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ppo_grad_matrix<DP, AP, VCLIP, BC>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) allowed[dev].store(true, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL((k_ppo_grad_matrix<DP, AP, VCLIP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
+    hipLaunchKernelGGL((k_ppo_grad_matrix<DP, AP, VCLIP, BC>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
                        actions, old_logp, adv, ret, adv_partial, slabs, control, old_values);
     return hipGetLastError();
 }
@@ -439,5 +452,18 @@ hipError_t mse_ppo_launch_grad_matrix(const GradArgs &G, int n_slabs, hipStream_
                                     control, old_values)
     MSE_PPO_DISPATCH(select_grad_shape(G.D, G.A), MSE_PPO_MATRIX_LAUNCH);
 #undef MSE_PPO_MATRIX_LAUNCH
+    return e;
+}
+
+hipError_t mse_ppo_launch_grad_matrix_bc(const GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+                                         const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
+                                         const float *ret, float *slabs)
+{
+    hipError_t e = hipErrorInvalidValue;
+#define MSE_BC_MATRIX_LAUNCH(DP, AP)                                                                                              \
+    e = launch<DP, AP, false, true>(G, n_slabs, stream, weights, rows, obs, mask, actions, nullptr, nullptr, ret, nullptr, slabs, \
+                                    nullptr, nullptr)
+    MSE_PPO_DISPATCH(select_grad_shape(G.D, G.A), MSE_BC_MATRIX_LAUNCH);
+#undef MSE_BC_MATRIX_LAUNCH
     return e;
 }

@@ -23,6 +23,11 @@
                                                           # (16 -> 11) side by side in Env_3, each on its own reward
                                                           # component (--reward team: both on the sum); the evaluation
                                                           # is the reference's "PPO Modular" scenario
+    python tools/train_ppo.py --kind mono --pretrain rule_based --pretrain-iterations 20 --eval-every 10
+                                                          # clone the env's rule-based controller first (ImitationLearner on
+                                                          # a DemonstrationCollector), then PPO from the cloned weights;
+                                                          # --kind modular clones both agents from their own views
+    python tools/train_ppo.py --time --time-section bc    # mse_bc_loss_grad beside mse_ppo_loss_grad, both arithmetics
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -209,12 +214,66 @@ def time_arithmetic(args):
                 for f, ts in times.items()) + f"; fma / matrix {worst:.2f} .. {best:.2f}")
 
 
+def time_bc(args):
+    """`mse_bc_loss_grad` beside `mse_ppo_loss_grad` on Env_3's shape at 4 096, 65 536 and 2^20 rows, both arithmetics:
+    rows_dev = NULL, one warm-up, then back-to-back calls ending in one synchronise, the time per call; the four calls
+    alternating, three timed repetitions each.  The cloning call gets the PPO rollout's rows with the rule's labels."""
+    D, A = M.OBS_DIM["mono"], M.NUM_ACTIONS["mono"]
+    K = 16
+    for rows in (4096, 65536, 2 ** 20):
+        n = rows // K
+        pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+        env = M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+        data = M.compute_gae(M.FusedPolicyRollout(env, pol, K, seed=args.seed).collect())
+        demo_env = M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+        demo = M.DemonstrationCollector(demo_env, K).collect()
+        stats = torch.zeros(8, device="cuda")
+        calls = 20 if rows <= 65536 else 5
+        group = {}
+        for f in ("fma", "matrix"):
+            group[f"ppo {f}"] = (M.PPOLearner(pol, ent_coef=0.05, arithmetic=f), data)
+            group[f"bc {f}"] = (M.ImitationLearner(pol, ent_coef=0.05, arithmetic=f), demo)
+        times = {name: [] for name in group}
+        for r in range(4):
+            for name, (lrn, d) in group.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    lrn.loss_grad(d, None, rows, stats)
+                torch.cuda.synchronize()
+                if r > 0:
+                    times[name].append((time.perf_counter() - t0) / calls)
+        print(f"mono rows={rows}: loss_grad " + ", ".join(f"{name} " + " / ".join(f"{t * 1e6:.1f}" for t in ts) + " us"
+                                                           for name, ts in times.items()))
+
+
+def pretrain(args, pol, env_kind, agent, name):
+    """--pretrain rule_based: clone the env's rule-based controller into `pol` before PPO (DemonstrationCollector on envs
+    of its own, ImitationLearner); the PPO learner constructed afterwards starts from the cloned weights."""
+    env = M.BatchedSortingEnv(kind=env_kind, num_envs=args.envs, device=0, base_seed=args.seed + 2 * 10 ** 6,
+                              max_steps=args.max_steps, auto_reset=True)
+    col = M.DemonstrationCollector(env, args.steps, agent=agent)
+    il = M.ImitationLearner(pol, learning_rate=args.pretrain_lr, n_epochs=args.pretrain_epochs, batch_size=args.batch_size,
+                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, arithmetic=args.arithmetic)
+    print(f"cloning the rule-based controller into {name} ({pol.obs_dim} -> {pol.n_actions}): {args.pretrain_iterations} "
+          f"iterations of {args.envs} envs x {args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}")
+
+    def show(it, rec):
+        print(f"bc {it:3d} reward/step of the expert {rec['reward']:+.4f} loss {rec['loss']:+.4f} bc {rec['bc_loss']:.4f} "
+              f"vf {rec['value_loss']:.4f} accuracy {rec['accuracy']:.4f} unusable {rec['unusable']:.4f}")
+
+    return il.learn(col, args.pretrain_iterations, callback=show)
+
+
 def train_modular(args):
     """--kind modular: both agents in Env_3_Monolith, one FusedModularRollout and one PPOLearner each (ModularTrainer)."""
     if args.time or args.resume or args.checkpoint:
         raise SystemExit("--kind modular takes neither --time nor --checkpoint / --resume")
     sort_ag = M.MlpPolicy.random_init(13, 2, seed=args.seed, precision="f16x3")
     press_ag = M.MlpPolicy.random_init(16, 11, seed=args.seed + 1, precision="f16x3")
+    if args.pretrain:
+        pretrain(args, sort_ag, "mono", "sort", "the sorting agent")
+        pretrain(args, press_ag, "mono", "press", "the pressing agent")
     env = M.BatchedSortingEnv(kind="mono", num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
     col = M.FusedModularRollout(env, sort_ag, press_ag, args.steps, sort_seed=args.seed, press_seed=args.seed + 1)
@@ -242,6 +301,9 @@ def train_modular(args):
     if args.eval_every > 0:
         eval_env = M.BatchedSortingEnv(kind="mono", num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
                                        auto_reset=True)
+        if args.pretrain:
+            mean, std = M.evaluate_rollout(eval_env, "model", sort_agent=sort_ag, press_agent=press_ag, press_agent_maskable=col.press_masked)
+            print(f"cloned pair, before PPO: eval (mode='model', both agents) {mean:+.3f} +- {std:.3f}")
     M.ModularTrainer(col, learners[0], learners[1], reward=args.reward).learn(
         args.iterations, callback=show, episode_stats=args.episode_stats, eval_env=eval_env, eval_freq=args.eval_every)
     if args.save:
@@ -282,8 +344,15 @@ def main():
                     help="linear: the clip range 0.2 times progress_remaining")
     ap.add_argument("--explained-variance", action="store_true",
                     help="print SB3's train/explained_variance of each rollout's values against its returns")
+    ap.add_argument("--pretrain", choices=("rule_based",), default=None,
+                    help="clone the env's rule-based controller into the policy first (ImitationLearner), then run PPO from there; "
+                         "--kind modular clones the sorting and the pressing agent from their own views of Env_3")
+    ap.add_argument("--pretrain-iterations", type=int, default=20, metavar="N",
+                    help="with --pretrain: collections of --envs x --steps demonstrations, each followed by one update")
+    ap.add_argument("--pretrain-epochs", type=int, default=4, help="with --pretrain: epochs per update")
+    ap.add_argument("--pretrain-lr", type=float, default=1e-3, help="with --pretrain: the cloning learning rate")
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic"), default="all",
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc"), default="all",
                     help="with --time: run one block of the timings only")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
                     help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
@@ -297,7 +366,8 @@ def main():
     if args.kind == "modular":
         return train_modular(args)
     if args.time:
-        for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic)):
+        for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic),
+                         ("bc", time_bc)):
             if args.time_section in ("all", name):
                 fn(args)
         return
@@ -308,6 +378,8 @@ def main():
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
     clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    if args.pretrain and not args.resume:  # a resumed run's weights come from its checkpoint
+        pretrain(args, pol, args.kind, "own", "the policy")
     learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
                            arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
@@ -335,6 +407,9 @@ def main():
         eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
                                        auto_reset=True)
         eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
+        if args.pretrain and not args.resume:
+            mean, std = M.evaluate_policy(eval_col)
+            print(f"cloned policy, before PPO: eval {mean:+.3f} +- {std:.3f}")
     first, history = 0, None
     if args.resume:
         ck = M.load_checkpoint(args.resume, learner=learner, collector=col)
