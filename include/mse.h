@@ -402,6 +402,63 @@ int mse_rollout_modular(mse_env *env, mse_policy *sort_agent, mse_policy *press_
 int mse_rollout_modular_check(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps,
                               uint64_t sort_seed, uint64_t press_seed, uint32_t flags);
 
+/* ---- Demonstrations on the states a student visits (DAgger): K steps in ONE launch in which the rule-based controller
+ * labels every visited state and, per env and step, either its action or a student policy's is stepped.
+ * Per step k and env i, in this order:
+ *   1. the rows the decision is taken from: observations f32[K,N,D], action_masks u8[K,N,A] (action_masks() of that
+ *      state) and episode_starts u8[K,N] (current_step == 0);
+ *   2. the label: the flat rule-based action for that state, exactly what mse_rule_actions returns for it; it consumes
+ *      no draw from any stream                                                                       (labels i32[K,N]);
+ *   3. the student's action = policy(observation) over the mask bits, drawn with the word of (seed, global env index,
+ *      t + k); with MSE_DEMO_ACTOR_DETERMINISTIC the argmax;
+ *   4. who steps: w = the policy stream's word of (mix_seed, global env index, t + k) (csrc/mse_policy_stream.h: the
+ *      word at t + k under the key of mix_seed and the index); the expert's action is
+ *      stepped iff (w >> 8) < expert_threshold, else the student's.  expert_threshold is an integer in [0, 2^24]:
+ *      0 = the student always steps, 2^24 = the expert always steps; integers are compared, nothing is rounded
+ *      (mse_demo_who_steps_host is the same rule on the host);
+ *   5. that action is stepped as mse_step steps it without MSE_STEP_UNMASKED, MSE_STEP_CHECK_OVERFLOW honoured,
+ *      auto-reset on termination; Env_2's sorting decision is sorting_rules();
+ *   6. stepped_actions i32[K,N], expert_stepped u8[K,N] (1: the expert's action was stepped), rewards f32[K,N], and
+ *      after the last step last_dones u8[N].
+ * actor == NULL: there is no student (no network, no matrix-core work); the expert always steps, expert_stepped is all
+ * ones, and seed / mix_seed / expert_threshold select nothing (the threshold is still range-checked).
+ * Any output pointer may be NULL.  The state is written back once; the policy step counter advances by K.  Serves the
+ * three env kinds with a policy of the env's own dimensions (13 -> 2, 16 -> 11, 29 -> 22) in both precision forms (the
+ * exact-f32 form in the 64-env shape, as in mse_rollout_policy's plain kernel).
+ * Bit-identical to K rounds of: read the observation and mask; mse_rule_actions; mse_policy_forward(seed, t = the
+ * handle's policy step counter, index_offset = the env's); the who-steps rule above; mse_step - in actions, labels,
+ * rows, rewards, flags, final mse_get_state record and step counter.
+ * Refusals, made before any device call, in this order: MSE_ERR_INVALID_ARGUMENT - a NULL env or out; a wrong
+ * struct_size; k_steps < 1; actor dimensions other than the env's, or an actor on another device; expert_threshold >
+ * 2^24; mix_seed == seed with a non-NULL actor (who steps and what the student draws would come from one word); a flag
+ * other than MSE_STEP_CHECK_OVERFLOW / MSE_DEMO_ACTOR_DETERMINISTIC (MSE_STEP_UNMASKED included); a handle without
+ * auto_reset=1 or not yet reset; an attached trace; observations / action_masks not 16-byte aligned.
+ * MSE_ERR_UNSUPPORTED_CONFIG - literal_choice, general generator mode, tables that do not fit the kernel's LDS image.
+ * Every one of them, this entry point's own statuses: a handle not yet reset and a misaligned row buffer are invalid
+ * arguments here. */
+#define MSE_DEMO_ACTOR_DETERMINISTIC 512u
+typedef struct mse_demo_buffers {
+    uint32_t struct_size; /* = sizeof(mse_demo_buffers); ABI check */
+    uint32_t reserved0;
+    float   *observations;
+    uint8_t *action_masks;
+    uint8_t *episode_starts;
+    int32_t *labels;
+    int32_t *stepped_actions;
+    uint8_t *expert_stepped;
+    float   *rewards;
+    uint8_t *last_dones;
+} mse_demo_buffers;
+int mse_rollout_demo(mse_env *env, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                     uint32_t expert_threshold, uint32_t flags, const mse_demo_buffers *out, void *stream);
+/* The status mse_rollout_demo would return for these arguments, its checks on `out` left out (MSE_OK or one of the
+ * refusals above, with its message in mse_last_error), without launching anything or touching the handle. */
+int mse_rollout_demo_check(mse_env *env, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                           uint32_t expert_threshold, uint32_t flags);
+/* Step 4 on the host, no device needed: out[j] = 1 iff the expert steps env index_offset + j at step counter t. */
+int mse_demo_who_steps_host(int64_t n, int64_t index_offset, uint64_t mix_seed, uint64_t t, uint32_t expert_threshold,
+                            uint8_t *out);
+
 /* Replaces the device image of `policy` with new weights (same flat order as mse_policy_create), repacked by the same
  * host routine, including the f16 range check: a policy in the "auto" form moves to f32 when a folded weight leaves
  * f16's range and back when all fit again; one pinned to f16x3 refuses such weights (MSE_ERR_UNSUPPORTED_CONFIG, image

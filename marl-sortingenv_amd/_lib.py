@@ -11,6 +11,7 @@ MSE_STEP_UNMASKED, MSE_STEP_CHECK_OVERFLOW, MSE_ROLLOUT_RULE_BASED, MSE_STEP_SAN
 MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_NO_PRESS_DRAW = 16, 32
 MSE_MODEL_PRESS_AGENT_MASKED = 64
 MSE_MODULAR_SORT_DETERMINISTIC, MSE_MODULAR_PRESS_DETERMINISTIC = 128, 256
+MSE_DEMO_ACTOR_DETERMINISTIC = 512
 MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
@@ -31,6 +32,7 @@ EXPORTS = [
     "mse_ppo_loss_grad_matrix",
     "mse_ppo_loss_grad_vclip", "mse_explained_variance_workspace_bytes", "mse_explained_variance", "mse_explained_variance_host",
     "mse_bc_loss_grad",
+    "mse_rollout_demo", "mse_rollout_demo_check", "mse_demo_who_steps_host",
 ]
 
 _other_libs: dict = {}
@@ -77,6 +79,16 @@ MODULAR_BUFFER_NAMES = ("sort_obs", "press_obs", "press_masks", "episode_starts"
 class MseModularBuffers(C.Structure):
     """struct mse_modular_buffers (include/mse.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(name, C.c_void_p) for name in MODULAR_BUFFER_NAMES]
+
+
+# the pointer members of struct mse_demo_buffers, in the header's order
+DEMO_BUFFER_NAMES = ("observations", "action_masks", "episode_starts", "labels", "stepped_actions", "expert_stepped",
+                     "rewards", "last_dones")
+
+
+class MseDemoBuffers(C.Structure):
+    """struct mse_demo_buffers (include/mse.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(name, C.c_void_p) for name in DEMO_BUFFER_NAMES]
 
 
 _lib = None
@@ -148,6 +160,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_modular.argtypes = [vp, vp, vp, i32, u64, u64, u32, C.POINTER(MseModularBuffers), vp]
     L.mse_rollout_modular_check.argtypes = [vp, vp, vp, i32, u64, u64, u32]
+    L.mse_rollout_demo.argtypes = [vp, vp, i32, u64, u64, u32, u32, C.POINTER(MseDemoBuffers), vp]
+    L.mse_rollout_demo_check.argtypes = [vp, vp, i32, u64, u64, u32, u32]
+    L.mse_demo_who_steps_host.argtypes = [i64, i64, u64, u64, u32, vp]
     L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
     L.mse_policy_set_weights_device.argtypes = [vp, vp, vp]
     L.mse_policy_sync.argtypes = [vp]

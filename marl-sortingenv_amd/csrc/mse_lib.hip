@@ -4,6 +4,7 @@
 //   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -std=c++17 -fPIC -shared -Iinclude \
 //         marl-sortingenv_amd/csrc/mse_lib.hip -o marl-sortingenv_amd/libmse_hip.so
 #include "mse_device.h"
+#include "mse_demo_mix.h" // after mse_device.h: MSE_HD needs the HIP runtime header
 #include "mse_host.h"
 #include "mse_plan.h"
 #include "mse_policy_device.h"
@@ -1992,6 +1993,132 @@ __global__ __launch_bounds__(512) void k_rollout_modular(Params P, uint4 *__rest
     }
 }
 
+// ==========================================================================================
+// Demonstration rollout: the rule-based controller labels every state a student (or a mixture of student and expert)
+// visits, K steps per launch (DESIGN.md "Demonstration rollout")
+//
+// k_rollout_policy's plain shape - one wave owns 32 TILES envs for the whole launch, the weight image and the tables in
+// LDS, the env state in registers, the same mirror lanes, phase priorities and row staging - with three things per
+// step instead of one: the label rule_based_action() of the state (what mse_rule_actions returns for it; no stream is
+// read), the student's action through msep::policy_tiles on the word of (seed, global env index, t + k), and the
+// integer decision of mse_demo_mix.h on the word of (mix_seed, global env index, t + k) which of the two is stepped.
+// ACTOR = false (no student): no weight image in LDS, no MFMA; the expert's action is stepped at every step.
+// LDS: [weights (ACTOR)][tables][per wave: obs tile (the mask tile reuses it) | bale ledger]
+// ==========================================================================================
+template <int KIND, bool NOISE, int TILES, bool F16X3, bool ACTOR>
+__global__ __launch_bounds__(512) void k_rollout_demo(Params P, uint4 *__restrict__ planes,
+                                                      const uint32_t *__restrict__ table_image,
+                                                      const float *__restrict__ weight_blob, int k_steps, uint64_t seed,
+                                                      uint64_t mix_seed, uint32_t expert_threshold, uint64_t policy_t0,
+                                                      uint32_t flags, const mse_demo_buffers out)
+{
+    using L = PolLayout<KIND, TILES>;
+    constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
+    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
+    float *lw = reinterpret_cast<float *>(lds);
+    constexpr int kWeightBytes = ACTOR ? L::weight_bytes : 0;
+    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
+    const int table_bytes = P.table_words * 4;
+    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
+    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
+    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
+    long long rem = P.n - wave_row0;
+    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
+    const bool wave_active = n_valid > 0;
+    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
+    // the batch's end its last env; mirrors store nothing
+    const int src_lane = TILES == 1 ? (lane & 31) : lane;
+    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
+    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
+
+    if (ACTOR) msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
+    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
+        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
+    const BaleRef bales{lbale + src_lane, ENVS};
+    if (P.track_bales && wave_active) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
+    }
+    Env e;
+    load_env<KIND, NOISE>(e, planes, P, i);
+    __syncthreads();
+    if (!wave_active) return;
+    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
+    const Tables tb = tables_at(ltab, P);
+    const msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
+    const bool deterministic = (flags & MSE_DEMO_ACTOR_DETERMINISTIC) != 0;
+    const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // stepped as mse_step steps it, masked
+
+    // the observation and mask of the current state (what reset / the previous launch left)
+    float o[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) o[j] = 0.0f;
+    int kcur[4];
+    container_purity_k(e, kcur);
+    env_obs<KIND>(e, P, tb, kcur, o);
+    uint32_t mbits = action_mask_bits<KIND>(e, P);
+    // the student's stream keys of the env(s) this lane serves as an MFMA column (k_rollout_policy); the mixture's key
+    // is the lane's own env's
+    const int h = lane >> 5, col = lane & 31;
+    const uint32_t key0 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + col));
+    const uint32_t key1 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
+    const uint32_t mix_key = mse_policy_key(mix_seed, (uint64_t)(P.index_offset + i));
+
+    const uint32_t lrow_obs = lds_row_address(reinterpret_cast<float *>(lwave) + src_lane * D);
+    const uint32_t lrow_mask = lds_row_address(lwave + src_lane * A);
+    int last_done = 0;
+    for (int s = 0; s < k_steps; ++s) {
+        if (ACTOR) __builtin_amdgcn_s_setprio(TILES == 2 ? 3 : 0); // policy phase (k_rollout_policy)
+        const long long srow = (long long)s * P.n + wave_row0;
+        const long long at = (long long)s * P.n + i;
+        const uint64_t t = policy_t0 + (uint64_t)s;
+        // the row the decision is taken from
+        if (out.observations != nullptr) wave_store_rows_f32<D, ENVS>(reinterpret_cast<float *>(lwave), lrow_obs, o, out.observations + srow * D, n_valid, lane);
+        if (out.action_masks != nullptr) wave_store_rows_mask<A, ENVS>(lwave, lrow_mask, mbits, out.action_masks + srow * A, n_valid, lane);
+        if (live && out.episode_starts != nullptr)
+            __builtin_nontemporal_store((uint8_t)(e.step == 0 ? 1 : 0), &out.episode_starts[at]);
+        // ---- the expert: sorting_rules() of the batch in the input stage, check_container_level() (policy_action)
+        const int label = rule_based_action<KIND>(e, Stage<false>::rule_mode(e.st_in, tb));
+        if (live && out.labels != nullptr) __builtin_nontemporal_store(label, &out.labels[at]);
+        // ---- the student, and who steps
+        int a = label;
+        bool expert = true;
+        if (ACTOR) {
+            float x[2][16];
+            operands_of(o, x);
+            uint32_t mb0, mb1;
+            msep::both_halves_u32(mbits, mb0, mb1);
+            const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
+            const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
+            msep::TileOut p[2];
+            msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, A, legal, deterministic, words, nullptr, p);
+            expert = mse_demo_expert_steps(mix_key, t, expert_threshold);
+            a = expert ? label : tile_pick<TILES>(h, p[0].action, p[1].action);
+            __builtin_amdgcn_s_setprio(TILES == 2 ? 0 : 3);
+        }
+        if (live) {
+            if (out.stepped_actions != nullptr) __builtin_nontemporal_store(a, &out.stepped_actions[at]);
+            if (out.expert_stepped != nullptr) __builtin_nontemporal_store((uint8_t)(expert ? 1 : 0), &out.expert_stepped[at]);
+        }
+        // ---- the env transition under that action, auto-reset on termination
+        StepResult r = env_step<KIND, NOISE, false>(e, P, tb, a, -1, step_flags, bales, kcur, o);
+        if (__builtin_expect(r.done != 0, 0)) {
+            auto_reset_env(e, P, tb, bales, kcur);
+            env_obs<KIND>(e, P, tb, kcur, o);
+        }
+        mbits = action_mask_bits<KIND>(e, P);
+        last_done = r.done;
+        if (live && out.rewards != nullptr) __builtin_nontemporal_store((float)r.reward, &out.rewards[at]);
+    }
+    if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
+    if (live) store_env<KIND, NOISE>(e, planes, P, i, false);
+    if (P.track_bales && live) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
+    }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_reset(Params P, uint4 *__restrict__ planes,
                                                   const uint32_t *__restrict__ table_image,
@@ -2540,6 +2667,29 @@ static void launch_rollout_modular(mse_env *h, const mse_policy *sort_ag, const 
     }, h->noise_on, plan.tiles == 1);
 }
 
+// mse_rollout_demo's shape: k_rollout_policy's plain one with one network, or with none (no actor: the f16x3 geometry)
+template <int KIND>
+static PolicyPlan plan_rollout_demo(const mse_env *h, const mse_policy *actor)
+{
+    return plan_policy_plain(h->P.n, h->cus, actor == nullptr || actor->use_f16(), actor != nullptr ? 1 : 0, policy_lds<KIND>(h->P));
+}
+
+// the caller has checked that the plan fits (rollout_demo_checks)
+template <int KIND>
+static void launch_rollout_demo(mse_env *h, const mse_policy *actor, hipStream_t s, int k_steps, uint64_t seed,
+                                uint64_t mix_seed, uint32_t expert_threshold, uint32_t flags, const mse_demo_buffers &out)
+{
+    const PolicyPlan plan = plan_rollout_demo<KIND>(h, actor);
+    with_flags([&](auto NOISE, auto ONE_TILE, auto F16, auto ACTOR) {
+        // the forms the plan gives: exact f32 in two tiles only; without an actor the precision names nothing
+        if constexpr ((F16 || !ONE_TILE) && (ACTOR || F16))
+            hipLaunchKernelGGL((k_rollout_demo<KIND, NOISE, ONE_TILE ? 1 : 2, F16, ACTOR>), dim3((unsigned)plan.workgroups),
+                               dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables,
+                               actor != nullptr ? actor->blob : nullptr, k_steps, seed, mix_seed, expert_threshold,
+                               h->policy_t, flags, out);
+    }, h->noise_on, plan.tiles == 1, actor == nullptr || actor->use_f16(), actor != nullptr);
+}
+
 // the checks the three rollout entry points share (`fn` names the entry point in the messages)
 static int rollout_checks(const mse_env *h, int32_t k_steps, const char *fn)
 {
@@ -2914,6 +3064,71 @@ int mse_rollout_modular(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, i
     launch_rollout_modular(h, sort_ag, press_ag, static_cast<hipStream_t>(stream), k_steps, sort_seed, press_seed, flags, *out);
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+// everything mse_rollout_demo refuses, in the order include/mse.h gives; `out` is looked at when `with_out` is set
+// (mse_rollout_demo_check has none)
+static int rollout_demo_checks(mse_env *h, const mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                               uint32_t expert_threshold, uint32_t flags, const mse_demo_buffers *out, bool with_out)
+{
+    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "env is NULL");
+    if (with_out && (!out || out->struct_size != sizeof(mse_demo_buffers)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "out is NULL or mse_demo_buffers.struct_size mismatch (header/library version skew)");
+    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
+    if (actor != nullptr && (actor->d_in != mse_obs_dim(h) || actor->n_act != mse_num_actions(h)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "the actor's observation / action dimensions do not match the env kind");
+    if (actor != nullptr && actor->device != h->device)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "actor and env live on different devices");
+    if (expert_threshold > MSE_DEMO_THRESHOLD_ONE)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "expert_threshold must be in [0, 2^24]");
+    if (actor != nullptr && mix_seed == seed)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mix_seed == seed: who steps and what the actor draws would come from one word");
+    if (flags & ~(MSE_STEP_CHECK_OVERFLOW | MSE_DEMO_ACTOR_DETERMINISTIC))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag (the stepped action is applied as the masked step applies it: no MSE_STEP_UNMASKED)");
+    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_demo needs auto_reset=1");
+    if (!h->seeded) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_demo before mse_reset(seeds)");
+    if (h->trace_rec != nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (with_out && (!aligned16(out->observations) || !aligned16(out->action_masks)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "observations / action_masks must be 16-byte aligned");
+    if (h->literal || h->P.gen_mode)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_demo serves the integer draw path with a remainder-free batch "
+                                                "(literal_choice or general generator mode: alternate mse_rule_actions, "
+                                                "mse_policy_forward and mse_step, as DemonstrationCollector does)");
+    const int fits = with_kind(h->P.env_kind, [&](auto KIND) { return plan_rollout_demo<KIND>(h, actor).status; });
+    if (fits != MSE_OK)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the demonstration rollout kernel's LDS image does not fit this config's tables");
+    return MSE_OK;
+}
+
+int mse_rollout_demo_check(mse_env *h, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                           uint32_t expert_threshold, uint32_t flags)
+{
+    return rollout_demo_checks(h, actor, k_steps, seed, mix_seed, expert_threshold, flags, nullptr, false);
+}
+
+int mse_rollout_demo(mse_env *h, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                     uint32_t expert_threshold, uint32_t flags, const mse_demo_buffers *out, void *stream)
+{
+    if (const int rc = rollout_demo_checks(h, actor, k_steps, seed, mix_seed, expert_threshold, flags, out, true)) return rc;
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        launch_rollout_demo<KIND>(h, actor, static_cast<hipStream_t>(stream), k_steps, seed, mix_seed, expert_threshold, flags, *out);
+    });
+    MSE_CHECK_LAUNCH();
+    h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+int mse_demo_who_steps_host(int64_t n, int64_t index_offset, uint64_t mix_seed, uint64_t t, uint32_t expert_threshold,
+                            uint8_t *out)
+{
+    if (n < 0 || index_offset < 0 || (n > 0 && out == nullptr))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_demo_who_steps_host: n and index_offset must be >= 0 and out non-NULL");
+    if (expert_threshold > MSE_DEMO_THRESHOLD_ONE)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_demo_who_steps_host: expert_threshold must be in [0, 2^24]");
+    for (int64_t j = 0; j < n; ++j)
+        out[j] = mse_demo_expert_steps(mse_policy_key(mix_seed, (uint64_t)(index_offset + j)), t, expert_threshold) ? 1 : 0;
     return MSE_OK;
 }
 

@@ -13,11 +13,12 @@ into a // 11 and a % 11); there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
 
-from ._lib import check
+from ._lib import (DEMO_BUFFER_NAMES, MSE_DEMO_ACTOR_DETERMINISTIC, MSE_STEP_CHECK_OVERFLOW, MseDemoBuffers, check)
 from .batched import BatchedSortingEnv
 from .learner import PPOLearner, _ptr, _stream
 from .policy import MlpPolicy
@@ -112,6 +113,88 @@ class DemonstrationCollector:
         return dict(b, last_dones=last_dones)
 
 
+def expert_threshold(beta: float) -> int:
+    """The integer `mse_rollout_demo` compares a draw's upper 24 bits with: int(round(beta * 2**24)), in [0, 2**24].
+    beta is the share of (env, step) pairs in which the expert's action is stepped; NaN and values outside [0, 1] are
+    refused."""
+    b = float(beta)
+    if math.isnan(b) or not 0.0 <= b <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], not {beta!r}")
+    return int(round(b * 2 ** 24))
+
+
+class FusedDemonstrationRollout:
+    """`DemonstrationCollector(agent="own")` in one launch (`mse_rollout_demo`): per step the expert labels the state,
+    the student `actor` acts on it (sampled with `seed`, or its argmax with deterministic_actor=True), and per env and
+    step the expert's action is stepped with probability `beta`, else the student's - the beta-mixture of DAgger, decided
+    by a word of `mix_seed`'s stream against `expert_threshold(beta)`.  beta = 0 is `DemonstrationCollector(actor=
+    student)`, beta = 1 steps what `DemonstrationCollector(actor=None)` steps.  `beta` may be set between calls; with
+    actor=None it must be 1.
+
+    `collect()` is that launch plus the one `mse_gae` launch for `returns`, and returns `DemonstrationCollector`'s dict
+    (`observations`, `action_masks`, `actions` = the labels, `stepped_actions`, `rewards`, `episode_starts`,
+    `last_dones`, `returns`) plus `expert_stepped` u8[K, N]; the buffers are allocated once.  The modular views ("sort" /
+    "press" on Env_3) stay with `DemonstrationCollector`.  The env's own obs / mask tensors are not refreshed."""
+
+    def __init__(self, env: BatchedSortingEnv, n_steps: int, actor: Optional[MlpPolicy] = None,
+                 deterministic_actor: bool = False, beta: Optional[float] = None, gamma: float = 0.99, seed: int = 2024,
+                 mix_seed: Optional[int] = None, check_overflow: bool = False):
+        if not env.auto_reset:
+            raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+        if int(n_steps) < 1:
+            raise ValueError("n_steps must be >= 1")
+        if actor is not None and (actor.obs_dim != env.obs_dim or actor.n_actions != env.num_actions):
+            raise ValueError(f"the actor must be a {env.obs_dim} -> {env.num_actions} policy")
+        self.env, self.actor = env, actor
+        self.deterministic_actor, self.gamma, self.check_overflow = bool(deterministic_actor), float(gamma), bool(check_overflow)
+        self.n_steps, self.seed = int(n_steps), int(seed)
+        self.mix_seed = self.seed + 1 if mix_seed is None else int(mix_seed)
+        if actor is not None and self.mix_seed == self.seed:
+            raise ValueError("mix_seed == seed: who steps and what the actor draws would come from one word")
+        self.beta = (1.0 if actor is None else 0.0) if beta is None else beta
+        n, K, dev = env.num_envs, self.n_steps, env.device
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        self.buffers = {
+            "observations": torch.empty((K, n, env.obs_dim), dtype=f32, device=dev),
+            "action_masks": torch.empty((K, n, env.num_actions), dtype=u8, device=dev),
+            "actions": torch.empty((K, n), dtype=i32, device=dev),
+            "stepped_actions": torch.empty((K, n), dtype=i32, device=dev),
+            "expert_stepped": torch.empty((K, n), dtype=u8, device=dev),
+            "rewards": torch.empty((K, n), dtype=f32, device=dev),
+            "episode_starts": torch.empty((K, n), dtype=u8, device=dev),
+            "last_dones": torch.empty((n,), dtype=u8, device=dev),
+            "returns": torch.empty((K, n), dtype=f32, device=dev),
+        }
+        self._zeros = torch.zeros((K + 1, n), dtype=f32, device=dev)  # mse_gae's values and last_values
+        self._adv = torch.empty((K, n), dtype=f32, device=dev)
+        b = self.buffers
+        self._out = MseDemoBuffers(C.sizeof(MseDemoBuffers), 0, *(b["actions" if name == "labels" else name].data_ptr()
+                                                                   for name in DEMO_BUFFER_NAMES))
+
+    @property
+    def beta(self) -> float:
+        return self._beta
+
+    @beta.setter
+    def beta(self, value: float) -> None:
+        threshold = expert_threshold(value)
+        if self.actor is None and threshold != 2 ** 24:
+            raise ValueError("without an actor the expert always steps: beta must be 1")
+        self._beta, self._threshold = float(value), threshold
+
+    def collect(self) -> dict:
+        env, b, K = self.env, self.buffers, self.n_steps
+        flags = (MSE_STEP_CHECK_OVERFLOW if self.check_overflow else 0) | \
+                (MSE_DEMO_ACTOR_DETERMINISTIC if self.deterministic_actor else 0)
+        with torch.cuda.device(env.device):
+            check(env.L.mse_rollout_demo(env._h, None if self.actor is None else self.actor._h, K, self.seed, self.mix_seed,
+                                         self._threshold, flags, C.byref(self._out), env._stream()))
+            check(env.L.mse_gae(K, env.num_envs, _ptr(b["rewards"]), _ptr(self._zeros), _ptr(b["episode_starts"]),
+                                _ptr(self._zeros[K]), _ptr(b["last_dones"]), self.gamma, 1.0, _ptr(self._adv), _ptr(b["returns"]),
+                                env._stream()))
+        return b
+
+
 class ImitationLearner(PPOLearner):
     """Supervised learning of demonstrated actions with the learner's own kernels.  The loss of a minibatch is
 
@@ -183,12 +266,16 @@ class ImitationLearner(PPOLearner):
         return {"stats": stats, "mean": dict(zip(BC_STAT_NAMES, mean))}
 
     def learn(self, collector, iterations: int, callback=None, eval_collector=None, eval_freq: int = 0,
-              n_eval_episodes: int = 10) -> list:
-        """Alternates `collector.collect()` (a `DemonstrationCollector`; one whose `actor` is this learner's policy
-        relabels the states the clone itself visits) and `update()`; returns the per-iteration mean statistics, each with
-        the collection's mean reward per env-step under "reward".  eval_collector (a `FusedPolicyRollout` over this
-        learner's policy and an env of its own) with eval_freq > 0: every eval_freq-th record gains `eval_mean_reward`
-        and `eval_std_reward` from `evaluate_policy(eval_collector, n_eval_episodes)`."""
+              n_eval_episodes: int = 10, beta=None) -> list:
+        """Alternates `collector.collect()` (a `DemonstrationCollector` or `FusedDemonstrationRollout`; one whose `actor`
+        is this learner's policy relabels the states the clone itself visits) and `update()`; returns the per-iteration
+        mean statistics, each with the collection's mean reward per env-step under "reward".  eval_collector (a
+        `FusedPolicyRollout` over this learner's policy and an env of its own) with eval_freq > 0: every eval_freq-th
+        record gains `eval_mean_reward` and `eval_std_reward` from `evaluate_policy(eval_collector, n_eval_episodes)`.
+        beta (a `FusedDemonstrationRollout`'s mixture): a number, or a function of the fraction of iterations done
+        (it / iterations, from 0 towards 1); it is written into `collector.beta` before each `collect()`, and each record
+        then carries `beta` and, under "expert_share", the share of rows the expert stepped.  None: nothing is set and
+        the records are as before."""
         from .episodes import evaluate_policy
 
         evaluating = eval_collector is not None and int(eval_freq) > 0
@@ -196,8 +283,12 @@ class ImitationLearner(PPOLearner):
             raise ValueError("eval_collector must run this learner's policy")
         history = []
         for it in range(int(iterations)):
+            if beta is not None:
+                collector.beta = float(beta(it / int(iterations)) if callable(beta) else beta)
             data = collector.collect()
             rec = dict(self.update(data)["mean"], reward=float(data["rewards"].mean()))
+            if beta is not None:
+                rec.update(beta=collector.beta, expert_share=float(data["expert_stepped"].float().mean()))
             if evaluating and (it + 1) % int(eval_freq) == 0:
                 mean, std = evaluate_policy(eval_collector, n_eval_episodes=n_eval_episodes)
                 rec.update(eval_mean_reward=mean, eval_std_reward=std)

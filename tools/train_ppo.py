@@ -28,6 +28,14 @@
                                                           # a DemonstrationCollector), then PPO from the cloned weights;
                                                           # --kind modular clones both agents from their own views
     python tools/train_ppo.py --time --time-section bc    # mse_bc_loss_grad beside mse_ppo_loss_grad, both arithmetics
+    python tools/train_ppo.py --kind mono --pretrain rule_based --dagger --beta-schedule linear --eval-every 10
+                                                          # DAgger: the clone (or a beta-mixture of clone and expert)
+                                                          # acts, the expert labels every visited state, in one launch
+                                                          # per collection (FusedDemonstrationRollout); --beta-schedule
+                                                          # one | linear | first: beta 1 throughout (pure cloning), 1 - the
+                                                          # fraction of iterations done, or 1 in the first iteration only
+    python tools/train_ppo.py --time --time-section demo  # collect() of FusedDemonstrationRollout beside
+                                                          # DemonstrationCollector(actor=student) and the plain policy rollout
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -247,28 +255,75 @@ def time_bc(args):
                                                            for name, ts in times.items()))
 
 
-def pretrain(args, pol, env_kind, agent, name):
+def time_demo(args):
+    """`collect()` of `FusedDemonstrationRollout` (beta 0, 0.5 and, without an actor, 1) beside its multi-launch twin
+    `DemonstrationCollector(actor=student)` and `FusedPolicyRollout` forced to the plain kernel (rollout_pipeline = 2: the
+    same loop without the label and the selection), Env_3, at 4 096 envs x 50 steps and 65 536 x 16: HIP events around
+    each call, one warm-up, then three timed calls each, the collectors alternating."""
+    D, A = M.OBS_DIM["mono"], M.NUM_ACTIONS["mono"]
+    pol = M.MlpPolicy.random_init(D, A, seed=args.seed, precision="f16x3")
+
+    def env(n, **kw):
+        return M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True, **kw)
+
+    for n, K in ((4096, 50), (65536, 16)):
+        group = {
+            "fused beta=0": M.FusedDemonstrationRollout(env(n), K, actor=pol, beta=0.0, seed=args.seed),
+            "fused beta=0.5": M.FusedDemonstrationRollout(env(n), K, actor=pol, beta=0.5, seed=args.seed),
+            "fused expert only": M.FusedDemonstrationRollout(env(n), K),
+            "twin actor=student": M.DemonstrationCollector(env(n), K, actor=pol, seed=args.seed),
+            "twin expert only": M.DemonstrationCollector(env(n), K),
+            "policy rollout (plain kernel)": M.FusedPolicyRollout(env(n, rollout_pipeline=2), pol, K, seed=args.seed),
+        }
+        times = {name: [] for name in group}
+        for r in range(4):
+            for name, col in group.items():
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                col.collect()
+                stop.record()
+                stop.synchronize()
+                if r > 0:
+                    times[name].append(start.elapsed_time(stop))
+        print(f"mono {n} envs x {K} steps: collect() " + ", ".join(
+            f"{name} " + " / ".join(f"{t:.3f}" for t in ts) + f" ms ({n * K / min(ts) / 1e3:.1f} M steps/s)" for name, ts in times.items()))
+
+
+BETA_SCHEDULES = {"one": 1.0, "linear": lambda f: 1.0 - f, "first": lambda f: 1.0 if f == 0.0 else 0.0}
+
+
+def pretrain(args, pol, env_kind, agent, name, eval_col=None):
     """--pretrain rule_based: clone the env's rule-based controller into `pol` before PPO (DemonstrationCollector on envs
     of its own, ImitationLearner); the PPO learner constructed afterwards starts from the cloned weights."""
     env = M.BatchedSortingEnv(kind=env_kind, num_envs=args.envs, device=0, base_seed=args.seed + 2 * 10 ** 6,
                               max_steps=args.max_steps, auto_reset=True)
-    col = M.DemonstrationCollector(env, args.steps, agent=agent)
+    if args.dagger:
+        col = M.FusedDemonstrationRollout(env, args.steps, actor=pol, beta=1.0, seed=args.seed + 7, mix_seed=args.seed + 8)
+    else:
+        col = M.DemonstrationCollector(env, args.steps, agent=agent)
     il = M.ImitationLearner(pol, learning_rate=args.pretrain_lr, n_epochs=args.pretrain_epochs, batch_size=args.batch_size,
                             seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, arithmetic=args.arithmetic)
     print(f"cloning the rule-based controller into {name} ({pol.obs_dim} -> {pol.n_actions}): {args.pretrain_iterations} "
-          f"iterations of {args.envs} envs x {args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}")
+          f"iterations of {args.envs} envs x {args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}"
+          + (f", DAgger with beta schedule '{args.beta_schedule}'" if args.dagger else ""))
 
     def show(it, rec):
-        print(f"bc {it:3d} reward/step of the expert {rec['reward']:+.4f} loss {rec['loss']:+.4f} bc {rec['bc_loss']:.4f} "
-              f"vf {rec['value_loss']:.4f} accuracy {rec['accuracy']:.4f} unusable {rec['unusable']:.4f}")
+        print(f"bc {it:3d} reward/step of the {'mixture' if args.dagger else 'expert'} {rec['reward']:+.4f} loss {rec['loss']:+.4f} "
+              f"bc {rec['bc_loss']:.4f} vf {rec['value_loss']:.4f} accuracy {rec['accuracy']:.4f} unusable {rec['unusable']:.4f}"
+              + (f" beta {rec['beta']:.3f} expert share {rec['expert_share']:.4f}" if "beta" in rec else "")
+              + (f" eval {rec['eval_mean_reward']:+.3f} +- {rec['eval_std_reward']:.3f}" if "eval_mean_reward" in rec else ""))
 
-    return il.learn(col, args.pretrain_iterations, callback=show)
+    return il.learn(col, args.pretrain_iterations, callback=show, eval_collector=eval_col,
+                    eval_freq=args.eval_every if eval_col is not None else 0,
+                    beta=BETA_SCHEDULES[args.beta_schedule] if args.dagger else None)
 
 
 def train_modular(args):
     """--kind modular: both agents in Env_3_Monolith, one FusedModularRollout and one PPOLearner each (ModularTrainer)."""
     if args.time or args.resume or args.checkpoint:
         raise SystemExit("--kind modular takes neither --time nor --checkpoint / --resume")
+    if args.dagger:
+        raise SystemExit("--dagger serves a policy of the env's own dimensions: the modular views have no fused collector")
     sort_ag = M.MlpPolicy.random_init(13, 2, seed=args.seed, precision="f16x3")
     press_ag = M.MlpPolicy.random_init(16, 11, seed=args.seed + 1, precision="f16x3")
     if args.pretrain:
@@ -351,8 +406,14 @@ def main():
                     help="with --pretrain: collections of --envs x --steps demonstrations, each followed by one update")
     ap.add_argument("--pretrain-epochs", type=int, default=4, help="with --pretrain: epochs per update")
     ap.add_argument("--pretrain-lr", type=float, default=1e-3, help="with --pretrain: the cloning learning rate")
+    ap.add_argument("--dagger", action="store_true",
+                    help="with --pretrain: the policy being cloned (or a beta-mixture of it and the expert) steps the envs and the "
+                         "expert labels every visited state, one launch per collection (FusedDemonstrationRollout)")
+    ap.add_argument("--beta-schedule", choices=sorted(BETA_SCHEDULES), default="linear",
+                    help="with --dagger: the share of steps the expert takes - 'one': all of them (pure cloning), 'linear': 1 minus "
+                         "the fraction of cloning iterations done, 'first': all in the first iteration, none afterwards")
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc"), default="all",
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo"), default="all",
                     help="with --time: run one block of the timings only")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
                     help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
@@ -367,7 +428,7 @@ def main():
         return train_modular(args)
     if args.time:
         for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic),
-                         ("bc", time_bc)):
+                         ("bc", time_bc), ("demo", time_demo)):
             if args.time_section in ("all", name):
                 fn(args)
         return
@@ -378,8 +439,13 @@ def main():
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
     clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    eval_col = None
+    if args.eval_every > 0:
+        eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
+                                       auto_reset=True)
+        eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
     if args.pretrain and not args.resume:  # a resumed run's weights come from its checkpoint
-        pretrain(args, pol, args.kind, "own", "the policy")
+        pretrain(args, pol, args.kind, "own", "the policy", eval_col if args.dagger else None)
     learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
                            arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
@@ -402,14 +468,9 @@ def main():
         if "eval_mean_reward" in rec:
             print(f"       eval {rec['eval_mean_reward']:+.3f} +- {rec['eval_std_reward']:.3f} (best {learner.best_mean_reward:+.3f})")
 
-    eval_col = None
-    if args.eval_every > 0:
-        eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
-                                       auto_reset=True)
-        eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
-        if args.pretrain and not args.resume:
-            mean, std = M.evaluate_policy(eval_col)
-            print(f"cloned policy, before PPO: eval {mean:+.3f} +- {std:.3f}")
+    if eval_col is not None and args.pretrain and not args.resume:
+        mean, std = M.evaluate_policy(eval_col)
+        print(f"cloned policy, before PPO: eval {mean:+.3f} +- {std:.3f}")
     first, history = 0, None
     if args.resume:
         ck = M.load_checkpoint(args.resume, learner=learner, collector=col)
