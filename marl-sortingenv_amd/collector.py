@@ -32,63 +32,96 @@ from .batched import BatchedSortingEnv
 from .policy import MlpPolicy
 
 
-def _check_collector(col, sd: dict, kind: str) -> None:
-    from .checkpoint import check_fingerprint
-
-    check_fingerprint({k: sd.get(k) for k in ("collector", "seed", "n_steps")},
-                      {"collector": kind, "seed": col.seed, "n_steps": col.n_steps}, type(col).__name__)
-    if not isinstance(sd.get("env"), dict):
-        raise ValueError(f"{type(col).__name__}: the checkpoint has no env state")
-    col.env.check_state_dict(sd["env"])
+F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+ROW_DTYPES = {"observations": F32, "action_masks": U8, "actions": I32, "log_probs": F32, "values": F32, "rewards": F32,
+              "episode_starts": U8, "last_values": F32, "last_dones": U8, "stepped_actions": I32, "expert_stepped": U8,
+              "returns": F32}
+POLICY_ROWS = ("observations", "action_masks", "actions", "log_probs", "values", "rewards", "episode_starts")
 
 
-class PolicyRolloutCollector:
+def rollout_buffers(env, K: int, last: bool = False, names=POLICY_ROWS, dims=None) -> dict:
+    """The `MaskableRolloutBuffer`-shaped dict of device tensors every single-policy collector fills: `names` in that
+    order, [K, N] each except `observations` [K, N, obs_dim], `action_masks` [K, N, n_actions] and the per-env rows
+    `last_values` / `last_dones` [N], which last=True appends.  dims: (obs_dim, n_actions) when they are not the env's."""
+    n, (obs_dim, n_actions) = env.num_envs, dims or (env.obs_dim, env.num_actions)
+    shapes = {"observations": (K, n, obs_dim), "action_masks": (K, n, n_actions), "last_values": (n,), "last_dones": (n,)}
+    names = tuple(names) + (("last_values", "last_dones") if last else ())
+    return {k: torch.empty(shapes.get(k, (K, n)), dtype=ROW_DTYPES[k], device=env.device) for k in names}
+
+
+def _check_policy_collector(env, policy, sort_policy) -> None:
+    """What `PolicyRolloutCollector` and `FusedPolicyRollout` refuse at construction."""
+    if policy.obs_dim != env.obs_dim or policy.n_actions != env.num_actions:
+        raise ValueError("policy dimensions do not match the env")
+    if sort_policy is not None and (env.kind != "press" or sort_policy.obs_dim != 13 or sort_policy.n_actions != 2):
+        raise ValueError("a sorting policy (13 -> 2) only applies to Env_2_Pressing")
+    if not env.auto_reset:
+        raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+
+
+class _CollectorState:
+    """The checkpoint surface of a collector (checkpoint.py): `KIND`, the `SEEDS` attributes, `n_steps` and the env's state
+    dict; a collector that carries more between calls adds it in `_extra_state` and extends check / load."""
+
+    KIND = None
+    SEEDS = ("seed",)
+
+    def _fingerprint(self) -> dict:
+        return {"collector": self.KIND, **{k: getattr(self, k) for k in self.SEEDS}, "n_steps": self.n_steps}
+
+    def _extra_state(self) -> dict:
+        return {}
+
+    def state_dict(self) -> dict:
+        """`KIND` under "collector", the seeds, `n_steps`, what `_extra_state` adds, and the env's state dict."""
+        return {**self._fingerprint(), **self._extra_state(), "env": self.env.state_dict()}
+
+    def check_state_dict(self, sd: dict) -> None:
+        """ValueError, with nothing touched, unless `sd` is this kind of collector's with these seeds and `n_steps` and
+        the env accepts its part."""
+        from .checkpoint import check_fingerprint
+
+        mine = self._fingerprint()
+        check_fingerprint({k: sd.get(k) for k in mine}, mine, type(self).__name__)
+        if not isinstance(sd.get("env"), dict):
+            raise ValueError(f"{type(self).__name__}: the checkpoint has no env state")
+        self.env.check_state_dict(sd["env"])
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.check_state_dict(sd)
+        self.env.load_state_dict(sd["env"])  # refreshes env.obs / env.mask, which a stepwise collect() starts from
+
+
+class PolicyRolloutCollector(_CollectorState):
+    KIND = "two_launch"
+
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, sort_policy: Optional[MlpPolicy] = None,
                  seed: int = 2024):
-        if policy.obs_dim != env.obs_dim or policy.n_actions != env.num_actions:
-            raise ValueError("policy dimensions do not match the env")
-        if sort_policy is not None and (env.kind != "press" or sort_policy.obs_dim != 13 or sort_policy.n_actions != 2):
-            raise ValueError("a sorting policy (13 -> 2) only applies to Env_2_Pressing")
-        if not env.auto_reset:
-            raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+        _check_policy_collector(env, policy, sort_policy)
         self.env, self.policy, self.sort_policy = env, policy, sort_policy
         self.n_steps, self.seed, self.t = int(n_steps), int(seed), 0
-        n, K, dev = env.num_envs, self.n_steps, env.device
-        self.buffers = {
-            "observations": torch.empty((K, n, env.obs_dim), dtype=torch.float32, device=dev),
-            "action_masks": torch.empty((K, n, env.num_actions), dtype=torch.uint8, device=dev),
-            "actions": torch.empty((K, n), dtype=torch.int32, device=dev),
-            "log_probs": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "values": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "rewards": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "episode_starts": torch.empty((K, n), dtype=torch.uint8, device=dev),
-        }
-        self._last_done = torch.ones((n,), dtype=torch.uint8, device=dev)  # the envs were just reset
+        self.buffers = rollout_buffers(env, self.n_steps)
+        self._last_done = torch.ones((env.num_envs,), dtype=torch.uint8, device=env.device)  # the envs were just reset
         self._out = None
         self._sort_out = None
 
-    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
-    def state_dict(self) -> dict:
-        """`seed`, `n_steps`, the policy stream's step `t`, the end marks of the last step (`_last_done`, the next
-        rollout's first `episode_starts`) and the env's state dict."""
+    # ---- checkpoint: _CollectorState plus the policy stream's step `t` and the end marks of the last step (`_last_done`,
+    # the next rollout's first `episode_starts`) -----------------------------------------------------------------------
+    def _extra_state(self) -> dict:
         from .checkpoint import cpu
 
-        return {"collector": "two_launch", "seed": self.seed, "n_steps": self.n_steps, "t": self.t,
-                "last_done": cpu(self._last_done), "env": self.env.state_dict()}
+        return {"t": self.t, "last_done": cpu(self._last_done)}
 
     def check_state_dict(self, sd: dict) -> None:
-        """ValueError, with nothing touched, unless `sd` is this kind of collector's with this `seed` and `n_steps` and
-        the env accepts its part."""
         from .checkpoint import check_tensor
 
-        _check_collector(self, sd, "two_launch")
+        super().check_state_dict(sd)
         check_tensor(sd, "last_done", self._last_done, "PolicyRolloutCollector")
         if isinstance(sd.get("t"), bool) or not isinstance(sd.get("t"), int) or sd["t"] < 0:
             raise ValueError(f"PolicyRolloutCollector: t must be a non-negative int, the checkpoint has {sd.get('t')!r}")
 
     def load_state_dict(self, sd: dict) -> None:
-        self.check_state_dict(sd)
-        self.env.load_state_dict(sd["env"])  # refreshes env.obs / env.mask, which the next collect() starts from
+        super().load_state_dict(sd)
         self.t = sd["t"]
         self._last_done.copy_(sd["last_done"])
 
@@ -119,50 +152,22 @@ class PolicyRolloutCollector:
         return dict(b, last_values=last["value"], last_dones=self._last_done.clone())
 
 
-class FusedPolicyRollout:
+class FusedPolicyRollout(_CollectorState):
     """K steps of policy forward + env transition per launch (`mse_rollout_policy`): MaskableRolloutBuffer-shaped
     device tensors [K, N, ...].  Env_2's sorting decisions: `sort_policy` (a 13 -> 2 MlpPolicy standing for the
-    pre-trained sorting agent, evaluated inside the kernel), else `sort_mode` (a per-env tensor), else the reference's rule."""
+    pre-trained sorting agent, evaluated inside the kernel), else `sort_mode` (a per-env tensor), else the reference's rule.
+    Checkpoint: _CollectorState's alone - the kernel derives `episode_starts` from the env state and reads the step counter
+    from the handle (`sort_mode`, a constructor argument, is given again at construction like the policies)."""
+
+    KIND = "fused"
 
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, seed: int = 2024,
                  sort_mode: Optional[torch.Tensor] = None, sort_policy: Optional[MlpPolicy] = None):
-        if policy.obs_dim != env.obs_dim or policy.n_actions != env.num_actions:
-            raise ValueError("policy dimensions do not match the env")
-        if sort_policy is not None and (env.kind != "press" or sort_policy.obs_dim != 13 or sort_policy.n_actions != 2):
-            raise ValueError("a sorting policy (13 -> 2) only applies to Env_2_Pressing")
-        if not env.auto_reset:
-            raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
+        _check_policy_collector(env, policy, sort_policy)
         self.env, self.policy, self.n_steps, self.seed = env, policy, int(n_steps), int(seed)
         self.sort_policy = sort_policy  # Env_2's pre-trained sorting agent, evaluated inside the kernel
         self.sort_mode = None if sort_mode is None else sort_mode.to(device=env.device, dtype=torch.int32).contiguous()
-        n, K, dev = env.num_envs, self.n_steps, env.device
-        self.buffers = {
-            "observations": torch.empty((K, n, env.obs_dim), dtype=torch.float32, device=dev),
-            "action_masks": torch.empty((K, n, env.num_actions), dtype=torch.uint8, device=dev),
-            "actions": torch.empty((K, n), dtype=torch.int32, device=dev),
-            "log_probs": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "values": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "rewards": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "episode_starts": torch.empty((K, n), dtype=torch.uint8, device=dev),
-            "last_values": torch.empty((n,), dtype=torch.float32, device=dev),
-            "last_dones": torch.empty((n,), dtype=torch.uint8, device=dev),
-        }
-
-    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
-    def state_dict(self) -> dict:
-        """`seed`, `n_steps` and the env's state dict: the kernel derives `episode_starts` from the env state and reads
-        the step counter from the handle, so the collector itself carries nothing else (`sort_mode`, a constructor
-        argument, is given again at construction like the policies)."""
-        return {"collector": "fused", "seed": self.seed, "n_steps": self.n_steps, "env": self.env.state_dict()}
-
-    def check_state_dict(self, sd: dict) -> None:
-        """ValueError, with nothing touched, unless `sd` is this kind of collector's with this `seed` and `n_steps` and
-        the env accepts its part."""
-        _check_collector(self, sd, "fused")
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.check_state_dict(sd)
-        self.env.load_state_dict(sd["env"])
+        self.buffers = rollout_buffers(env, self.n_steps, last=True)
 
     def collect(self, n_steps: Optional[int] = None, deterministic: bool = False, use_action_masking: bool = True,
                 check_overflow: bool = False) -> dict:
@@ -308,10 +313,12 @@ def modular_view(buffers: dict, who: str, reward: str = "own", press_masked: boo
     }
 
 
-class _ModularBase:
-    """Constructor, views and checkpoint surface the fused modular collector and its multi-launch twin share."""
+class _ModularBase(_CollectorState):
+    """Constructor and views the fused modular collector and its multi-launch twin share.  Checkpoint: _CollectorState's
+    with both seeds - the kernel derives `episode_starts` from the env state, which also carries the policy step counter."""
 
     KIND = "modular"
+    SEEDS = ("sort_seed", "press_seed")
     PARTS = True  # fills rewards_sort / rewards_press
 
     def __init__(self, env: BatchedSortingEnv, sort_agent: MlpPolicy, press_agent: MlpPolicy, n_steps: int,
@@ -336,29 +343,6 @@ class _ModularBase:
         if not 1 <= K <= self.n_steps:
             raise ValueError("n_steps must be in [1, the collector's K]")
         return K
-
-    # ---- checkpoint (checkpoint.py) ----------------------------------------------------------------------------------
-    def state_dict(self) -> dict:
-        """Both seeds, `n_steps` and the env's state dict (which carries the policy step counter): the kernel derives
-        `episode_starts` from the env state, so the collector carries nothing else."""
-        return {"collector": self.KIND, "sort_seed": self.sort_seed, "press_seed": self.press_seed, "n_steps": self.n_steps,
-                "env": self.env.state_dict()}
-
-    def check_state_dict(self, sd: dict) -> None:
-        """ValueError, with nothing touched, unless `sd` is this kind of collector's with these seeds and `n_steps` and
-        the env accepts its part."""
-        from .checkpoint import check_fingerprint
-
-        check_fingerprint({k: sd.get(k) for k in ("collector", "sort_seed", "press_seed", "n_steps")},
-                          {"collector": self.KIND, "sort_seed": self.sort_seed, "press_seed": self.press_seed,
-                           "n_steps": self.n_steps}, type(self).__name__)
-        if not isinstance(sd.get("env"), dict):
-            raise ValueError(f"{type(self).__name__}: the checkpoint has no env state")
-        self.env.check_state_dict(sd["env"])
-
-    def load_state_dict(self, sd: dict) -> None:
-        self.check_state_dict(sd)
-        self.env.load_state_dict(sd["env"])
 
 
 class FusedModularRollout(_ModularBase):

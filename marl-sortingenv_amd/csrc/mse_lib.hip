@@ -2702,6 +2702,13 @@ static int rollout_checks(const mse_env *h, int32_t k_steps, const char *fn)
     return MSE_OK;
 }
 
+// the refusal of everything but the integer draw path; `advice` says what to run instead
+static int integer_path_check(const mse_env *h, const char *fn, const char *advice)
+{
+    if (!h->literal && !h->P.gen_mode) return MSE_OK;
+    return fail(MSE_ERR_UNSUPPORTED_CONFIG, std::string(fn) + " serves the integer draw path with a remainder-free batch (" + advice + ")");
+}
+
 extern "C" {
 
 int mse_version(void) { return MSE_VERSION; }
@@ -2973,10 +2980,8 @@ int mse_rollout_policy(mse_env *h, mse_policy *pol, mse_policy *sort_pol, int32_
     }
     if ((obs_out && !aligned16(obs_out)) || (mask_out && !aligned16(mask_out)))
         return fail(MSE_ERR_ALIGNMENT, "obs_out / mask_out must be 16-byte aligned");
-    if (h->literal || h->P.gen_mode)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_policy serves the integer draw path with a remainder-free batch "
-                                                "(literal_choice, input_batch_size > 127 or with a floor() remainder: "
-                                                "alternate mse_policy_forward and mse_step)");
+    if (const int rc = integer_path_check(h, "mse_rollout_policy", "literal_choice, input_batch_size > 127 or with a floor() "
+                                                                  "remainder: alternate mse_policy_forward and mse_step")) return rc;
     const int rc = with_kind(h->P.env_kind, [&](auto KIND) {
         return launch_rollout_policy<KIND>(h, pol, sort_pol, static_cast<hipStream_t>(stream), k_steps, seed, deterministic,
                                            sort_mode, flags, obs_out, mask_out, actions_out, logp_out, value_out,
@@ -3008,11 +3013,9 @@ int mse_rollout_model(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, int
         return fail(MSE_ERR_ALIGNMENT, "obs_out / mask_out / sort_obs_out / press_obs_out must be 16-byte aligned");
     if ((sort_ag != nullptr && !sort_ag->use_f16()) || (press_ag != nullptr && !press_ag->use_f16()))
         return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the in-loop agents exist in the f16x3 form (mse_policy_set_precision)");
-    if (h->literal || h->P.gen_mode)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_model serves the integer draw path with a remainder-free batch "
-                                                "(literal_choice or general generator mode: alternate mse_sort_agent_obs / "
-                                                "mse_press_agent_obs, mse_policy_forward, mse_model_actions and mse_step, "
-                                                "as ModelRolloutCollector does)");
+    if (const int rc = integer_path_check(h, "mse_rollout_model", "literal_choice or general generator mode: alternate "
+                                          "mse_sort_agent_obs / mse_press_agent_obs, mse_policy_forward, mse_model_actions and "
+                                          "mse_step, as ModelRolloutCollector does")) return rc;
     const int rc = launch_rollout_model(h, sort_ag, press_ag, static_cast<hipStream_t>(stream), k_steps, flags, actions_out,
                                         obs_out, reward_out, done_out, mask_out, sort_obs_out, press_obs_out);
     if (rc != MSE_OK) return fail(rc, "the model rollout kernel's LDS image does not fit this config's tables");
@@ -3040,10 +3043,8 @@ static int rollout_modular_checks(mse_env *h, const mse_policy *sort_ag, const m
         return fail(MSE_ERR_INVALID_ARGUMENT, "sort_seed == press_seed: the two agents would draw from one word");
     if (!sort_ag->use_f16() || !press_ag->use_f16())
         return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the in-loop agents exist in the f16x3 form (mse_policy_set_precision)");
-    if (h->literal || h->P.gen_mode)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_modular serves the integer draw path with a remainder-free batch "
-                                                "(literal_choice or general generator mode: alternate mse_sort_agent_obs / "
-                                                "mse_press_agent_obs, mse_policy_forward and mse_step)");
+    if (const int rc = integer_path_check(h, "mse_rollout_modular", "literal_choice or general generator mode: alternate "
+                                          "mse_sort_agent_obs / mse_press_agent_obs, mse_policy_forward and mse_step")) return rc;
     if (plan_policy_plain(h->P.n, h->cus, true, 2, policy_lds<3>(h->P)).status != MSE_OK)
         return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the modular rollout kernel's LDS image does not fit this config's tables");
     return MSE_OK;
@@ -3092,10 +3093,8 @@ static int rollout_demo_checks(mse_env *h, const mse_policy *actor, int32_t k_st
         return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
     if (with_out && (!aligned16(out->observations) || !aligned16(out->action_masks)))
         return fail(MSE_ERR_INVALID_ARGUMENT, "observations / action_masks must be 16-byte aligned");
-    if (h->literal || h->P.gen_mode)
-        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_demo serves the integer draw path with a remainder-free batch "
-                                                "(literal_choice or general generator mode: alternate mse_rule_actions, "
-                                                "mse_policy_forward and mse_step, as DemonstrationCollector does)");
+    if (const int rc = integer_path_check(h, "mse_rollout_demo", "literal_choice or general generator mode: alternate "
+                                          "mse_rule_actions, mse_policy_forward and mse_step, as DemonstrationCollector does")) return rc;
     const int fits = with_kind(h->P.env_kind, [&](auto KIND) { return plan_rollout_demo<KIND>(h, actor).status; });
     if (fits != MSE_OK)
         return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the demonstration rollout kernel's LDS image does not fit this config's tables");

@@ -20,11 +20,15 @@ import torch
 
 from ._lib import (DEMO_BUFFER_NAMES, MSE_DEMO_ACTOR_DETERMINISTIC, MSE_STEP_CHECK_OVERFLOW, MseDemoBuffers, check)
 from .batched import BatchedSortingEnv
-from .learner import PPOLearner, _ptr, _stream
+from .collector import rollout_buffers
+from .learner import PPOLearner, _ptr, _stream, training_loop
 from .policy import MlpPolicy
 
 BC_STAT_NAMES = ("loss", "bc_loss", "value_loss", "entropy_loss", "accuracy", "unusable", "_", "_")
 AGENT_DIMS = {"sort": (13, 2), "press": (16, 11)}
+DEMO_ROWS = ("observations", "action_masks", "actions", "stepped_actions", "rewards", "episode_starts", "returns")
+FUSED_DEMO_ROWS = ("observations", "action_masks", "actions", "stepped_actions", "expert_stepped", "rewards", "episode_starts",
+                   "last_dones", "returns")
 
 
 class DemonstrationCollector:
@@ -60,15 +64,9 @@ class DemonstrationCollector:
         self.deterministic_actor, self.gamma = bool(deterministic_actor), float(gamma)
         self.n_steps, self.seed, self.t = int(n_steps), int(seed), 0
         n, K, dev = env.num_envs, self.n_steps, env.device
-        self.buffers = {
-            "observations": torch.empty((K, n, self.obs_dim), dtype=torch.float32, device=dev),
-            "action_masks": None if agent == "sort" else torch.empty((K, n, self.n_actions), dtype=torch.uint8, device=dev),
-            "actions": torch.empty((K, n), dtype=torch.int32, device=dev),
-            "stepped_actions": torch.empty((K, n), dtype=torch.int32, device=dev),
-            "rewards": torch.empty((K, n), dtype=torch.float32, device=dev),
-            "episode_starts": torch.empty((K, n), dtype=torch.uint8, device=dev),
-            "returns": torch.empty((K, n), dtype=torch.float32, device=dev),
-        }
+        self.buffers = rollout_buffers(env, K, names=DEMO_ROWS, dims=(self.obs_dim, self.n_actions))
+        if agent == "sort":
+            self.buffers["action_masks"] = None  # the sorter is not maskable
         self._zeros = torch.zeros((K + 1, n), dtype=torch.float32, device=dev)  # mse_gae's values and last_values
         self._adv = torch.empty((K, n), dtype=torch.float32, device=dev)
         self._last_done = torch.ones((n,), dtype=torch.uint8, device=dev)  # the envs were just reset
@@ -153,20 +151,9 @@ class FusedDemonstrationRollout:
             raise ValueError("mix_seed == seed: who steps and what the actor draws would come from one word")
         self.beta = (1.0 if actor is None else 0.0) if beta is None else beta
         n, K, dev = env.num_envs, self.n_steps, env.device
-        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
-        self.buffers = {
-            "observations": torch.empty((K, n, env.obs_dim), dtype=f32, device=dev),
-            "action_masks": torch.empty((K, n, env.num_actions), dtype=u8, device=dev),
-            "actions": torch.empty((K, n), dtype=i32, device=dev),
-            "stepped_actions": torch.empty((K, n), dtype=i32, device=dev),
-            "expert_stepped": torch.empty((K, n), dtype=u8, device=dev),
-            "rewards": torch.empty((K, n), dtype=f32, device=dev),
-            "episode_starts": torch.empty((K, n), dtype=u8, device=dev),
-            "last_dones": torch.empty((n,), dtype=u8, device=dev),
-            "returns": torch.empty((K, n), dtype=f32, device=dev),
-        }
-        self._zeros = torch.zeros((K + 1, n), dtype=f32, device=dev)  # mse_gae's values and last_values
-        self._adv = torch.empty((K, n), dtype=f32, device=dev)
+        self.buffers = rollout_buffers(env, K, names=FUSED_DEMO_ROWS)
+        self._zeros = torch.zeros((K + 1, n), dtype=torch.float32, device=dev)  # mse_gae's values and last_values
+        self._adv = torch.empty((K, n), dtype=torch.float32, device=dev)
         b = self.buffers
         self._out = MseDemoBuffers(C.sizeof(MseDemoBuffers), 0, *(b["actions" if name == "labels" else name].data_ptr()
                                                                    for name in DEMO_BUFFER_NAMES))
@@ -246,20 +233,9 @@ class ImitationLearner(PPOLearner):
         bs = max(1, min(int(bs), total))
         n_mb = self.n_epochs * ((total + bs - 1) // bs)
         stats = torch.zeros((n_mb, 8), dtype=torch.float32, device=self.device)
-        self.last_permutations, self.last_epochs = [], []
-        i = 0
-        for _ in range(self.n_epochs):
-            if self.shuffle == "device":
-                perm = self._device_permutation(total)
-            else:
-                perm_cpu = torch.randperm(total, generator=self.generator)
-                self.last_permutations.append(perm_cpu)
-                perm = perm_cpu.to(self.device)
-            for start in range(0, total, bs):
-                rows = perm[start:start + bs]
-                self.loss_grad(data, rows, rows.numel(), stats[i])
-                self.adam_step()
-                i += 1
+        for i, rows in enumerate(self._minibatches(total, bs)):
+            self.loss_grad(data, rows, rows.numel(), stats[i])
+            self.adam_step()
         self._hand_over()
         mean = stats.mean(dim=0).cpu().tolist()
         self.policy.sync()
@@ -276,26 +252,19 @@ class ImitationLearner(PPOLearner):
         (it / iterations, from 0 towards 1); it is written into `collector.beta` before each `collect()`, and each record
         then carries `beta` and, under "expert_share", the share of rows the expert stepped.  None: nothing is set and
         the records are as before."""
-        from .episodes import evaluate_policy
-
-        evaluating = eval_collector is not None and int(eval_freq) > 0
-        if evaluating and eval_collector.policy is not self.policy:
-            raise ValueError("eval_collector must run this learner's policy")
-        history = []
-        for it in range(int(iterations)):
+        def collect(it):
             if beta is not None:
                 collector.beta = float(beta(it / int(iterations)) if callable(beta) else beta)
-            data = collector.collect()
+            return collector.collect()
+
+        def step(data, progress_remaining):
             rec = dict(self.update(data)["mean"], reward=float(data["rewards"].mean()))
             if beta is not None:
                 rec.update(beta=collector.beta, expert_share=float(data["expert_stepped"].float().mean()))
-            if evaluating and (it + 1) % int(eval_freq) == 0:
-                mean, std = evaluate_policy(eval_collector, n_eval_episodes=n_eval_episodes)
-                rec.update(eval_mean_reward=mean, eval_std_reward=std)
-            history.append(rec)
-            if callback is not None:
-                callback(it, rec)
-        return history
+            return rec
+
+        return training_loop(iterations, collect, step, evaluate=self._evaluator(eval_collector, eval_freq, n_eval_episodes),
+                             eval_freq=eval_freq, callback=callback)
 
     def state_dict(self) -> dict:
         raise NotImplementedError("ImitationLearner is not checkpointed: save the policy's state_dict()")

@@ -25,6 +25,8 @@ from typing import Callable, Optional, Union
 import torch
 
 from ._lib import MsePpoParams, check, load_library
+from .checkpoint import format_path, save_checkpoint
+from .episodes import EpisodeStats, evaluate_policy
 from .policy import MlpPolicy
 
 STAT_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
@@ -77,6 +79,44 @@ def compute_gae(data: dict, gamma: float = 0.99, gae_lambda: float = 0.95) -> di
                         _ptr(adv), _ptr(ret), _stream(r.device)))
     data["advantages"], data["returns"] = adv, ret
     return data
+
+
+def training_loop(iterations: int, collect, step, first_iteration: Optional[int] = None, history: Optional[list] = None,
+                  stats_owner=None, stats_device=None, evaluate=None, eval_freq: int = 0, checkpoint=None,
+                  checkpoint_freq: int = 0, callback=None) -> list:
+    """The loop of `PPOLearner.learn`, `ImitationLearner.learn` and `ModularTrainer.learn`, defined once: for `it` in
+    range(first_iteration, iterations) (None: from 0, unchecked) `data = collect(it)` and `rec = step(data, 1 - (it + 1) /
+    iterations)`.  With `stats_owner` its `episode_stats` (created on `stats_device` when absent or of another width) books
+    the rollout before `step`, and rec gains `episodes`, `ep_rew_mean`, `ep_len_mean` after it; every eval_freq-th rec
+    gains `eval_mean_reward`, `eval_std_reward` = `evaluate()`.  Then, always in this order: `history.append(rec)`,
+    every checkpoint_freq-th iteration `checkpoint(it + 1, history)`, `callback(it, rec)`.  -> history (a copy, extended)."""
+    iterations, eval_freq, checkpoint_freq = int(iterations), int(eval_freq), int(checkpoint_freq)
+    if first_iteration is not None and not 0 <= int(first_iteration) <= iterations:
+        raise ValueError(f"first_iteration must be in [0, iterations = {iterations}], not {first_iteration!r}")
+    if checkpoint_freq < 0 or (checkpoint_freq > 0 and checkpoint is None):
+        raise ValueError("checkpoint_freq must be >= 0, and > 0 needs a checkpoint_path")
+    history = [] if history is None else list(history)
+    for it in range(int(first_iteration or 0), iterations):
+        data = collect(it)
+        if stats_owner is not None:
+            n = data["rewards"].shape[1]
+            if stats_owner.episode_stats is None or stats_owner.episode_stats.num_envs != n:
+                stats_owner.episode_stats = EpisodeStats(n, stats_device)
+            stats_owner.episode_stats.reset_totals()
+            stats_owner.episode_stats.update(data)
+        rec = step(data, 1.0 - (it + 1) / iterations)
+        if stats_owner is not None:
+            t = stats_owner.episode_stats.totals()
+            rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
+        if evaluate is not None and eval_freq > 0 and (it + 1) % eval_freq == 0:
+            mean, std = evaluate()
+            rec.update(eval_mean_reward=mean, eval_std_reward=std)
+        history.append(rec)
+        if checkpoint_freq > 0 and (it + 1) % checkpoint_freq == 0:
+            checkpoint(it + 1, history)
+        if callback is not None:
+            callback(it, rec)
+    return history
 
 
 class PPOLearner:
@@ -238,6 +278,20 @@ class PPOLearner:
         self.epochs_done += 1
         return self._perm
 
+    def _minibatches(self, total: int, bs: int):
+        """Yields the device row indices of every minibatch of an update, in order: n_epochs permutations of `total` rows
+        (`shuffle`; `last_permutations` / `last_epochs` record them), each cut into runs of `bs`, the last maybe short."""
+        self.last_permutations, self.last_epochs = [], []
+        for _ in range(self.n_epochs):
+            if self.shuffle == "device":
+                perm = self._device_permutation(total)
+            else:
+                perm_cpu = torch.randperm(total, generator=self.generator)
+                self.last_permutations.append(perm_cpu)
+                perm = perm_cpu.to(self.device)
+            for start in range(0, total, bs):
+                yield perm[start:start + bs]
+
     def _resolve_schedules(self) -> None:
         """What SB3 does at the top of train(): the scheduled values at `progress_remaining`, once per update."""
         p = self.progress_remaining
@@ -396,20 +450,9 @@ class PPOLearner:
         else:
             stats, control = torch.zeros((n_mb, 8), dtype=torch.float32, device=self.device), None
         step0 = self.step
-        self.last_permutations, self.last_epochs = [], []
-        i = 0
-        for _ in range(self.n_epochs):
-            if self.shuffle == "device":
-                perm = self._device_permutation(total)
-            else:
-                perm_cpu = torch.randperm(total, generator=self.generator)
-                self.last_permutations.append(perm_cpu)
-                perm = perm_cpu.to(self.device)
-            for start in range(0, total, bs):
-                rows = perm[start:start + bs]
-                self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
-                self.adam_step(control)
-                i += 1
+        for i, rows in enumerate(self._minibatches(total, bs)):
+            self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
+            self.adam_step(control)
         self._hand_over()
         if not gated:
             if ev is None:
@@ -455,26 +498,10 @@ class PPOLearner:
         far; an `{iteration}` field in checkpoint_path is filled in, so earlier files can be kept.  `eval_collector`'s
         env is not saved and needs no state: `evaluate_policy` resets it every time.  With the defaults nothing is
         written and the loop is what it was."""
-        from .checkpoint import format_path, save_checkpoint
-        from .episodes import EpisodeStats, evaluate_policy
+        evaluate = self._evaluator(eval_collector, eval_freq, n_eval_episodes, keep_best=True)
 
-        evaluating = eval_collector is not None and int(eval_freq) > 0
-        if evaluating and eval_collector.policy is not self.policy:
-            raise ValueError("eval_collector must run this learner's policy")
-        if not 0 <= int(first_iteration) <= int(iterations):
-            raise ValueError(f"first_iteration must be in [0, iterations = {int(iterations)}], not {first_iteration!r}")
-        if int(checkpoint_freq) < 0 or (int(checkpoint_freq) > 0 and checkpoint_path is None):
-            raise ValueError("checkpoint_freq must be >= 0, and > 0 needs a checkpoint_path")
-        history = [] if history is None else list(history)
-        for it in range(int(first_iteration), int(iterations)):
-            data = collector.collect()
-            if episode_stats:
-                n = data["rewards"].shape[1]
-                if self.episode_stats is None or self.episode_stats.num_envs != n:
-                    self.episode_stats = EpisodeStats(n, self.device)
-                self.episode_stats.reset_totals()
-                self.episode_stats.update(data)
-            self.progress_remaining = 1.0 - (it + 1) / int(iterations)
+        def step(data, progress_remaining):
+            self.progress_remaining = progress_remaining
             out = self.update(data, explained_variance=True) if explained_variance else self.update(data)
             rec = dict(out["mean"], reward=float(data["rewards"].mean()))
             if "stopped" in out:  # target_kl is set
@@ -485,26 +512,37 @@ class PPOLearner:
                 rec.update(clip_range_vf=self.clip_range_vf)
             if explained_variance:
                 rec.update(explained_variance=out["explained_variance"])
-            if episode_stats:
-                t = self.episode_stats.totals()
-                rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
-            if evaluating and (it + 1) % int(eval_freq) == 0:
-                mean, std = evaluate_policy(eval_collector, n_eval_episodes=n_eval_episodes)
-                rec.update(eval_mean_reward=mean, eval_std_reward=std)
-                if mean > self.best_mean_reward:
-                    self.best_mean_reward = mean
-                    if self.best_weights is None:
-                        self.best_weights = torch.empty_like(self.weights)
-                    self.best_weights.copy_(self.weights)  # device to device
-            history.append(rec)
-            if int(checkpoint_freq) > 0 and (it + 1) % int(checkpoint_freq) == 0:
-                sort_policy = getattr(collector, "sort_policy", None)
-                save_checkpoint(format_path(checkpoint_path, it + 1), learner=self, collector=collector,
-                                policies=None if sort_policy is None else {"sort_policy": sort_policy}, iteration=it + 1,
-                                iterations=int(iterations), history=history)
-            if callback is not None:
-                callback(it, rec)
-        return history
+            return rec
+
+        def checkpoint(iteration, history):
+            sort_policy = getattr(collector, "sort_policy", None)
+            save_checkpoint(format_path(checkpoint_path, iteration), learner=self, collector=collector,
+                            policies=None if sort_policy is None else {"sort_policy": sort_policy}, iteration=iteration,
+                            iterations=int(iterations), history=history)
+
+        return training_loop(iterations, lambda it: collector.collect(), step, first_iteration=first_iteration, history=history,
+                             stats_owner=self if episode_stats else None, stats_device=self.device, evaluate=evaluate,
+                             eval_freq=eval_freq, checkpoint=None if checkpoint_path is None else checkpoint,
+                             checkpoint_freq=checkpoint_freq, callback=callback)
+
+    def _evaluator(self, eval_collector, eval_freq: int, n_eval_episodes: int, keep_best: bool = False):
+        """`learn`'s evaluation: None unless eval_collector is given with eval_freq > 0 (one over another policy is refused),
+        else a function -> `evaluate_policy(...)`'s pair that with keep_best also tracks `best_mean_reward` / `best_weights`."""
+        if eval_collector is None or int(eval_freq) <= 0:
+            return None
+        if eval_collector.policy is not self.policy:
+            raise ValueError("eval_collector must run this learner's policy")
+
+        def evaluate():
+            mean, std = evaluate_policy(eval_collector, n_eval_episodes=n_eval_episodes)
+            if keep_best and mean > self.best_mean_reward:
+                self.best_mean_reward = mean
+                if self.best_weights is None:
+                    self.best_weights = torch.empty_like(self.weights)
+                self.best_weights.copy_(self.weights)  # device to device
+            return mean, std
+
+        return evaluate
 
     def restore_best(self) -> None:
         """Loads `best_weights` back into the learner's master copy and the policy (EvalCallback's best_model)."""

@@ -10,7 +10,8 @@ from __future__ import annotations
 
 from typing import Optional
 
-from .learner import PPOLearner
+from .episodes import evaluate_rollout
+from .learner import PPOLearner, training_loop
 
 AGENTS = ("sort", "press")
 
@@ -44,39 +45,27 @@ class ModularTrainer:
         the team reward.  eval_env (an Env_3 handle of its own) with eval_freq > 0: every eval_freq-th record gains
         `eval_mean_reward` / `eval_std_reward` from `evaluate_rollout(eval_env, "model", ...)` with both agents - the
         reference's "PPO Modular" scenario."""
-        from .episodes import EpisodeStats, evaluate_rollout
-
         col = self.collector
-        if not 0 <= int(first_iteration) <= int(iterations):
-            raise ValueError(f"first_iteration must be in [0, iterations = {int(iterations)}], not {first_iteration!r}")
-        evaluating = eval_env is not None and int(eval_freq) > 0
-        history = []
-        for it in range(int(first_iteration), int(iterations)):
-            data = col.collect(sort_deterministic=self.learners["sort"] is None,
+
+        def collect(it):
+            return col.collect(sort_deterministic=self.learners["sort"] is None,
                                press_deterministic=self.learners["press"] is None)
-            if episode_stats:
-                n = data["rewards"].shape[1]
-                if self.episode_stats is None or self.episode_stats.num_envs != n:
-                    self.episode_stats = EpisodeStats(n, col.env.device)
-                self.episode_stats.reset_totals()
-                self.episode_stats.update(data)
+
+        def step(data, progress_remaining):
             rec = {"reward": float(data["rewards"].mean())}
             for who in AGENTS:
                 if data.get(f"rewards_{who}") is not None:
                     rec[f"reward_{who}"] = float(data[f"rewards_{who}"].mean())
-            progress = 1.0 - (it + 1) / int(iterations)
             for who in AGENTS:
                 learner = self.learners[who]
                 if learner is not None:
-                    rec[who] = learner.update(col.view(who, self.reward), progress_remaining=progress)["mean"]
-            if episode_stats:
-                t = self.episode_stats.totals()
-                rec.update(episodes=t["episodes"], ep_rew_mean=t["mean_return"], ep_len_mean=t["mean_length"])
-            if evaluating and (it + 1) % int(eval_freq) == 0:
-                mean, std = evaluate_rollout(eval_env, "model", n_eval_episodes=n_eval_episodes, sort_agent=col.sort_agent,
-                                             press_agent=col.press_agent, press_agent_maskable=col.press_masked)
-                rec.update(eval_mean_reward=mean, eval_std_reward=std)
-            history.append(rec)
-            if callback is not None:
-                callback(it, rec)
-        return history
+                    rec[who] = learner.update(col.view(who, self.reward), progress_remaining=progress_remaining)["mean"]
+            return rec
+
+        def evaluate():
+            return evaluate_rollout(eval_env, "model", n_eval_episodes=n_eval_episodes, sort_agent=col.sort_agent,
+                                    press_agent=col.press_agent, press_agent_maskable=col.press_masked)
+
+        return training_loop(iterations, collect, step, first_iteration=first_iteration,
+                             stats_owner=self if episode_stats else None, stats_device=col.env.device if episode_stats else None,
+                             evaluate=None if eval_env is None else evaluate, eval_freq=eval_freq, callback=callback)
