@@ -451,6 +451,29 @@ typedef struct mse_demo_buffers {
 } mse_demo_buffers;
 int mse_rollout_demo(mse_env *env, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
                      uint32_t expert_threshold, uint32_t flags, const mse_demo_buffers *out, void *stream);
+/* mse_rollout_policy with the rule-based controller's label of every recorded row, in the same launch: the rollout that PPO
+ * with an imitation term trains on (mse_ppo_bc_loss_grad).  The arguments are mse_rollout_policy's without the sorting policy,
+ * then
+ *   expert_actions_out  i32[K, N]: per step, what mse_rule_actions returns for the state the recorded row shows (the state
+ *                       before the step) - mse_rollout_demo's label expression; no stream is read or advanced for it
+ * Every other output, the written-back state and the policy step counter are bit-identical to mse_rollout_policy with
+ * sort_policy = NULL on the same handle.  Two limits: there is no in-loop sorting policy (alternate mse_policy_forward,
+ * mse_rule_actions and mse_step for that: Python's PolicyRolloutCollector(sort_policy=, expert_labels=True)), and there is no
+ * roles shape - the plain kernel (one wave owns 32 or 64 envs, one network, f16x3 in either wave shape, exact f32 in the
+ * 64-env shape) runs at every size, as in mse_rollout_demo, whatever rollout_pipeline says.
+ * Refusals: mse_rollout_policy's, in its order (NULL env / policy, before reset, k_steps < 1, auto_reset = 0, an attached
+ * trace, unknown flags, mismatched dimensions or devices, unaligned obs_out / mask_out, a config off the integer path, tables
+ * that do not fit the kernel's LDS image), then expert_actions_out == NULL (MSE_ERR_INVALID_ARGUMENT).  Nothing is written
+ * and the step counter stays when a call is refused. */
+int mse_rollout_policy_labelled(mse_env *env, mse_policy *policy, int32_t k_steps, uint64_t seed, int deterministic,
+                                const int32_t *sort_mode_dev, uint32_t flags, float *obs_out, uint8_t *mask_out,
+                                int32_t *actions_out, float *logp_out, float *value_out, float *reward_out,
+                                uint8_t *episode_start_out, float *last_value_out, uint8_t *last_done_out,
+                                int32_t *expert_actions_out, void *stream);
+/* The status mse_rollout_policy_labelled would return for these arguments, its checks on the outputs left out; no launch */
+int mse_rollout_policy_labelled_check(mse_env *env, mse_policy *policy, int32_t k_steps, uint64_t seed, int deterministic,
+                                      const int32_t *sort_mode_dev, uint32_t flags);
+
 /* The status mse_rollout_demo would return for these arguments, its checks on `out` left out (MSE_OK or one of the
  * refusals above, with its message in mse_last_error), without launching anything or touching the handle. */
 int mse_rollout_demo_check(mse_env *env, mse_policy *actor, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
@@ -642,6 +665,37 @@ int mse_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64
                      const float *obs, const uint8_t *mask /* or NULL */, const int32_t *actions,
                      const float *returns /* or NULL: actor only */, const mse_ppo_params *params, float *grad_out,
                      float *stats_out, void *workspace, void *stream, int arithmetic /* 0 fma, 1 matrix */);
+
+/* PPO with an auxiliary imitation term (DAPG / kickstarting): mse_ppo_loss_grad_vclip's loss plus bc_coef times the
+ * cross-entropy of the rule-based controller's action at every row, from ONE forward pass, in one gradient launch:
+ *   loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss + bc_coef bc_loss
+ * The first 22 arguments are mse_ppo_loss_grad_vclip's with the same meaning (either arithmetic, gated or not, with or
+ * without old_values), except:
+ *   stats_out      f32[12]: [0] the loss above, [1..7] as mse_ppo_loss_grad, [8] bc_loss = mean(ce), [9] accuracy = hits /
+ *                  batch, [10] unusable rows / batch, [11] 0.  The gate reads [4] as before.
+ *   workspace      mse_ppo_bc_workspace_bytes(D, A) bytes (a few KiB more than mse_ppo_workspace_bytes: wider slabs)
+ *   expert_actions i32[n_rows]: the label of every row (mse_rule_actions of the state the row shows:
+ *                  mse_rollout_policy_labelled's expert_actions_out), clamped into [0, A)
+ *   bc_coef        >= 0, used as a float32; 0 is allowed
+ * Per row (csrc/mse_ppo_math.h, policy_bc_head_terms): the masked softmax and every PPO term are policy_head_terms'; with
+ * usable = the label is legal under the mask,  ce = usable ? -lp[expert] : 0,  g_bc = usable ? -(bc_coef / batch) : 0,
+ *   d loss / d logit[a] = g_logp (onehot(a == action) - p[a]) + g_bc (onehot(a == expert) - p[a])
+ *                         + ent_coef / batch (p[a] (lp[a] + 1) - p[a] rest)        for legal a, else 0,  added left to right
+ *   hit = usable and argmax of the masked logits == expert (ties to the lowest index)
+ * A row whose label the mask forbids adds 0 to ce and its gradient and 1 to `unusable`, and keeps its PPO and entropy terms.
+ * With bc_coef = 0 grad_out and stats_out[0..7] equal mse_ppo_loss_grad_vclip's on the same inputs bit for bit, up to the
+ * sign of a zero.  Three launches as before (the advantage pass, the KICK entry of the gradient kernel, the reduction's
+ * twelve-column form), the same grid rule, fixed-order sums without atomics: equal inputs give bit-equal outputs.
+ * Checks, all before any device call, in this order: mse_ppo_loss_grad_vclip's; expert_actions == NULL; bc_coef not finite,
+ * negative, or not finite as a float32.  Each of the new ones is MSE_ERR_INVALID_ARGUMENT. */
+int64_t mse_ppo_bc_workspace_bytes(int obs_dim, int n_actions); /* 0 for dimensions outside 1..32; needs no device */
+int mse_ppo_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                         int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                         const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                         float *stats_out /* f32[12] */, void *workspace, void *stream, double target_kl,
+                         int32_t *control_dev /* NULL: no gate */, int arithmetic /* 0 fma, 1 matrix */,
+                         const float *old_values /* f32[n_rows] or NULL */, double clip_range_vf,
+                         const int32_t *expert_actions /* i32[n_rows] */, double bc_coef);
 
 /* SB3's train/explained_variance: 1 - var(returns - values) / var(returns) over n rows (all K * N of a rollout), population
  * variances, NaN when var(returns) is 0 (n = 1, constant returns).  csrc/mse_ppo_math.h specifies the arithmetic

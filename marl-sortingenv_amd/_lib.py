@@ -31,8 +31,9 @@ EXPORTS = [
     "mse_episode_workspace_bytes", "mse_episode_scan", "mse_episode_scan_host", "mse_episode_summary", "mse_episode_summary_host",
     "mse_ppo_loss_grad_matrix",
     "mse_ppo_loss_grad_vclip", "mse_explained_variance_workspace_bytes", "mse_explained_variance", "mse_explained_variance_host",
-    "mse_bc_loss_grad",
+    "mse_bc_loss_grad", "mse_ppo_bc_workspace_bytes", "mse_ppo_bc_loss_grad",
     "mse_rollout_demo", "mse_rollout_demo_check", "mse_demo_who_steps_host",
+    "mse_rollout_policy_labelled", "mse_rollout_policy_labelled_check",
 ]
 
 _other_libs: dict = {}
@@ -162,6 +163,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_rollout_modular_check.argtypes = [vp, vp, vp, i32, u64, u64, u32]
     L.mse_rollout_demo.argtypes = [vp, vp, i32, u64, u64, u32, u32, C.POINTER(MseDemoBuffers), vp]
     L.mse_rollout_demo_check.argtypes = [vp, vp, i32, u64, u64, u32, u32]
+    L.mse_rollout_policy_labelled.argtypes = [vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mse_rollout_policy_labelled_check.argtypes = [vp, vp, i32, u64, C.c_int, vp, u32]
     L.mse_demo_who_steps_host.argtypes = [i64, i64, u64, u64, u32, vp]
     L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
     L.mse_policy_set_weights_device.argtypes = [vp, vp, vp]
@@ -180,6 +183,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
     L.mse_ppo_loss_grad_matrix.argtypes = L.mse_ppo_loss_grad_gated.argtypes
     L.mse_ppo_loss_grad_vclip.argtypes = L.mse_ppo_loss_grad_gated.argtypes + [C.c_int, vp, C.c_double]
+    L.mse_ppo_bc_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    L.mse_ppo_bc_workspace_bytes.restype = i64
+    L.mse_ppo_bc_loss_grad.argtypes = L.mse_ppo_loss_grad_vclip.argtypes + [vp, C.c_double]
     L.mse_bc_loss_grad.argtypes = [C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, vp, C.c_int]
     L.mse_explained_variance_workspace_bytes.argtypes = []
     L.mse_explained_variance_workspace_bytes.restype = i64

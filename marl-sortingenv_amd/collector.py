@@ -35,7 +35,7 @@ from .policy import MlpPolicy
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 ROW_DTYPES = {"observations": F32, "action_masks": U8, "actions": I32, "log_probs": F32, "values": F32, "rewards": F32,
               "episode_starts": U8, "last_values": F32, "last_dones": U8, "stepped_actions": I32, "expert_stepped": U8,
-              "returns": F32}
+              "returns": F32, "expert_actions": I32}
 POLICY_ROWS = ("observations", "action_masks", "actions", "log_probs", "values", "rewards", "episode_starts")
 
 
@@ -96,11 +96,15 @@ class PolicyRolloutCollector(_CollectorState):
     KIND = "two_launch"
 
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, sort_policy: Optional[MlpPolicy] = None,
-                 seed: int = 2024):
+                 seed: int = 2024, expert_labels: bool = False):
+        """expert_labels: `env.rule_actions()` of every state the rollout visits, taken before its step, is recorded in
+        `buffers["expert_actions"]` (i32[K, N]): what the rule-based controller would do there, the labels of
+        `PPOLearner(bc_coef=...)`.  The labels are outputs, not state: the checkpoint surface is the same."""
         _check_policy_collector(env, policy, sort_policy)
         self.env, self.policy, self.sort_policy = env, policy, sort_policy
         self.n_steps, self.seed, self.t = int(n_steps), int(seed), 0
-        self.buffers = rollout_buffers(env, self.n_steps)
+        self.expert_labels = bool(expert_labels)
+        self.buffers = rollout_buffers(env, self.n_steps, names=POLICY_ROWS + (("expert_actions",) if self.expert_labels else ()))
         self._last_done = torch.ones((env.num_envs,), dtype=torch.uint8, device=env.device)  # the envs were just reset
         self._out = None
         self._sort_out = None
@@ -134,6 +138,8 @@ class PolicyRolloutCollector(_CollectorState):
             b["observations"][k].copy_(obs)
             b["action_masks"][k].copy_(mask)
             b["episode_starts"][k].copy_(self._last_done)
+            if self.expert_labels:
+                b["expert_actions"][k].copy_(env.rule_actions())
             self._out = self.policy.forward(obs, mask, seed=self.seed, t=self.t, deterministic=deterministic,
                                             index_offset=env.index_offset, out=self._out)
             sort_mode = None
@@ -162,12 +168,21 @@ class FusedPolicyRollout(_CollectorState):
     KIND = "fused"
 
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, seed: int = 2024,
-                 sort_mode: Optional[torch.Tensor] = None, sort_policy: Optional[MlpPolicy] = None):
+                 sort_mode: Optional[torch.Tensor] = None, sort_policy: Optional[MlpPolicy] = None, expert_labels: bool = False):
+        """expert_labels: `collect()` is one `mse_rollout_policy_labelled` launch and the buffers gain `expert_actions`
+        (i32[K, N]): the rule-based controller's action in every recorded state, `PolicyRolloutCollector(expert_labels=True)`'s
+        bits.  The plain kernel runs at every size (no roles shape) and there is no in-loop sorting policy.  The labels are
+        outputs, not state: the checkpoint surface is the same."""
         _check_policy_collector(env, policy, sort_policy)
+        if expert_labels and sort_policy is not None:
+            raise ValueError("the one-launch labelled rollout has no in-loop sorting policy: collect with "
+                             "PolicyRolloutCollector(sort_policy=..., expert_labels=True)")
+        self.expert_labels = bool(expert_labels)
         self.env, self.policy, self.n_steps, self.seed = env, policy, int(n_steps), int(seed)
         self.sort_policy = sort_policy  # Env_2's pre-trained sorting agent, evaluated inside the kernel
         self.sort_mode = None if sort_mode is None else sort_mode.to(device=env.device, dtype=torch.int32).contiguous()
-        self.buffers = rollout_buffers(env, self.n_steps, last=True)
+        self.buffers = rollout_buffers(env, self.n_steps, last=True,
+                                       names=POLICY_ROWS + (("expert_actions",) if self.expert_labels else ()))
 
     def collect(self, n_steps: Optional[int] = None, deterministic: bool = False, use_action_masking: bool = True,
                 check_overflow: bool = False) -> dict:
@@ -186,6 +201,14 @@ class FusedPolicyRollout(_CollectorState):
         def ptr(x):
             return None if x is None else C.c_void_p(x.data_ptr())
 
+        if self.expert_labels:
+            with torch.cuda.device(env.device):
+                check(env.L.mse_rollout_policy_labelled(env._h, self.policy._h, K, self.seed, 1 if deterministic else 0,
+                                                        ptr(self.sort_mode), flags, ptr(b["observations"]), ptr(b["action_masks"]),
+                                                        ptr(b["actions"]), ptr(b["log_probs"]), ptr(b["values"]), ptr(b["rewards"]),
+                                                        ptr(b["episode_starts"]), ptr(b["last_values"]), ptr(b["last_dones"]),
+                                                        ptr(b["expert_actions"]), env._stream()))
+            return b
         with torch.cuda.device(env.device):
             check(env.L.mse_rollout_policy(env._h, self.policy._h, None if self.sort_policy is None else self.sort_policy._h,
                                            K, self.seed, 1 if deterministic else 0,

@@ -1177,150 +1177,33 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
                                                         float *__restrict__ last_value_out,
                                                         uint8_t *__restrict__ last_done_out)
 {
-    using L = PolLayout<KIND, TILES>;
-    constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
-    constexpr int kWeightBytes = L::weight_bytes * (SORTPOL ? 2 : 1); // [policy image][sorting policy image]
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // Every lane of an active wave steps an env, so that the step loop has no per-lane "is there an env here" region
-    // (the compiler kept two copies of the env's ~90 registers around one and moved them back and forth every step):
-    // TILES = 1: lanes 32-63 mirror lanes 0-31; lanes past the batch's end mirror its last env.  Mirrors compute what
-    // their original computes and store nothing.
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
+    // the body needs: KIND, NOISE, TILES, F16X3, SORTPOL (template parameters), LABEL, expert_out and the arguments above
+    constexpr bool LABEL = false;
+    [[maybe_unused]] int *const expert_out = nullptr;
+#include "mse_rollout_policy_body.inc"
+}
 
-    msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
-    if (SORTPOL) msep_copy_image(lw + msep::kLdsFloats, sort_weight_blob, F16X3, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    int sm = -1;
-    load_env<KIND, NOISE>(e, planes, P, i);
-    if (KIND == 2 && sort_mode != nullptr) sm = sort_mode[i];
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
-    msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
-
-    // the observation and mask of the current state (what reset / the previous launch left)
-    float o[32];
-#pragma unroll
-    for (int j = 0; j < 32; ++j) o[j] = 0.0f;
-    int kcur[4]; // container purities of the current state (the sorting agent's view needs them)
-    container_purity_k(e, kcur);
-    env_obs<KIND>(e, P, tb, kcur, o);
-    uint32_t mbits = action_mask_bits<KIND>(e, P);
-    msep::lds_f4 wl_sort = (msep::lds_f4)(__attribute__((address_space(3))) float *)(lw + msep::kLdsFloats);
-    // policy stream keys of the env(s) this lane serves as an MFMA column: tile t = envs 32 t .. 32 t + 31 of the wave
-    const int h = lane >> 5, col = lane & 31;
-    const uint32_t key0 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + col));
-    const uint32_t key1 = mse_policy_key(policy_seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
-
-    const uint32_t lrow_obs = lds_row_address(reinterpret_cast<float *>(lwave) + src_lane * D);
-    const uint32_t lrow_mask = lds_row_address(lwave + src_lane * A);
-    int last_done = 0;
-#ifdef MSE_TIMELINE
-    Timeline ptl;
-    ptl.start();
-#endif
-    for (int s = 0; s < k_steps; ++s) {
-        __builtin_amdgcn_s_setprio(TILES == 2 ? 3 : 0); // policy phase (see below)
-        const long long srow = (long long)s * P.n + wave_row0;
-        // the row the action is taken from (MaskableRolloutBuffer: observations, action_masks, episode_starts)
-        if (obs_out != nullptr) wave_store_rows_f32<D, ENVS>(reinterpret_cast<float *>(lwave), lrow_obs, o, obs_out + srow * D, n_valid, lane);
-        if (mask_out != nullptr) wave_store_rows_mask<A, ENVS>(lwave, lrow_mask, mbits, mask_out + srow * A, n_valid, lane);
-        if (live && start_out != nullptr)
-            __builtin_nontemporal_store((uint8_t)(e.step == 0 ? 1 : 0), &start_out[(long long)s * P.n + i]);
-        MSE_TLB(ptl, 0); // row stores
-        // ---- policy
-        float x[2][16];
-        operands_of(o, x);
-        // without masking (plain PPO on the unmasked env) the policy samples from the whole action space and the
-        // step sanitises; the recorded mask row is action_masks() either way
-        uint32_t mb0, mb1;
-        msep::both_halves_u32((flags & MSE_STEP_UNMASKED) ? ((1u << A) - 1u) : mbits, mb0, mb1);
-        const uint64_t t = policy_t0 + (uint64_t)s;
-        const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
-        const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
-        msep::TileOut p[2];
-        msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, A, legal, deterministic != 0, words, nullptr, p);
-        const int a = tile_pick<TILES>(h, p[0].action, p[1].action);
-        const float logp = tile_pick<TILES>(h, p[0].logp, p[1].logp), value = tile_pick<TILES>(h, p[0].value, p[1].value);
-        MSE_TLB(ptl, 1); // policy forward
-        // Phase priorities: the two waves of a SIMD fall into step with each other (both in the policy, both in the
-        // dynamics) and then compete for the same pipe; letting one phase win the issue arbitration pulls them apart so
-        // that one wave's MFMA chains run under the other's dynamics.  Which phase should win was measured on the box
-        // (same-box A/B, 16 steps per launch): 64-env waves +8 % with the policy phase high, 32-env waves +8 % with the
-        // dynamics phase high (the other choice +4 ... 6 % each; a static per-wave priority: nothing).
-        __builtin_amdgcn_s_setprio(TILES == 2 ? 0 : 3);
-        if (SORTPOL) {
-            // the sorting agent's decision for the coming step: get_sort_obs() one flow update ahead (a copy steps
-            // the flow; env_step will take the same step), through the second network's actor, argmax
-            float so[32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) so[j] = 0.0f;
-            {
-                Env ec = e;
-                update_environment<false>(ec, P);
-                sort_obs<false>(ec, P, tb, kcur, so);
-            }
-            float sx[2][16];
-            operands_of(so, sx);
-            int sa[2];
-            msep::actor_argmax2_tiles<F16X3, TILES>(wl_sort, lane, sx, sa);
-            sm = tile_pick<TILES>(h, sa[0], sa[1]);
-        }
-        MSE_TLB(ptl, 2); // sorting agent
-        // ---- the env transition under that action
-        StepResult r = env_step<KIND, NOISE, false>(e, P, tb, a, sm, flags, bales, kcur, o);
-        MSE_TLB(ptl, 3); // env transition
-        if (__builtin_expect(r.done != 0, 0)) {
-            auto_reset_env(e, P, tb, bales, kcur);
-            env_obs<KIND>(e, P, tb, kcur, o);
-        }
-        mbits = action_mask_bits<KIND>(e, P);
-        last_done = r.done;
-        if (live) {
-            const long long at = (long long)s * P.n + i;
-            if (actions_out != nullptr) __builtin_nontemporal_store(a, &actions_out[at]);
-            if (logp_out != nullptr) __builtin_nontemporal_store(logp, &logp_out[at]);
-            if (value_out != nullptr) __builtin_nontemporal_store(value, &value_out[at]);
-            if (reward_out != nullptr) __builtin_nontemporal_store((float)r.reward, &reward_out[at]);
-        }
-        MSE_TLB(ptl, 4); // auto-reset, mask, per-env stores
-    }
-#ifdef MSE_TIMELINE
-    ptl.flush(0);
-#endif
-    // the bootstrap value of the state the rollout ends in: the critic alone
-    if (last_value_out != nullptr) {
-        float x[2][16], v[2];
-        operands_of(o, x);
-        msep::value_tiles<F16X3, TILES>(wl, lane, x, v);
-        if (live) last_value_out[i] = tile_pick<TILES>(h, v[0], v[1]);
-    }
-    if (live && last_done_out != nullptr) last_done_out[i] = (uint8_t)last_done;
-    if (live) store_env<KIND, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+// k_rollout_policy's plain shape with one more expression and one more store per step: the rule-based controller's label of
+// the state the recorded row shows, rule_based_action<KIND>(e, Stage<false>::rule_mode(e.st_in, tb)) - k_rollout_demo's label,
+// so what mse_rule_actions returns for that state; no stream is read.  Every other output, the written-back state and the
+// step counter are k_rollout_policy's bits: the same statements (mse_rollout_policy_body.inc).  One network: no SORTPOL.
+template <int KIND, bool NOISE, int TILES, bool F16X3>
+__global__ __launch_bounds__(512) void k_rollout_policy_labelled(Params P, uint4 *__restrict__ planes,
+                                                                 const uint32_t *__restrict__ table_image,
+                                                                 const float *__restrict__ weight_blob,
+                                                                 const float *__restrict__ sort_weight_blob, int k_steps,
+                                                                 uint64_t policy_seed, uint64_t policy_t0, int deterministic,
+                                                                 const int *__restrict__ sort_mode, uint32_t flags,
+                                                                 float *__restrict__ obs_out, uint8_t *__restrict__ mask_out,
+                                                                 int *__restrict__ actions_out, float *__restrict__ logp_out,
+                                                                 float *__restrict__ value_out, float *__restrict__ reward_out,
+                                                                 uint8_t *__restrict__ start_out,
+                                                                 float *__restrict__ last_value_out,
+                                                                 uint8_t *__restrict__ last_done_out, int *__restrict__ expert_out)
+{
+    // the body needs: KIND, NOISE, TILES, F16X3 (template parameters), SORTPOL, LABEL, expert_out and the arguments above
+    constexpr bool SORTPOL = false, LABEL = true;
+#include "mse_rollout_policy_body.inc"
 }
 
 // ---- the learned-policy rollout in roles (batches that leave a SIMD 64 envs: n <= 256 envs x CUs) --------------------
@@ -2636,6 +2519,31 @@ static int launch_rollout_policy(mse_env *h, const mse_policy *pol, const mse_po
     return MSE_OK;
 }
 
+// mse_rollout_policy_labelled's shape: k_rollout_policy's plain one with one network at every size (no roles shape, as
+// mse_rollout_demo)
+template <int KIND>
+static PolicyPlan plan_rollout_policy_labelled(const mse_env *h, const mse_policy *pol)
+{
+    return plan_policy_plain(h->P.n, h->cus, pol->use_f16(), 1, policy_lds<KIND>(h->P));
+}
+
+// the caller has checked that the plan fits (rollout_policy_labelled_checks)
+template <int KIND>
+static void launch_rollout_policy_labelled(mse_env *h, const mse_policy *pol, hipStream_t s, int k_steps, uint64_t seed,
+                                           int deterministic, const int32_t *sort_mode, uint32_t flags, float *obs, uint8_t *mask,
+                                           int32_t *actions, float *logp, float *value, float *rew, uint8_t *start,
+                                           float *last_value, uint8_t *last_done, int32_t *expert)
+{
+    const PolicyPlan plan = plan_rollout_policy_labelled<KIND>(h, pol);
+    with_flags([&](auto NOISE, auto ONE_TILE, auto F16) {
+        if constexpr (F16 || !ONE_TILE) // the forms the plan gives: exact f32 in two tiles only
+            hipLaunchKernelGGL((k_rollout_policy_labelled<KIND, NOISE, ONE_TILE ? 1 : 2, F16>), dim3((unsigned)plan.workgroups),
+                               dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables, pol->blob,
+                               (const float *)nullptr, k_steps, seed, h->policy_t, deterministic, sort_mode, flags, obs, mask,
+                               actions, logp, value, rew, start, last_value, last_done, expert);
+    }, h->noise_on, plan.tiles == 1, pol->use_f16());
+}
+
 // mse_rollout_model's shape: k_rollout_policy's f16x3 one with two networks (plan_policy_plain)
 static int launch_rollout_model(mse_env *h, const mse_policy *sort_ag, const mse_policy *press_ag, hipStream_t s,
                                 int k_steps, uint32_t flags, int32_t *actions, float *obs, float *rew, uint8_t *done,
@@ -2988,6 +2896,52 @@ int mse_rollout_policy(mse_env *h, mse_policy *pol, mse_policy *sort_pol, int32_
                                            reward_out, episode_start_out, last_value_out, last_done_out);
     });
     if (rc != MSE_OK) return fail(rc, "the policy rollout kernel's LDS image does not fit this config's tables");
+    MSE_CHECK_LAUNCH();
+    h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+// everything mse_rollout_policy_labelled refuses: mse_rollout_policy's refusals in its order (there is no sorting policy), then
+// a NULL expert_actions_out; the outputs are looked at when `with_out` is set (mse_rollout_policy_labelled_check has none)
+static int rollout_policy_labelled_checks(mse_env *h, mse_policy *pol, int32_t k_steps, uint32_t flags, bool with_out,
+                                          const float *obs_out, const uint8_t *mask_out, const int32_t *expert_out)
+{
+    if (!h || !pol) return fail(MSE_ERR_INVALID_ARGUMENT, "env/policy is NULL");
+    if (const int rc = rollout_checks(h, k_steps, "mse_rollout_policy_labelled")) return rc;
+    if (flags & ~(MSE_STEP_UNMASKED | MSE_STEP_CHECK_OVERFLOW))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag");
+    if (pol->d_in != mse_obs_dim(h) || pol->n_act != mse_num_actions(h))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "the policy's observation / action dimensions do not match the env kind");
+    if (pol->device != h->device) return fail(MSE_ERR_INVALID_ARGUMENT, "policy and env live on different devices");
+    if (with_out && ((obs_out && !aligned16(obs_out)) || (mask_out && !aligned16(mask_out))))
+        return fail(MSE_ERR_ALIGNMENT, "obs_out / mask_out must be 16-byte aligned");
+    if (const int rc = integer_path_check(h, "mse_rollout_policy_labelled", "literal_choice, input_batch_size > 127 or with a floor() "
+                                                                           "remainder: PolicyRolloutCollector(expert_labels=True)")) return rc;
+    const int rc = with_kind(h->P.env_kind, [&](auto KIND) { return plan_rollout_policy_labelled<KIND>(h, pol).status; });
+    if (rc != MSE_OK) return fail(rc, "the policy rollout kernel's LDS image does not fit this config's tables");
+    if (with_out && expert_out == nullptr) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_policy_labelled: expert_actions_out is NULL");
+    return MSE_OK;
+}
+
+int mse_rollout_policy_labelled_check(mse_env *h, mse_policy *pol, int32_t k_steps, uint64_t seed, int deterministic,
+                                      const int32_t *sort_mode, uint32_t flags)
+{
+    (void)seed, (void)deterministic, (void)sort_mode;
+    return rollout_policy_labelled_checks(h, pol, k_steps, flags, false, nullptr, nullptr, nullptr);
+}
+
+int mse_rollout_policy_labelled(mse_env *h, mse_policy *pol, int32_t k_steps, uint64_t seed, int deterministic,
+                                const int32_t *sort_mode, uint32_t flags, float *obs_out, uint8_t *mask_out, int32_t *actions_out,
+                                float *logp_out, float *value_out, float *reward_out, uint8_t *episode_start_out,
+                                float *last_value_out, uint8_t *last_done_out, int32_t *expert_actions_out, void *stream)
+{
+    if (const int rc = rollout_policy_labelled_checks(h, pol, k_steps, flags, true, obs_out, mask_out, expert_actions_out)) return rc;
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        launch_rollout_policy_labelled<KIND>(h, pol, static_cast<hipStream_t>(stream), k_steps, seed, deterministic, sort_mode, flags,
+                                             obs_out, mask_out, actions_out, logp_out, value_out, reward_out, episode_start_out,
+                                             last_value_out, last_done_out, expert_actions_out);
+        return MSE_OK;
+    });
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
     return MSE_OK;

@@ -198,160 +198,40 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
                                                   const double *__restrict__ adv_partial, float *__restrict__ slabs,
                                                   const int *__restrict__ control, const float *__restrict__ old_values)
 {
-    typedef Padded<DP, AP> PW;
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (gate_closed(control)) { // grid-uniform
-        mark_gate_closed(flat_layout(G.D, G.A).total, slabs);
-        return;
-    }
-    float *wl0 = lds;                     // PW::total floats: the padded weights
-    float *strips = lds + PW::total;      // 4 x kStageFloats: one staging strip per wave
-    float *misc = strips + 4 * kStageFloats; // kMiscFloats
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int D = G.D, A = G.A;
-    const Flat F = flat_layout(D, A);
-    for (int i = tid; i < PW::total; i += 256) wl0[i] = 0.0f;
-    __syncthreads();
-    for (int f = tid; f < F.total; f += 256) wl0[padded_index<DP, AP>(f, D, A)] = weights[f];
-    publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
-    __syncthreads();
-    const bool normalize = G.n_adv_partial > 0;
-    const float mean = misc[0], std = misc[1];
-    const float inv_b_all = 1.0f / (float)G.batch;
-    const bool critic = (wave & 1) != 0;
-    float *strip = strips + wave * kStageFloats;
-    LayerAcc L1 = {}, L2 = {}, L3 = {}; // first, second hidden layer, head
-    float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f, st3 = 0.0f;
-    long long n_tiles = (G.batch + 63) / 64;
-    if constexpr (BC) n_tiles = critic && ret == nullptr ? 0 : n_tiles; // wave-uniform: no returns, nothing for the critic
-    for (long long tile = (long long)blockIdx.x * 2 + (wave >> 1); tile < n_tiles; tile += (long long)gridDim.x * 2) {
-        // the weights are re-read from LDS every tile: an offset the compiler cannot see through keeps it from hoisting
-        // ~5 000 wave-uniform values out of the loop into (spilled) scalar registers
-        unsigned opaque = 0;
-        asm volatile("" : "+v"(opaque));
-        const float *wl = static_cast<const float *>(__builtin_assume_aligned(wl0 + 4 * opaque, 16));
-        const long long b = tile * 64 + lane;
-        const bool valid = b < G.batch;
-        const long long row = row_at(rows, valid ? b : 0, G.n_rows);
-        const float inv_b = valid ? inv_b_all : 0.0f; // a padding lane contributes zero deltas
-        float x[DP];
-#pragma unroll
-        for (int i = 0; i < DP; ++i) {
-            const float v = obs[row * D + (i < D ? i : 0)];
-            x[i] = i < D ? v : 0.0f;
-        }
-        float h1[kH], h2[kH], dz[kH];
-        if (!critic) {
-            uint32_t legal = 0;
-#pragma unroll
-            for (int a = 0; a < AP; ++a) {
-                const bool ok = a < A && (mask == nullptr || mask[row * A + (a < A ? a : 0)] != 0);
-                legal |= (ok ? 1u : 0u) << a;
-            }
-            float dl[AP];
-            if constexpr (BC) {
-                hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
-                head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
-                const BcTerms t = bc_head_terms<AP>(dl, A, legal, actions[row], G.P, inv_b);
-                if (valid) {
-                    st0 += t.ce;
-                    st1 += t.entropy;
-                    st2 += t.hit;
-                    st3 += t.unusable;
-                }
-            } else {
-                const int action = clamped_action(actions[row], A);
-                const float a_raw = adv[row];
-                const float a_used = normalize ? normalized_advantage(a_raw, mean, std) : a_raw;
-                hidden_forward<DP>(wl + PW::pi_w1, wl + PW::pi_b1, wl + PW::pi_w2, wl + PW::pi_b2, x, h1, h2);
-                head_forward<AP>(wl + PW::act_w, wl + PW::act_b, h2, dl);
-                const PolicyTerms t = policy_head_terms<AP>(dl, A, legal, action, old_logp[row], a_used, G.P, inv_b);
-                if (valid) {
-                    st0 += t.surrogate;
-                    st1 += t.entropy;
-                    st2 += t.kl;
-                    st3 += t.clipped;
-                }
-            }
-            accumulate_layer(strip, lane, dl, h2, L3.w, L3.b);
-            backprop<AP>(wl + PW::act_w, dl, h2, dz);
-        } else {
-            hidden_forward<DP>(wl + PW::vf_w1, wl + PW::vf_b1, wl + PW::vf_w2, wl + PW::vf_b2, x, h1, h2);
-            float v[1];
-            head_forward<1>(wl + PW::val_w, wl + PW::val_b, h2, v);
-            float dv[1];
-            float sq;
-            if constexpr (VCLIP)
-                sq = value_head_terms_clipped(v[0], old_values[row], ret[row], G.P, inv_b, dv[0]);
-            else
-                sq = value_head_terms(v[0], ret[row], G.P, inv_b, dv[0]);
-            if (valid) st0 += sq;
-            accumulate_layer(strip, lane, dv, h2, L3.w, L3.b);
-            backprop<1>(wl + PW::val_w, dv, h2, dz);
-        }
-        const float *w2 = wl + (critic ? PW::vf_w2 : PW::pi_w2);
-        accumulate_layer(strip, lane, dz, h1, L2.w, L2.b);
-        float dz1[kH];
-        backprop<kH>(w2, dz, h1, dz1);
-        accumulate_layer(strip, lane, dz1, x, L1.w, L1.b);
-    }
-    // ---- the two waves of a network: slot 1 hands its sums to slot 0 through LDS; fixed order (slot 0 + slot 1) ----
-    st0 = wave_sum(st0);
-    st1 = wave_sum(st1);
-    st2 = wave_sum(st2);
-    st3 = wave_sum(st3);
-    __syncthreads(); // every wave is done with its strip
-    float *xch = strips + (wave & 1) * (60 * 64);
-    if (wave >= 2) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            xch[(k)*64 + lane] = L1.w[k];
-            xch[(16 + k) * 64 + lane] = L2.w[k];
-            xch[(32 + k) * 64 + lane] = L3.w[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            xch[(48 + k) * 64 + lane] = L1.b[k];
-            xch[(52 + k) * 64 + lane] = L2.b[k];
-            xch[(56 + k) * 64 + lane] = L3.b[k];
-        }
-    }
-    publish_loss_sums(misc, wave, lane, st0, st1, st2, st3);
-    __syncthreads();
-    float *slab = slabs + (long long)blockIdx.x * slab_stride(F.total);
-    if (wave < 2) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            L1.w[k] += xch[(k)*64 + lane];
-            L2.w[k] += xch[(16 + k) * 64 + lane];
-            L3.w[k] += xch[(32 + k) * 64 + lane];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            L1.b[k] += xch[(48 + k) * 64 + lane];
-            L2.b[k] += xch[(52 + k) * 64 + lane];
-            L3.b[k] += xch[(56 + k) * 64 + lane];
-        }
-        if (!critic) {
-            store_layer(slab, L1, lane, F.pi_w1, F.pi_b1, kH, D, D);
-            store_layer(slab, L2, lane, F.pi_w2, F.pi_b2, kH, kH, kH);
-            store_layer(slab, L3, lane, F.act_w, F.act_b, A, kH, kH);
-        } else {
-            store_layer(slab, L1, lane, F.vf_w1, F.vf_b1, kH, D, D);
-            store_layer(slab, L2, lane, F.vf_w2, F.vf_b2, kH, kH, kH);
-            store_layer(slab, L3, lane, F.val_w, F.val_b, 1, kH, kH);
-        }
-    }
-    if (tid == 0) store_slab_stats(slab + F.total, misc);
+    // the body needs: DP, AP, VCLIP, BC (template parameters), KICK, K and the arguments above
+    constexpr bool KICK = false;
+    [[maybe_unused]] const KickArgs K{nullptr, 0.0f};
+#include "mse_ppo_grad_body.inc"
+}
+
+// KICK: PPO with an imitation term (mse_ppo_bc_loss_grad).  The actor reads K.expert_actions at the row it reads `actions` at,
+// its head is policy_bc_head_terms with K.bc_coef, and it carries seven sums (ce, hits, unusable rows after the four); the slab
+// is slab_stride_kick wide and the misc strip kKickMiscFloats long.  The critic, the advantage pass, the gate, the row clamping
+// and the grid rule are the same statements (mse_ppo_grad_body.inc).
+template <int DP, int AP, bool VCLIP>
+__global__ __launch_bounds__(256) void k_ppo_grad_kick(GradArgs G, const float *__restrict__ weights, const long long *__restrict__ rows,
+                                                       const float *__restrict__ obs, const uint8_t *__restrict__ mask,
+                                                       const int *__restrict__ actions, const float *__restrict__ old_logp,
+                                                       const float *__restrict__ adv, const float *__restrict__ ret,
+                                                       const double *__restrict__ adv_partial, float *__restrict__ slabs,
+                                                       const int *__restrict__ control, const float *__restrict__ old_values,
+                                                       KickArgs K)
+{
+    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K and the arguments above
+    constexpr bool BC = false, KICK = true;
+#include "mse_ppo_grad_body.inc"
 }
 
 // grad_out[i] = sum over slabs, in slab order, in double; the last workgroup turns the loss sums into stats_out
-__global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int w_total, const float *__restrict__ slabs,
-                                                    const long long *__restrict__ rows, const float *__restrict__ adv,
-                                                    const double *__restrict__ adv_partial, float *__restrict__ grad_out,
-                                                    float *__restrict__ stats_out, Gate gate)
+// KICK: the slabs are slab_stride_kick apart; stats_out is f32[12]: [0] gains bc_coef * bc_loss, [8] bc_loss = mean ce,
+// [9] hits / batch, [10] unusable rows / batch, [11] 0.  false is the kernel as it was without the flag and never reads bc_coef.
+template <bool KICK>
+__device__ __forceinline__ void ppo_reduce_body(const GradArgs &G, int n_slabs, int w_total, const float *__restrict__ slabs,
+                                                const long long *__restrict__ rows, const float *__restrict__ adv,
+                                                const double *__restrict__ adv_partial, float *__restrict__ grad_out,
+                                                float *__restrict__ stats_out, const Gate &gate, float bc_coef)
 {
-    const long long stride = slab_stride(w_total);
+    const long long stride = KICK ? slab_stride_kick(w_total) : slab_stride(w_total);
     if (gate.control != nullptr && slabs[w_total + kGateCell] != 0.0f) return; // the gate as k_ppo_grad saw it
     if (blockIdx.x + 1 < gridDim.x) {
         const int i = blockIdx.x * 256 + threadIdx.x;
@@ -362,8 +242,8 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
         grad_out[i] = (float)s;
         return;
     }
-    __shared__ double sums[kStatFloats];
-    if (threadIdx.x < kStatSums) {
+    __shared__ double sums[KICK ? kKickStatFloats : kStatFloats];
+    if (threadIdx.x < kStatSums || (KICK && threadIdx.x >= kKickCe && threadIdx.x < kKickCe + 3)) {
         double s = 0.0;
 #pragma unroll 8
         for (int g = 0; g < n_slabs; ++g) s += (double)slabs[(long long)g * stride + w_total + threadIdx.x];
@@ -374,7 +254,16 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
         float mean = 0.0f, std = 1.0f;
         if (G.n_adv_partial > 0) adv_mean_std(adv_partial, G.n_adv_partial, (double)adv[row_at(rows, 0, G.n_rows)], G.batch, mean, std);
         const double policy_loss = sums[0], value_loss = sums[1], entropy_loss = -sums[2];
-        stats_out[0] = (float)(policy_loss + (double)G.P.ent_coef * entropy_loss + (double)G.P.vf_coef * value_loss);
+        if constexpr (KICK) {
+            const double bc_loss = sums[kKickCe];
+            stats_out[0] = (float)(policy_loss + (double)G.P.ent_coef * entropy_loss + (double)G.P.vf_coef * value_loss + (double)bc_coef * bc_loss);
+            stats_out[8] = (float)bc_loss;
+            stats_out[9] = (float)sums[kKickCe + 1];
+            stats_out[10] = (float)sums[kKickCe + 2];
+            stats_out[11] = 0.0f;
+        } else {
+            stats_out[0] = (float)(policy_loss + (double)G.P.ent_coef * entropy_loss + (double)G.P.vf_coef * value_loss);
+        }
         stats_out[1] = (float)policy_loss;
         stats_out[2] = (float)value_loss;
         stats_out[3] = (float)entropy_loss;
@@ -388,6 +277,22 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int
             if (gate.kl_limit > 0.0 && (double)stats_out[4] > gate.kl_limit) gate.control[0] = 1;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void k_ppo_reduce(GradArgs G, int n_slabs, int w_total, const float *__restrict__ slabs,
+                                                    const long long *__restrict__ rows, const float *__restrict__ adv,
+                                                    const double *__restrict__ adv_partial, float *__restrict__ grad_out,
+                                                    float *__restrict__ stats_out, Gate gate)
+{
+    ppo_reduce_body<false>(G, n_slabs, w_total, slabs, rows, adv, adv_partial, grad_out, stats_out, gate, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void k_ppo_reduce_kick(GradArgs G, int n_slabs, int w_total, const float *__restrict__ slabs,
+                                                         const long long *__restrict__ rows, const float *__restrict__ adv,
+                                                         const double *__restrict__ adv_partial, float *__restrict__ grad_out,
+                                                         float *__restrict__ stats_out, Gate gate, float bc_coef)
+{
+    ppo_reduce_body<true>(G, n_slabs, w_total, slabs, rows, adv, adv_partial, grad_out, stats_out, gate, bc_coef);
 }
 
 // ---- clip_grad_norm_ + Adam, one workgroup ----------------------------------------------------------------------------
@@ -477,6 +382,21 @@ void launch_grad(const GradArgs &G, int n_slabs, hipStream_t s, const float *wei
                            old_logp, adv, ret, adv_partial, slabs, control, old_values);
 }
 
+// enqueues the KICK entry of the same body: one more misc strip size, two more arguments
+template <int DP, int AP>
+void launch_grad_kick(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                      const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret,
+                      const double *adv_partial, float *slabs, const int *control, const float *old_values, const KickArgs &K)
+{
+    const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kKickMiscFloats) * sizeof(float);
+    if (old_values != nullptr)
+        hipLaunchKernelGGL((k_ppo_grad_kick<DP, AP, true>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                           old_logp, adv, ret, adv_partial, slabs, control, old_values, K);
+    else
+        hipLaunchKernelGGL((k_ppo_grad_kick<DP, AP, false>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
+                           old_logp, adv, ret, adv_partial, slabs, control, old_values, K);
+}
+
 // enqueues the BC instantiation of k_ppo_grad: no old log-probabilities, advantages, gate or old values
 template <int DP, int AP>
 void launch_grad_bc(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
@@ -491,12 +411,13 @@ void launch_grad_bc(const GradArgs &G, int n_slabs, hipStream_t s, const float *
 // mse_ppo_loss_grad (control == NULL), mse_ppo_loss_grad_gated, mse_ppo_loss_grad_matrix (matrix: the gradient launch is
 // k_ppo_grad_matrix of mse_ppo_matrix.hip; everything around it is the same) and mse_ppo_loss_grad_vclip (old_values != NULL:
 // the gradient launch is the VCLIP instantiation with clip_range_vf, which the entry point has checked); `who` names the
-// entry point in messages
+// entry point in messages.  mse_ppo_bc_loss_grad (kick): the KICK gradient launch of either arithmetic on expert_actions with
+// bc_coef, wider slabs, and k_ppo_reduce_kick
 int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
               int64_t batch, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
               const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out, float *stats_out,
               void *workspace, void *stream, Gate gate, int arithmetic = 0, const float *old_values = nullptr,
-              double clip_range_vf = 0.0)
+              double clip_range_vf = 0.0, bool kick = false, const int32_t *expert_actions = nullptr, double bc_coef = 0.0)
 {
     auto fail = [who](int status, const char *why) { return mse_internal_fail(status, (std::string(who) + ": " + why).c_str()); };
     if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
@@ -517,6 +438,11 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
     const float c_vf = old_values != nullptr ? (float)clip_range_vf : 0.0f; // without old_values clip_range_vf is not read
     if (old_values != nullptr && !(std::isfinite(clip_range_vf) && c_vf > 0.0f && std::isfinite(c_vf)))
         return fail(MSE_ERR_INVALID_ARGUMENT, "clip_range_vf must be finite and > 0 (as a float32) with old_values");
+    // what only mse_ppo_bc_loss_grad can get wrong, after everything above: the labels, then the coefficient
+    if (kick && expert_actions == nullptr) return fail(MSE_ERR_INVALID_ARGUMENT, "null expert_actions");
+    if (kick && !(std::isfinite(bc_coef) && bc_coef >= 0.0 && std::isfinite((float)bc_coef)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "bc_coef must be finite and >= 0 (as a float32)");
+    const KickArgs K{expert_actions, (float)bc_coef};
     const int cus = cu_count();
     if (cus <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -533,7 +459,16 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
     }
     const int n_slabs = (int)grad_groups(batch, cus);
     hipError_t e = hipSuccess;
-    if (arithmetic == 1) {
+    if (kick && arithmetic == 1) {
+        e = mse_ppo_launch_grad_matrix_kick(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns,
+                                            adv_partial, slabs, gate.control, old_values, K);
+    } else if (kick) {
+#define MSE_PPO_LAUNCH_KICK(DP, AP)                                                                                                     \
+    launch_grad_kick<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial, slabs, \
+                             gate.control, old_values, K)
+        MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH_KICK);
+#undef MSE_PPO_LAUNCH_KICK
+    } else if (arithmetic == 1) {
         e = mse_ppo_launch_grad_matrix(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, adv_partial,
                                        slabs, gate.control, old_values);
     } else {
@@ -546,8 +481,13 @@ int loss_grad(const char *who, int obs_dim, int n_actions, const float *weights_
     }
     if (e == hipSuccess) {
         const int w_total = flat_layout(obs_dim, n_actions).total;
-        hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((w_total + 255) / 256 + 1)), dim3(256), 0, s, G, n_slabs, w_total, slabs, rows,
-                           advantages, adv_partial, grad_out, stats_out, gate);
+        const dim3 grid((unsigned)((w_total + 255) / 256 + 1));
+        if (kick)
+            hipLaunchKernelGGL(k_ppo_reduce_kick, grid, dim3(256), 0, s, G, n_slabs, w_total, slabs, rows, advantages, adv_partial, grad_out,
+                               stats_out, gate, K.bc_coef);
+        else
+            hipLaunchKernelGGL(k_ppo_reduce, grid, dim3(256), 0, s, G, n_slabs, w_total, slabs, rows, advantages, adv_partial, grad_out,
+                               stats_out, gate);
         e = hipGetLastError();
     }
     if (e != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
@@ -644,6 +584,27 @@ int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev
                      advantages, returns, params, grad_out, stats_out, workspace, stream,
                      control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, arithmetic, old_values,
                      clip_range_vf);
+}
+
+int64_t mse_ppo_bc_workspace_bytes(int obs_dim, int n_actions)
+{
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32) return 0;
+    const long long w = flat_layout(obs_dim, n_actions).total;
+    return (int64_t)(kMaxAdvPartials * 2 * sizeof(double) + (size_t)kMaxSlabs * slab_stride_kick(w) * sizeof(float));
+}
+
+int mse_ppo_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,
+                         const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                         const float *advantages, const float *returns, const mse_ppo_params *params, float *grad_out,
+                         float *stats_out, void *workspace, void *stream, double target_kl, int32_t *control_dev, int arithmetic,
+                         const float *old_values, double clip_range_vf, const int32_t *expert_actions, double bc_coef)
+{
+    if (control_dev != nullptr && target_kl != target_kl)
+        return mse_internal_fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_bc_loss_grad: target_kl is NaN");
+    return loss_grad("mse_ppo_bc_loss_grad", obs_dim, n_actions, weights_dev, n_rows, rows_dev, batch, obs, mask, actions, old_logp,
+                     advantages, returns, params, grad_out, stats_out, workspace, stream,
+                     control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, arithmetic, old_values,
+                     clip_range_vf, true, expert_actions, bc_coef);
 }
 
 int mse_bc_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev, int64_t batch,

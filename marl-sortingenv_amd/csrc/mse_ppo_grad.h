@@ -32,6 +32,14 @@ constexpr int kGateCell = 5;
 
 __host__ __device__ constexpr long long slab_stride(long long w) { return (w + kStatFloats + 3) / 4 * 4; }
 
+// The KICK instantiations (PPO with an imitation term, mse_ppo_bc_loss_grad) carry three more sums than the slab has free cells,
+// so THEIR slabs are four floats wider: cells 0 .. 7 as above, then
+//   8 cross-entropy of the label   9 hits   10 unusable rows   11 zero
+// and their workspace is sized by mse_ppo_bc_workspace_bytes.  The other kernels' slabs are as they were.
+constexpr int kKickStatFloats = 12;
+constexpr int kKickCe = 8; // first of the three
+__host__ __device__ constexpr long long slab_stride_kick(long long w) { return (w + kKickStatFloats + 3) / 4 * 4; }
+
 // rows a workgroup takes per pass of its grid-stride loop: two tile slots of 64 rows.  Used by the host rule below only: the
 // kernels' tile loops state the two slots and the 64 rows themselves (tile = 2 blockIdx.x + (wave >> 1), row = 64 tile + lane)
 constexpr int kRowsPerGroup = 128;
@@ -144,6 +152,40 @@ __device__ __forceinline__ void store_slab_stats(float *s, const float *misc)
     s[5] = s[6] = s[7] = 0.0f;
 }
 
+// ... and of a KICK instantiation, whose actor waves carry seven sums (the four above, then ce, hits, unusable): its misc
+// strip is kKickMiscFloats long, [0] and [1] as above, [4 + 8 w + k] loss sum k of wave w
+constexpr int kKickMiscFloats = 36;
+
+__device__ __forceinline__ void publish_loss_sums_kick(float *misc, int wave, int lane, const float (&sum)[7])
+{
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) misc[4 + 8 * wave + k] = sum[k];
+    }
+}
+
+// cells 0 .. 7 are store_slab_stats' with the same additions; s has kKickStatFloats cells
+__device__ __forceinline__ void store_slab_stats_kick(float *s, const float *misc)
+{
+    const float(*sh)[8] = reinterpret_cast<const float(*)[8]>(misc + 4);
+    s[0] = sh[0][0] + sh[2][0]; // surrogate
+    s[1] = sh[1][0] + sh[3][0]; // squared value error
+    s[2] = sh[0][1] + sh[2][1]; // entropy
+    s[3] = sh[0][2] + sh[2][2]; // kl
+    s[4] = sh[0][3] + sh[2][3]; // clipped
+    s[5] = s[6] = s[7] = 0.0f;
+    s[kKickCe] = sh[0][4] + sh[2][4];     // cross-entropy of the label
+    s[kKickCe + 1] = sh[0][5] + sh[2][5]; // hits
+    s[kKickCe + 2] = sh[0][6] + sh[2][6]; // unusable rows
+    s[kKickCe + 3] = 0.0f;
+}
+
+// what a KICK instantiation reads beyond the other kernels' arguments; {NULL, 0} for those, which never read it
+struct KickArgs {
+    const int *expert_actions; // i32[n_rows]: the label of every row
+    float bc_coef;
+};
+
 } // namespace mseppo
 
 // mse_ppo_matrix.hip: enqueues k_ppo_grad_matrix on `n_slabs` workgroups; it writes what k_ppo_grad writes.  Returns
@@ -160,3 +202,8 @@ hipError_t mse_ppo_launch_grad_matrix(const mseppo::GradArgs &G, int n_slabs, hi
 hipError_t mse_ppo_launch_grad_matrix_bc(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
                                          const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                          const float *ret, float *slabs);
+// ... the KICK entry (PPO with an imitation term on K.expert_actions); it writes what k_ppo_grad_kick writes
+hipError_t mse_ppo_launch_grad_matrix_kick(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+                                           const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
+                                           const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
+                                           float *slabs, const int *control, const float *old_values, const mseppo::KickArgs &K);

@@ -8,6 +8,8 @@
 //                       MaskablePPO.train and the gradient of  policy_loss + ent_coef * entropy_loss  w.r.t. the logits
 //   bc_head_terms       behaviour cloning: the cross-entropy of a demonstrated action under the same masked softmax, its
 //                       accuracy / unusable-row counts and the gradient of  ce + ent_coef * entropy_loss  (restates no SB3 code)
+//   policy_bc_head_terms  PPO with an auxiliary imitation term: policy_head_terms and bc_head_terms on one masked softmax, the
+//                       gradient of  policy_loss + ent_coef * entropy_loss + bc_coef * ce  (DAPG / kickstarting; no SB3 code)
 //   value_head_terms    F.mse_loss(returns, values) and its gradient
 //   value_head_terms_clipped   the same for PPO.train's clip_range_vf: values clipped to within c of the rollout's
 //   ev_groups / ev_lane_sums / ev_from_sums   explained_variance(values, returns), the sums and their order in full
@@ -414,6 +416,88 @@ MSE_PPO_HD BcTerms bc_head_terms(float (&logit)[AP], int A, uint32_t legal, int 
         const bool ok = a < A && ((legal >> a) & 1u);
         const float onehot = a == action ? 1.0f : 0.0f;
         const float d = g_logp * (onehot - p[a]) + ge * (p[a] * (logit[a] + 1.0f) - p[a] * rest);
+        logit[a] = ok ? d : 0.0f;
+    }
+    return t;
+}
+
+// ---- PPO with an auxiliary imitation term: both heads on one masked softmax ----------------------------------------------------
+struct PolicyBcTerms {
+    float surrogate, entropy, kl, clipped, logp; // policy_head_terms' five, for the action taken
+    float ce;       // -log p(expert), 0 where the label is illegal under the mask
+    float hit;      // 1 where the row is usable and the argmax of the masked logits is the label
+    float unusable; // 1 where the label is illegal under the mask
+};
+
+// logit[a] (a < A real, the rest padding) -> terms; on return logit[] holds
+//   d/d logit of ( surrogate + ent_coef * (-entropy) + bc_coef * ce ) * inv_b    (0 for illegal actions and for the padding).
+// float32, every operation rounded separately.  The masked softmax (illegal logits at -1e8, then lse, p[a], lp[a], entropy,
+// mass, rest) and the PPO terms of `action` (ratio, clamped, surrogate, kl, clipped, g_logp) are policy_head_terms' to the
+// letter; `action` arrives clamped, as it does there.  `expert` is the label, clamped into [0, A) here (clamped_action's
+// rule); usable = bit `expert` of legal:
+//   ce   = usable ? -lp[expert] : 0
+//   hit  = usable && argmax(masked f32 logits, ties to the lowest index) == expert        (bc_head_terms' rule)
+//   g_bc = usable ? -(bc_coef * inv_b) : 0                                                (the product rounded once, then negated)
+//   logit[a] = g_logp (onehot(a == action) - p[a])  +  g_bc (onehot(a == expert) - p[a])
+//              +  ent_coef inv_b (p[a] (lp[a] + 1) - p[a] rest)                           for legal a
+// The three summands are added left to right.  With bc_coef = 0 the middle one is +-0, so the sum of the first two is the
+// first under ==, and every logit[a] and every PPO term equals policy_head_terms' under ==.  A row whose label the mask forbids
+// adds 0 to ce and to the gradient and 1 to unusable, and keeps its PPO and entropy terms.
+template <int AP>
+MSE_PPO_HD PolicyBcTerms policy_bc_head_terms(float (&logit)[AP], int A, uint32_t legal, int action, int expert, float old_logp,
+                                              float adv, const Params &P, float bc_coef, float inv_b)
+{
+    expert = expert < 0 ? 0 : (expert >= A ? A - 1 : expert);
+    float m = -INFINITY;
+    int best = 0;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        if (a < A) {
+            logit[a] = ((legal >> a) & 1u) ? logit[a] : kMaskedLogit;
+            best = logit[a] > m ? a : best;
+            m = fmaxf(m, logit[a]);
+        }
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a)
+        if (a < A) s += expf(logit[a] - m);
+    const float lse = m + logf(s);
+    float p[AP];
+    float ent = 0.0f, mass = 0.0f, logp_act = 0.0f, logp_exp = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float lp = logit[a] - lse;
+        p[a] = ok ? expf(lp) : 0.0f;
+        logit[a] = ok ? lp : 0.0f; // now the log-probability
+        ent -= ok ? p[a] * lp : 0.0f;
+        mass += p[a];
+        if (a == action) logp_act = a < A ? lp : 0.0f; // (an illegal action keeps its -1e8-based log-probability)
+        if (a == expert) logp_exp = lp;
+    }
+    const bool usable = ((legal >> expert) & 1u) != 0;
+    PolicyBcTerms t;
+    t.logp = logp_act;
+    t.entropy = ent;
+    const float log_ratio = logp_act - old_logp;
+    const float ratio = expf(log_ratio);
+    const float clamped = fminf(fmaxf(ratio, 1.0f - P.clip_range), 1.0f + P.clip_range);
+    const float s1 = adv * ratio, s2 = adv * clamped;
+    t.surrogate = -fminf(s1, s2);
+    t.kl = (ratio - 1.0f) - log_ratio;
+    t.clipped = fabsf(ratio - 1.0f) > P.clip_range ? 1.0f : 0.0f;
+    t.ce = usable ? -logp_exp : 0.0f;
+    t.hit = usable && best == expert ? 1.0f : 0.0f;
+    t.unusable = usable ? 0.0f : 1.0f;
+    const float g_logp = s1 <= s2 ? -(adv * ratio) * inv_b : 0.0f;
+    const float g_bc = usable ? -(bc_coef * inv_b) : 0.0f;
+    const float ge = P.ent_coef * inv_b, rest = mass - ent; // sum over legal a of p (log p + 1)
+#pragma unroll
+    for (int a = 0; a < AP; ++a) {
+        const bool ok = a < A && ((legal >> a) & 1u);
+        const float on_act = a == action ? 1.0f : 0.0f, on_exp = a == expert ? 1.0f : 0.0f;
+        const float d = g_logp * (on_act - p[a]) + g_bc * (on_exp - p[a]) + ge * (p[a] * (logit[a] + 1.0f) - p[a] * rest);
         logit[a] = ok ? d : 0.0f;
     }
     return t;

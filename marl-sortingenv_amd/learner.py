@@ -11,6 +11,8 @@ computes anything on this path, and there is no CPU fallback.  With `shuffle="de
 SB3's `clip_range_vf` is a second instantiation of either gradient kernel (`mse_ppo_loss_grad_vclip`), its schedules are
 host arithmetic on `progress_remaining` (`resolve_schedule`), and `train/explained_variance` is one more small kernel per
 update (`mse_explained_variance`).
+`bc_coef` adds an imitation term to the loss (`mse_ppo_bc_loss_grad`: the rule-based controller's labels of the rollout's own
+states, `data["expert_actions"]`, in the same gradient launch), so that fine-tuning a cloned policy does not forget its teacher.
 `learn` can report the reference's unit, cumulative reward per episode (episodes.py): SB3's `rollout/ep_rew_mean` from an
 `EpisodeStats` over the training rollouts, and `EvalCallback`'s periodic `evaluate_policy` with the best weights kept.
 `state_dict` / `load_state_dict` carry everything of a run that lives here, and `learn(first_iteration=...,
@@ -30,6 +32,8 @@ from .episodes import EpisodeStats, evaluate_policy
 from .policy import MlpPolicy
 
 STAT_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
+# the columns with `bc_coef` set (`mse_ppo_bc_loss_grad`): `loss` then includes bc_coef * bc_loss; the last one is always 0
+PPO_BC_STAT_NAMES = STAT_NAMES + ("bc_loss", "bc_accuracy", "bc_unusable", "reserved")
 
 
 def _ptr(x):
@@ -152,13 +156,22 @@ class PPOLearner:
     sets it, `learn` sets it to `1 - (it + 1) / iterations` before update `it` - SB3's order, in which `num_timesteps`
     has already counted the rollout about to be trained on, so the last update of a linear schedule runs at 0.  The three
     are evaluated once at the top of each `update()` into `learning_rate` (the `lr` of the Adam launches), `clip_range`
-    (written into `params`) and `clip_range_vf`.  With plain numbers nothing is evaluated and nothing changes."""
+    (written into `params`) and `clip_range_vf`.  With plain numbers nothing is evaluated and nothing changes.
+
+    `bc_coef` (None = off; a number >= 0 or a schedule, which may reach 0): the minibatch loss gains `bc_coef * bc_loss`,
+    the cross-entropy of the rule-based controller's action under the policy's masked softmax at every rollout row (DAPG /
+    kickstarting).  Every `loss_grad` then goes through `mse_ppo_bc_loss_grad`, with either arithmetic, gated or not, with
+    or without `clip_range_vf`, and reads `data["expert_actions"]` (i32, one per row: the collectors' `expert_labels=True`).
+    A row whose label the mask forbids adds nothing to that term.  The statistics have twelve columns (PPO_BC_STAT_NAMES).
+    With None everything is exactly what it was without the argument."""
+
+    bc_coef: Optional[float] = None  # off unless the constructor sets it
 
     def __init__(self, policy: MlpPolicy, learning_rate: Schedule = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
                  gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: Schedule = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
                  seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None,
-                 arithmetic: str = "fma", clip_range_vf: Optional[Schedule] = None):
+                 arithmetic: str = "fma", clip_range_vf: Optional[Schedule] = None, bc_coef: Optional[Schedule] = None):
         if shuffle not in ("cpu", "device"):
             raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
         if weight_sync not in ("host", "device"):
@@ -171,13 +184,14 @@ class PPOLearner:
         # a callable is kept as the schedule and evaluated at progress 1 for now; update() re-evaluates it
         self.progress_remaining = 1.0
         self.schedules = {name: v for name, v in (("learning_rate", learning_rate), ("clip_range", clip_range),
-                                                  ("clip_range_vf", clip_range_vf)) if callable(v)}
+                                                  ("clip_range_vf", clip_range_vf), ("bc_coef", bc_coef)) if callable(v)}
         if "learning_rate" in self.schedules:
             learning_rate = resolve_schedule(learning_rate, 1.0, "learning_rate", allow_zero=True)
         if "clip_range" in self.schedules:
             clip_range = resolve_schedule(clip_range, 1.0, "clip_range", allow_zero=True)
         self.clip_range = float(clip_range)
         self.clip_range_vf = None if clip_range_vf is None else resolve_schedule(clip_range_vf, 1.0, "clip_range_vf")
+        self.bc_coef = None if bc_coef is None else resolve_schedule(bc_coef, 1.0, "bc_coef", allow_zero=True)
         self.policy, self.L = policy, policy.L
         self.learning_rate, self.n_epochs, self.batch_size = float(learning_rate), int(n_epochs), batch_size
         self.gamma, self.gae_lambda = float(gamma), float(gae_lambda)
@@ -195,7 +209,8 @@ class PPOLearner:
         self.m = torch.zeros_like(self.grad)
         self.v = torch.zeros_like(self.grad)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
-        ws = int(self.L.mse_ppo_workspace_bytes(policy.obs_dim, policy.n_actions))
+        ws = int((self.L.mse_ppo_workspace_bytes if self.bc_coef is None else self.L.mse_ppo_bc_workspace_bytes)(
+            policy.obs_dim, policy.n_actions))
         self.workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
         self.step = 0  # Adam steps taken
         self.last_permutations: list = []  # the CPU permutations of the last update(), one per epoch (shuffle="cpu")
@@ -213,7 +228,9 @@ class PPOLearner:
         gradient tensor.  rows: i64 device tensor of row indices, or None for rows 0 .. batch - 1.
         control: i32[2] device tensor {stopped, minibatches_run}: `mse_ppo_loss_grad_gated` with `target_kl` instead.
         With `arithmetic="matrix"` both go to `mse_ppo_loss_grad_matrix`.  With `clip_range_vf` set, all of them go to
-        `mse_ppo_loss_grad_vclip` with `data["values"]` (f32[K, N], contiguous) as the old values."""
+        `mse_ppo_loss_grad_vclip` with `data["values"]` (f32[K, N], contiguous) as the old values.  With `bc_coef` set, all
+        of them go to `mse_ppo_bc_loss_grad` with `data["expert_actions"]` (i32[K, N], contiguous) as the labels, and
+        stats_out is f32[12]."""
         p = self.policy
         obs = data["observations"]
         n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
@@ -231,6 +248,16 @@ class PPOLearner:
             old = data["values"]
             if old.dtype != torch.float32 or not old.is_contiguous() or old.numel() != n_rows or old.device != obs.device:
                 raise ValueError("clip_range_vf needs data['values']: contiguous f32, one per rollout row, on the rollout's device")
+        if self.bc_coef is not None:
+            expert = data.get("expert_actions")
+            if not isinstance(expert, torch.Tensor) or expert.dtype != torch.int32 or not expert.is_contiguous() \
+                    or expert.numel() != n_rows or expert.device != obs.device:
+                raise ValueError("bc_coef needs data['expert_actions']: contiguous i32, one per rollout row, on the rollout's "
+                                 "device (collect with expert_labels=True: PolicyRolloutCollector or FusedPolicyRollout)")
+            with torch.cuda.device(self.device):
+                check(self.L.mse_ppo_bc_loss_grad(*args, float(target_kl), _ptr(control), 1 if self.arithmetic == "matrix" else 0,
+                                                  _ptr(old), float(self.clip_range_vf or 0.0), _ptr(expert), float(self.bc_coef)))
+            return g
         with torch.cuda.device(self.device):
             if old is not None:
                 check(self.L.mse_ppo_loss_grad_vclip(*args, float(target_kl), _ptr(control), 1 if self.arithmetic == "matrix" else 0,
@@ -302,6 +329,8 @@ class PPOLearner:
             self.params.clip_range = self.clip_range
         if "clip_range_vf" in self.schedules:
             self.clip_range_vf = resolve_schedule(self.schedules["clip_range_vf"], p, "clip_range_vf")
+        if "bc_coef" in self.schedules:
+            self.bc_coef = resolve_schedule(self.schedules["bc_coef"], p, "bc_coef", allow_zero=True)
 
     def explained_variance(self, data: dict, out: torch.Tensor) -> None:
         """One `mse_explained_variance` over all rows of `data["values"]` / `data["returns"]` into `out` (f32[1], device),
@@ -320,7 +349,7 @@ class PPOLearner:
         """Everything the constructor fixes that changes results, as plain data: the dims, the constructor's numbers and
         modes, `scheduled` (the names of the fields that are schedules) and the plain values of the other ones of
         `learning_rate`, `clip_range`, `clip_range_vf`.  `ent_coef` / `vf_coef` are read back from `params`, i.e. as the
-        f32 the kernels get."""
+        f32 the kernels get.  `bc_coef` is there (as a value, or under `scheduled`) only when it is set."""
         hp = {"obs_dim": self.policy.obs_dim, "n_actions": self.policy.n_actions, "n_epochs": self.n_epochs,
               "batch_size": None if self.batch_size is None else int(self.batch_size), "gamma": self.gamma,
               "gae_lambda": self.gae_lambda, "ent_coef": float(self.params.ent_coef), "vf_coef": float(self.params.vf_coef),
@@ -331,12 +360,15 @@ class PPOLearner:
         for name in ("learning_rate", "clip_range", "clip_range_vf"):
             if name not in self.schedules:
                 hp[name] = getattr(self, name)
+        if self.bc_coef is not None and "bc_coef" not in self.schedules:
+            hp["bc_coef"] = self.bc_coef
         return hp
 
     def state_dict(self) -> dict:
         """The run state as CPU tensors and plain data: `weights`, `m`, `v`, `step`, `epochs_done`, the CPU generator's
         state (`generator`, its `get_state()` bytes), `progress_remaining`, the resolved `learning_rate` / `clip_range` /
-        `clip_range_vf`, `best_mean_reward`, `best_weights` and `episode_stats` (its state dict) when there are any, and
+        `clip_range_vf` (and `bc_coef` when it is set), `best_mean_reward`, `best_weights` and `episode_stats` (its state
+        dict) when there are any, and
         `hyperparameters()`.  Schedules are callables and are not stored: construct the learner with them again."""
         from .checkpoint import cpu, generator_state
 
@@ -345,6 +377,8 @@ class PPOLearner:
               "progress_remaining": float(self.progress_remaining), "learning_rate": self.learning_rate,
               "clip_range": self.clip_range, "clip_range_vf": self.clip_range_vf,
               "best_mean_reward": float(self.best_mean_reward), "hyperparameters": self.hyperparameters()}
+        if self.bc_coef is not None:
+            sd["bc_coef"] = self.bc_coef
         if self.best_weights is not None:
             sd["best_weights"] = cpu(self.best_weights)
         if self.episode_stats is not None:
@@ -368,7 +402,8 @@ class PPOLearner:
             if isinstance(sd.get(key), bool) or not isinstance(sd.get(key), int) or sd[key] < 0:
                 raise ValueError(f"PPOLearner: {key} must be a non-negative int, the checkpoint has {sd.get(key)!r}")
         if strict:
-            for key in ("learning_rate", "clip_range", "clip_range_vf", "progress_remaining"):
+            for key in ("learning_rate", "clip_range", "clip_range_vf", "progress_remaining") + \
+                    (("bc_coef",) if self.bc_coef is not None else ()):
                 if key not in sd:
                     raise ValueError(f"PPOLearner: the checkpoint has no {key}")
         es = sd.get("episode_stats")
@@ -402,6 +437,8 @@ class PPOLearner:
             self.learning_rate, self.clip_range = float(sd["learning_rate"]), float(sd["clip_range"])
             self.clip_range_vf = None if sd["clip_range_vf"] is None else float(sd["clip_range_vf"])
             self.params.clip_range = self.clip_range
+            if self.bc_coef is not None:
+                self.bc_coef = float(sd["bc_coef"])
         else:
             self._resolve_schedules()
         self.best_mean_reward = float(sd.get("best_mean_reward", float("-inf")))
@@ -420,7 +457,8 @@ class PPOLearner:
         the device once per epoch; shuffle="device": one `mse_ppo_shuffle` launch per epoch; the last minibatch of an
         epoch may be short), one loss_grad + adam_step per minibatch without a host
         synchronisation, then the weights' hand-over to the policy (`weight_sync`).  Returns {"stats":
-        f32[n_minibatches, 8] (device; columns STAT_NAMES), "mean": {name: float}}.
+        f32[n_minibatches, 8] (device; columns STAT_NAMES), "mean": {name: float}}; with `bc_coef` set the columns are
+        the twelve of PPO_BC_STAT_NAMES, and "mean" gains `bc_loss`, `bc_accuracy`, `bc_unusable`.
         With `target_kl` the result gains "stopped" (bool) and "minibatches_run" (int): "mean" is over the first
         minibatches_run rows of "stats", the rows after them stay zero.
         progress_remaining: sets `self.progress_remaining` first; the schedules are then evaluated once, here.
@@ -438,17 +476,19 @@ class PPOLearner:
         per_epoch = (total + bs - 1) // bs
         n_mb = self.n_epochs * per_epoch
         gated = self.target_kl is not None
+        names = STAT_NAMES if self.bc_coef is None else PPO_BC_STAT_NAMES[:11]
+        w = 8 if self.bc_coef is None else 12  # columns of a minibatch's statistics
         ev = None
         if gated or explained_variance:  # statistics, control block and explained variance in one buffer: one copy brings all
             n_ctl, n_ev = (2 if gated else 0), (1 if explained_variance else 0)
-            buf = torch.zeros(n_mb * 8 + n_ctl + n_ev, dtype=torch.float32, device=self.device)
-            stats = buf[:n_mb * 8].view(n_mb, 8)
-            control = buf[n_mb * 8:n_mb * 8 + n_ctl].view(torch.int32) if gated else None
+            buf = torch.zeros(n_mb * w + n_ctl + n_ev, dtype=torch.float32, device=self.device)
+            stats = buf[:n_mb * w].view(n_mb, w)
+            control = buf[n_mb * w:n_mb * w + n_ctl].view(torch.int32) if gated else None
             if explained_variance:
-                ev = buf[n_mb * 8 + n_ctl:]
+                ev = buf[n_mb * w + n_ctl:]
                 self.explained_variance(data, ev)
         else:
-            stats, control = torch.zeros((n_mb, 8), dtype=torch.float32, device=self.device), None
+            stats, control = torch.zeros((n_mb, w), dtype=torch.float32, device=self.device), None
         step0 = self.step
         for i, rows in enumerate(self._minibatches(total, bs)):
             self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
@@ -458,18 +498,18 @@ class PPOLearner:
             if ev is None:
                 mean = stats.mean(dim=0).cpu().tolist()
                 self.policy.sync()
-                return {"stats": stats, "mean": dict(zip(STAT_NAMES, mean))}
+                return {"stats": stats, "mean": dict(zip(names, mean))}
             host = torch.cat((stats.mean(dim=0), ev)).cpu().tolist()  # still one copy
             self.policy.sync()
-            return {"stats": stats, "mean": dict(zip(STAT_NAMES, host[:8])), "explained_variance": host[8]}
+            return {"stats": stats, "mean": dict(zip(names, host[:w])), "explained_variance": host[w]}
         host = buf.cpu()
         self.policy.sync()
-        stopped, run = (int(x) for x in host[n_mb * 8:n_mb * 8 + 2].view(torch.int32))
+        stopped, run = (int(x) for x in host[n_mb * w:n_mb * w + 2].view(torch.int32))
         self.step = step0 + run - (1 if stopped else 0)  # the stopping minibatch took no step, nor did any after it
-        mean = host[:n_mb * 8].view(n_mb, 8)[:run].mean(dim=0).tolist()
-        out = {"stats": stats, "mean": dict(zip(STAT_NAMES, mean)), "stopped": bool(stopped), "minibatches_run": run}
+        mean = host[:n_mb * w].view(n_mb, w)[:run].mean(dim=0).tolist()
+        out = {"stats": stats, "mean": dict(zip(names, mean)), "stopped": bool(stopped), "minibatches_run": run}
         if ev is not None:
-            out["explained_variance"] = float(host[n_mb * 8 + 2])
+            out["explained_variance"] = float(host[n_mb * w + 2])
         return out
 
     def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
@@ -486,7 +526,7 @@ class PPOLearner:
         `best_weights` (`restore_best()` loads them back).  With the defaults the records and the device work are
         what they were without these arguments.
         Before update `it` `progress_remaining` becomes `1 - (it + 1) / iterations`.  A record gains `learning_rate` and
-        `clip_range` (the values that update used) when either is a schedule, `clip_range_vf` when it is set, and
+        `clip_range` (the values that update used) when either is a schedule, `clip_range_vf` and `bc_coef` when set, and
         `explained_variance` with explained_variance=True.
         first_iteration: the loop runs `it` in range(first_iteration, iterations) with `progress_remaining` as above, so
         a run resumed from a checkpoint (`load_checkpoint`, then first_iteration = its "iteration") is on the same
@@ -510,6 +550,8 @@ class PPOLearner:
                 rec.update(learning_rate=self.learning_rate, clip_range=self.clip_range)
             if self.clip_range_vf is not None:
                 rec.update(clip_range_vf=self.clip_range_vf)
+            if self.bc_coef is not None:
+                rec.update(bc_coef=self.bc_coef)
             if explained_variance:
                 rec.update(explained_variance=out["explained_variance"])
             return rec

@@ -4,7 +4,8 @@
 
 For every kernel, matched by its mangled name, it compares the instruction lines (comments and assembler directives
 stripped, labels kept - but without the function's ordinal in the listing, which the compiler writes into every local
-label (.LBB17_4, .LJTI17_0): a kernel added in front of others shifts that number and nothing else) and the kernel's
+label (.LBB17_4, .LJTI17_0): a kernel added in front of others shifts that number and nothing else; likewise the listing-wide
+count in a long branch's .Lpost_getpc<n>, renumbered per kernel by first appearance) and the kernel's
 metadata: VGPR / AGPR / SGPR counts, spill counts, private and group segment sizes.  It prints one summary line
 and, for each kernel that differs, its name and both instruction counts.  Exit status 1 on any difference, a kernel
 present in only one listing included.  A refactor of the device code is checked with this instead of a timing run."""
@@ -16,6 +17,15 @@ META = (".agpr_count", ".vgpr_count", ".sgpr_count", ".sgpr_spill_count", ".vgpr
 
 
 ORDINAL = re.compile(r"\.L([A-Za-z_]+?)\d+_(\d+)")  # .LBB<function ordinal>_<block> -> .LBB_<block>
+# .Lpost_getpc<n>, the label of a long branch's s_getpc_b64: n counts the long branches of the whole listing, so a kernel
+# added in front shifts it like the ordinal.  Within a kernel the labels are renumbered by first appearance, so which label
+# an instruction names is still compared.
+LONG_BRANCH = re.compile(r"\.Lpost_getpc(\d+)")
+
+
+def renumber_long_branches(text):
+    seen = {}
+    return [LONG_BRANCH.sub(lambda m: ".Lpost_getpc#%d" % seen.setdefault(m.group(1), len(seen)), t) for t in text]
 
 
 def kernels(path):
@@ -40,7 +50,7 @@ def kernels(path):
             end = next(j for j in range(i, len(lines)) if lines[j].startswith(".Lfunc_end"))
             text = [ORDINAL.sub(r".L\1_\2", t) for t in (b.split(";")[0].strip() for b in lines[i + 1:end])
                     if t and (t[0] != "." or t.endswith(":"))]
-            out[name] = (text, tuple(meta[name].get(k) for k in META))
+            out[name] = (renumber_long_branches(text), tuple(meta[name].get(k) for k in META))
     return out
 
 

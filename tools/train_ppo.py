@@ -34,6 +34,11 @@
                                                           # per collection (FusedDemonstrationRollout); --beta-schedule
                                                           # one | linear | first: beta 1 throughout (pure cloning), 1 - the
                                                           # fraction of iterations done, or 1 in the first iteration only
+    python tools/train_ppo.py --kind mono --pretrain rule_based --dagger --bc-coef 1 --bc-schedule linear --eval-every 10
+                                                          # PPO with an imitation term: the rule-based controller labels
+                                                          # the rollout PPO trains on (expert_labels=True) and the loss
+                                                          # gains bc_coef * bc_loss; linear: bc_coef times
+                                                          # progress_remaining, which reaches 0 in the last iteration
     python tools/train_ppo.py --time --time-section demo  # collect() of FusedDemonstrationRollout beside
                                                           # DemonstrationCollector(actor=student) and the plain policy rollout
 
@@ -223,9 +228,11 @@ def time_arithmetic(args):
 
 
 def time_bc(args):
-    """`mse_bc_loss_grad` beside `mse_ppo_loss_grad` on Env_3's shape at 4 096, 65 536 and 2^20 rows, both arithmetics:
-    rows_dev = NULL, one warm-up, then back-to-back calls ending in one synchronise, the time per call; the four calls
-    alternating, three timed repetitions each.  The cloning call gets the PPO rollout's rows with the rule's labels."""
+    """`mse_bc_loss_grad` and `mse_ppo_bc_loss_grad` beside `mse_ppo_loss_grad` on Env_3's shape at 4 096, 65 536 and 2^20
+    rows, both arithmetics: rows_dev = NULL, one warm-up, then back-to-back calls ending in one synchronise, the time per
+    call; the six calls alternating, three timed repetitions each.  The cloning call gets the PPO rollout's rows with the
+    rule's labels; the PPO call with the imitation term gets the PPO rollout with the labels of a twin's states beside it
+    (any labels cost the same)."""
     D, A = M.OBS_DIM["mono"], M.NUM_ACTIONS["mono"]
     K = 16
     for rows in (4096, 65536, 2 ** 20):
@@ -235,12 +242,14 @@ def time_bc(args):
         data = M.compute_gae(M.FusedPolicyRollout(env, pol, K, seed=args.seed).collect())
         demo_env = M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
         demo = M.DemonstrationCollector(demo_env, K).collect()
-        stats = torch.zeros(8, device="cuda")
+        stats = torch.zeros(12, device="cuda")
         calls = 20 if rows <= 65536 else 5
+        labelled = dict(data, expert_actions=demo["actions"])
         group = {}
         for f in ("fma", "matrix"):
             group[f"ppo {f}"] = (M.PPOLearner(pol, ent_coef=0.05, arithmetic=f), data)
             group[f"bc {f}"] = (M.ImitationLearner(pol, ent_coef=0.05, arithmetic=f), demo)
+            group[f"ppo+bc {f}"] = (M.PPOLearner(pol, ent_coef=0.05, arithmetic=f, bc_coef=1.0), labelled)
         times = {name: [] for name in group}
         for r in range(4):
             for name, (lrn, d) in group.items():
@@ -274,6 +283,8 @@ def time_demo(args):
             "twin actor=student": M.DemonstrationCollector(env(n), K, actor=pol, seed=args.seed),
             "twin expert only": M.DemonstrationCollector(env(n), K),
             "policy rollout (plain kernel)": M.FusedPolicyRollout(env(n, rollout_pipeline=2), pol, K, seed=args.seed),
+            "labelled rollout": M.FusedPolicyRollout(env(n), pol, K, seed=args.seed, expert_labels=True),
+            "labelled twin": M.PolicyRolloutCollector(env(n), pol, K, seed=args.seed, expert_labels=True),
         }
         times = {name: [] for name in group}
         for r in range(4):
@@ -412,6 +423,11 @@ def main():
     ap.add_argument("--beta-schedule", choices=sorted(BETA_SCHEDULES), default="linear",
                     help="with --dagger: the share of steps the expert takes - 'one': all of them (pure cloning), 'linear': 1 minus "
                          "the fraction of cloning iterations done, 'first': all in the first iteration, none afterwards")
+    ap.add_argument("--bc-coef", type=float, default=None, metavar="X",
+                    help="PPO with an imitation term: the loss gains X times the cross-entropy of the rule-based controller's "
+                         "action at every rollout row (the collector then labels its rollout: expert_labels=True)")
+    ap.add_argument("--bc-schedule", choices=("const", "linear"), default="const",
+                    help="with --bc-coef: linear is X times progress_remaining, which reaches 0 in the last iteration")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo"), default="all",
                     help="with --time: run one block of the timings only")
@@ -436,9 +452,13 @@ def main():
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
     env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
-    col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
+    if args.bc_coef is None:
+        col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
+    else:  # the rollout PPO trains on, with the rule's label of every state it visits, in one launch
+        col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed, expert_labels=True)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
     clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    bc_coef = (lambda p: args.bc_coef * p) if args.bc_coef is not None and args.bc_schedule == "linear" else args.bc_coef
     eval_col = None
     if args.eval_every > 0:
         eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
@@ -448,15 +468,19 @@ def main():
         pretrain(args, pol, args.kind, "own", "the policy", eval_col if args.dagger else None)
     learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
-                           arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
+                           arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf, bc_coef=bc_coef)
     print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
           f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}, "
-          f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}")
+          f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}"
+          + (f", bc_coef {args.bc_coef:g} {args.bc_schedule}" if args.bc_coef is not None else ""))
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
               f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
 
+        if "bc_coef" in rec:
+            print(f"       bc_coef {rec['bc_coef']:.4f} bc_loss {rec['bc_loss']:.4f} bc_accuracy {rec['bc_accuracy']:.4f} "
+                  f"bc_unusable {rec['bc_unusable']:.4f}")
         if "learning_rate" in rec:
             print(f"       learning_rate {rec['learning_rate']:.3e} clip_range {rec['clip_range']:.4f}")
         if "explained_variance" in rec:
