@@ -402,6 +402,45 @@ int mse_rollout_modular(mse_env *env, mse_policy *sort_agent, mse_policy *press_
 int mse_rollout_modular_check(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps,
                               uint64_t sort_seed, uint64_t press_seed, uint32_t flags);
 
+/* ---- mse_rollout_modular with the rule-based controller in the same launch: its label of every recorded state in the two
+ * agents' halves, and the DAgger mixture of mse_rollout_demo deciding per env and step who steps.  Per step k and env i:
+ *   1. mse_rollout_modular's steps 1-4, unchanged: previews, press_action_masks(), the rows, both agents' action,
+ *      log-probability and value.  sort_actions / press_actions are the agents' own draws whoever steps, so they match
+ *      the recorded log-probabilities;
+ *   2. the label: the flat rule-based action of the state before the step, exactly what mse_rule_actions returns for it
+ *      (mse_rollout_demo's label); no stream is read or advanced.  sort_expert_actions[k,i] = label / 11,
+ *      press_expert_actions[k,i] = label % 11;
+ *   3. who steps: mse_rollout_demo's step 4 with the word of (mix_seed, global env index, t + k) - the expert iff
+ *      (w >> 8) < expert_threshold, an integer in [0, 2^24]; mse_demo_who_steps_host is the same rule on the host.  One
+ *      decision covers both halves: the stepped flat action is the label, or 11 sort + press;
+ *   4. stepped_actions i32[K,N] (that flat action), expert_stepped u8[K,N] (1: the label was stepped); the action is
+ *      stepped as mse_step steps it without MSE_STEP_UNMASKED, MSE_STEP_CHECK_OVERFLOW honoured, auto-reset on termination;
+ *   5. rewards, reward parts, bootstrap values, last_dones and the state write-back as in mse_rollout_modular.
+ * Any pointer inside either struct may be NULL.  The flags are mse_rollout_modular's four.
+ * CONTRACT: with expert_threshold = 0 every mse_modular_buffers output, the written-back state and the policy step counter
+ * are bit-identical to mse_rollout_modular on the same handle.  For every threshold the env's rng_sorting / rng_pressing
+ * planes are neither read nor written, and the policy step counter advances by K.
+ * The shape is mse_rollout_modular's (both wave forms; no roles shape).
+ * Refusals, in this order: mse_rollout_modular's, in its own order; expert_threshold > 2^24; mix_seed equal to sort_seed
+ * or press_seed, whatever the threshold; out or labels NULL, or a struct_size mismatch (all MSE_ERR_INVALID_ARGUMENT).  A
+ * refused call writes nothing and leaves the step counter unchanged. */
+typedef struct mse_modular_label_buffers {
+    uint32_t struct_size; /* = sizeof(mse_modular_label_buffers); ABI check */
+    uint32_t reserved0;
+    int32_t *sort_expert_actions;  /* i32[K,N] */
+    int32_t *press_expert_actions; /* i32[K,N] */
+    int32_t *stepped_actions;      /* i32[K,N], flat */
+    uint8_t *expert_stepped;       /* u8[K,N] */
+} mse_modular_label_buffers;
+int mse_rollout_modular_labelled(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps,
+                                 uint64_t sort_seed, uint64_t press_seed, uint64_t mix_seed, uint32_t expert_threshold,
+                                 uint32_t flags, const mse_modular_buffers *out, const mse_modular_label_buffers *labels,
+                                 void *stream);
+/* The status mse_rollout_modular_labelled would return for these arguments, its checks on out / labels left out; no launch */
+int mse_rollout_modular_labelled_check(mse_env *env, mse_policy *sort_agent, mse_policy *press_agent, int32_t k_steps,
+                                       uint64_t sort_seed, uint64_t press_seed, uint64_t mix_seed, uint32_t expert_threshold,
+                                       uint32_t flags);
+
 /* ---- Demonstrations on the states a student visits (DAgger): K steps in ONE launch in which the rule-based controller
  * labels every visited state and, per env and step, either its action or a student policy's is stepped.
  * Per step k and env i, in this order:

@@ -34,6 +34,7 @@ EXPORTS = [
     "mse_bc_loss_grad", "mse_ppo_bc_workspace_bytes", "mse_ppo_bc_loss_grad",
     "mse_rollout_demo", "mse_rollout_demo_check", "mse_demo_who_steps_host",
     "mse_rollout_policy_labelled", "mse_rollout_policy_labelled_check",
+    "mse_rollout_modular_labelled", "mse_rollout_modular_labelled_check",
 ]
 
 _other_libs: dict = {}
@@ -90,6 +91,16 @@ DEMO_BUFFER_NAMES = ("observations", "action_masks", "episode_starts", "labels",
 class MseDemoBuffers(C.Structure):
     """struct mse_demo_buffers (include/mse.h)"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(name, C.c_void_p) for name in DEMO_BUFFER_NAMES]
+
+
+# the pointer members of struct mse_modular_label_buffers, in the header's order (= the keys a labelled modular collector adds)
+MODULAR_LABEL_BUFFER_NAMES = ("sort_expert_actions", "press_expert_actions", "stepped_actions", "expert_stepped")
+
+
+class MseModularLabelBuffers(C.Structure):
+    """struct mse_modular_label_buffers (include/mse.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + \
+               [(name, C.c_void_p) for name in MODULAR_LABEL_BUFFER_NAMES]
 
 
 _lib = None
@@ -161,6 +172,9 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_rollout_model.argtypes = [vp, vp, vp, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_modular.argtypes = [vp, vp, vp, i32, u64, u64, u32, C.POINTER(MseModularBuffers), vp]
     L.mse_rollout_modular_check.argtypes = [vp, vp, vp, i32, u64, u64, u32]
+    L.mse_rollout_modular_labelled.argtypes = [vp, vp, vp, i32, u64, u64, u64, u32, u32, C.POINTER(MseModularBuffers),
+                                               C.POINTER(MseModularLabelBuffers), vp]
+    L.mse_rollout_modular_labelled_check.argtypes = [vp, vp, vp, i32, u64, u64, u64, u32, u32]
     L.mse_rollout_demo.argtypes = [vp, vp, i32, u64, u64, u32, u32, C.POINTER(MseDemoBuffers), vp]
     L.mse_rollout_demo_check.argtypes = [vp, vp, i32, u64, u64, u32, u32]
     L.mse_rollout_policy_labelled.argtypes = [vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]

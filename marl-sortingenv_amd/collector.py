@@ -323,7 +323,7 @@ def modular_view(buffers: dict, who: str, reward: str = "own", press_masked: boo
     rkey = "rewards" if reward == "team" else f"rewards_{who}"
     if buffers.get(rkey) is None:
         raise KeyError(f"this collector does not fill {rkey!r} (the multi-launch twin has no reward parts)")
-    return {
+    view = {
         "observations": buffers[f"{who}_obs"],
         "action_masks": buffers["press_masks"] if who == "press" and press_masked else None,
         "actions": buffers[f"{who}_actions"],
@@ -334,24 +334,108 @@ def modular_view(buffers: dict, who: str, reward: str = "own", press_masked: boo
         "last_values": buffers[f"{who}_last_values"],
         "last_dones": buffers["last_dones"],
     }
+    if buffers.get(f"{who}_expert_actions") is not None:  # a labelled collector: that agent's half of the label
+        view["expert_actions"] = buffers[f"{who}_expert_actions"]
+    return view
+
+
+def _modular_label_buffers(n: int, K: int, dev, returns: bool = False) -> dict:
+    """What `expert_labels=True` adds to `_modular_buffers`: struct mse_modular_label_buffers' members, and `returns`
+    with a `gamma`."""
+    b = {"sort_expert_actions": torch.empty((K, n), dtype=I32, device=dev),
+         "press_expert_actions": torch.empty((K, n), dtype=I32, device=dev),
+         "stepped_actions": torch.empty((K, n), dtype=I32, device=dev),
+         "expert_stepped": torch.empty((K, n), dtype=U8, device=dev)}
+    if returns:
+        b["returns"] = torch.empty((K, n), dtype=F32, device=dev)
+    return b
+
+
+def demo_view(buffers: dict, who: str, press_masked: bool = True) -> dict:
+    """One agent's part of a LABELLED modular collector's buffer dict as `DemonstrationCollector(agent=who)`'s dict, what
+    an `ImitationLearner` consumes; every value IS the buffer's tensor (no copy).  `actions` is that agent's half of the
+    rule-based label, `rewards` the team reward, `returns` its discounted reward-to-go (None without a `gamma`);
+    `action_masks` is None for the sorter, and for the presser when it was not shown its mask.  Buffers without labels
+    are refused by name."""
+    if who not in ("sort", "press"):
+        raise ValueError(f"who must be 'sort' or 'press', not {who!r}")
+    if buffers.get(f"{who}_expert_actions") is None:
+        raise KeyError(f"demo_view: this collector does not fill '{who}_expert_actions' (construct it with expert_labels=True)")
+    return {
+        "observations": buffers[f"{who}_obs"],
+        "action_masks": buffers["press_masks"] if who == "press" and press_masked else None,
+        "actions": buffers[f"{who}_expert_actions"],
+        "stepped_actions": buffers["stepped_actions"],
+        "expert_stepped": buffers["expert_stepped"],
+        "rewards": buffers["rewards"],
+        "episode_starts": buffers["episode_starts"],
+        "last_dones": buffers["last_dones"],
+        "returns": buffers.get("returns"),
+    }
+
+
+def modular_mix_seed(sort_seed: int, press_seed: int, mix_seed: Optional[int] = None) -> int:
+    """The seed of the who-steps stream of a labelled modular collector: `mix_seed`, or by default one past the larger agent
+    seed.  A seed that is one of the agents' is refused: who steps and what that agent draws would come from one word."""
+    mix = max(int(sort_seed), int(press_seed)) + 1 if mix_seed is None else int(mix_seed)
+    if mix in (int(sort_seed), int(press_seed)):
+        raise ValueError("mix_seed equals an agent's seed: who steps and what that agent draws would come from one word")
+    return mix
 
 
 class _ModularBase(_CollectorState):
     """Constructor and views the fused modular collector and its multi-launch twin share.  Checkpoint: _CollectorState's
-    with both seeds - the kernel derives `episode_starts` from the env state, which also carries the policy step counter."""
+    with both seeds - the kernel derives `episode_starts` from the env state, which also carries the policy step counter;
+    a labelled collector adds `mix_seed` (checked like the seeds) and `beta` (restored).
+
+    expert_labels=True: every recorded state also carries the rule-based controller's action in its two halves
+    (`sort_expert_actions` = a // 11, `press_expert_actions` = a % 11; `view()` hands them to `PPOLearner(bc_coef=...)` as
+    `expert_actions`), and per env and step the label is stepped with probability `beta`, else the agents' 11 sort + press
+    (`stepped_actions`, `expert_stepped`): DAgger's mixture, decided by a word of `mix_seed`'s stream against
+    `imitation.expert_threshold(beta)`; one decision covers both halves.  `beta` may be set between calls.  gamma: `collect()`
+    also fills `returns`, the discounted reward-to-go of the team reward (`mse_gae` with zero values and lambda = 1,
+    `DemonstrationCollector`'s definition).  `demo_view(who)` is what an `ImitationLearner` of that agent consumes."""
 
     KIND = "modular"
     SEEDS = ("sort_seed", "press_seed")
     PARTS = True  # fills rewards_sort / rewards_press
 
     def __init__(self, env: BatchedSortingEnv, sort_agent: MlpPolicy, press_agent: MlpPolicy, n_steps: int,
-                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True):
+                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True, expert_labels: bool = False,
+                 beta: float = 0.0, mix_seed: Optional[int] = None, gamma: Optional[float] = None):
         _check_modular(env, sort_agent, press_agent, n_steps, sort_seed, press_seed)
+        self.expert_labels = bool(expert_labels)
+        if not self.expert_labels and (mix_seed is not None or gamma is not None):
+            raise ValueError("mix_seed / gamma belong to the labelled rollout: they need expert_labels=True")
         self.env, self.sort_agent, self.press_agent = env, sort_agent, press_agent
         self.n_steps, self.sort_seed, self.press_seed = int(n_steps), int(sort_seed), int(press_seed)
         self.press_masked = bool(press_masked)
-        self.buffers = _modular_buffers(env.num_envs, self.n_steps, env.device, self.PARTS)
+        self.mix_seed = modular_mix_seed(sort_seed, press_seed, mix_seed) if self.expert_labels else None
+        self.gamma = None if gamma is None else float(gamma)
+        self.beta = beta  # refuses NaN, values outside [0, 1], and anything but 0 without labels
+        if self.expert_labels:
+            self.SEEDS = type(self).SEEDS + ("mix_seed",)
+        n, K, dev = env.num_envs, self.n_steps, env.device
+        self.buffers = _modular_buffers(n, K, dev, self.PARTS)
+        if self.expert_labels:
+            self.buffers.update(_modular_label_buffers(n, K, dev, returns=self.gamma is not None))
+        if self.gamma is not None:
+            self._zeros = torch.zeros((K + 1, n), dtype=F32, device=dev)  # mse_gae's values and last_values
+            self._adv = torch.empty((K, n), dtype=F32, device=dev)
         self._views: dict = {}
+
+    @property
+    def beta(self) -> float:
+        return self._beta
+
+    @beta.setter
+    def beta(self, value: float) -> None:
+        from .imitation import expert_threshold
+
+        threshold = expert_threshold(value)
+        if not self.expert_labels and threshold != 0:
+            raise ValueError("beta != 0 needs expert_labels=True: without labels there is no expert to step")
+        self._beta, self._threshold = float(value), threshold
 
     def view(self, who: str, reward: str = "own") -> dict:
         """`modular_view` of this collector's buffers.  The dict of a (who, reward) pair is kept, so the advantages and
@@ -361,18 +445,67 @@ class _ModularBase(_CollectorState):
             self._views[key] = modular_view(self.buffers, who, reward, self.press_masked)
         return self._views[key]
 
+    def demo_view(self, who: str) -> dict:
+        """`demo_view` of this collector's buffers (kept per agent); refused on a collector without labels."""
+        if not self.expert_labels:
+            raise ValueError("demo_view needs a collector constructed with expert_labels=True")
+        key = (who, "demo")
+        if key not in self._views:
+            self._views[key] = demo_view(self.buffers, who, self.press_masked)
+        return self._views[key]
+
     def _check_run(self, n_steps) -> int:
         K = self.n_steps if n_steps is None else int(n_steps)
         if not 1 <= K <= self.n_steps:
             raise ValueError("n_steps must be in [1, the collector's K]")
         return K
 
+    def _fill_returns(self, K: int) -> None:
+        """One `mse_gae` launch over the first K rows: zero values, lambda = 1, no bootstrap at the window's end."""
+        import ctypes as C
+
+        from ._lib import check
+
+        env, b = self.env, self.buffers
+
+        def ptr(x):
+            return C.c_void_p(x.data_ptr())
+
+        with torch.cuda.device(env.device):
+            check(env.L.mse_gae(K, env.num_envs, ptr(b["rewards"]), ptr(self._zeros), ptr(b["episode_starts"]),
+                                ptr(self._zeros[K]), ptr(b["last_dones"]), self.gamma, 1.0, ptr(self._adv), ptr(b["returns"]),
+                                env._stream()))
+
+    # ---- checkpoint: a labelled collector's who-steps stream and mixture ---------------------------------------------------
+    def _extra_state(self) -> dict:
+        return {"beta": self._beta} if self.expert_labels else {}
+
+    def check_state_dict(self, sd: dict) -> None:
+        super().check_state_dict(sd)
+        if ("mix_seed" in sd) != self.expert_labels:
+            raise ValueError(f"{type(self).__name__}: the checkpoint is of a collector "
+                             f"{'with' if 'mix_seed' in sd else 'without'} expert labels, this one is "
+                             f"{'with' if self.expert_labels else 'without'}")
+        if self.expert_labels:
+            from .imitation import expert_threshold
+
+            if isinstance(sd.get("beta"), bool) or not isinstance(sd.get("beta"), (int, float)):
+                raise ValueError(f"{type(self).__name__}: beta must be a number, the checkpoint has {sd.get('beta')!r}")
+            expert_threshold(sd["beta"])
+
+    def load_state_dict(self, sd: dict) -> None:
+        super().load_state_dict(sd)
+        if self.expert_labels:
+            self.beta = sd["beta"]
+
 
 class FusedModularRollout(_ModularBase):
     """The sorting agent (13 -> 2) and the pressing agent (16 -> 11) acting side by side in Env_3_Monolith, K steps per
     launch (`mse_rollout_modular`): per agent the rows a `PPOLearner` consumes - observations, actions,
     log-probabilities, values, the bootstrap value - plus the step's reward whole (`rewards`) and in its two parts
-    (`rewards_sort`, `rewards_press`).  press_masked: the pressing agent is maskable and sees press_action_masks()."""
+    (`rewards_sort`, `rewards_press`).  press_masked: the pressing agent is maskable and sees press_action_masks().
+    expert_labels=True (see `_ModularBase`): `collect()` is one `mse_rollout_modular_labelled` launch - plus one `mse_gae`
+    launch with a `gamma` - and at beta = 0 every other buffer holds the bits of the plain launch."""
 
     def collect(self, n_steps: Optional[int] = None, sort_deterministic: bool = False, press_deterministic: bool = False,
                 check_overflow: bool = False) -> dict:
@@ -389,6 +522,18 @@ class FusedModularRollout(_ModularBase):
                 (MSE_MODULAR_SORT_DETERMINISTIC if sort_deterministic else 0) | \
                 (MSE_MODULAR_PRESS_DETERMINISTIC if press_deterministic else 0)
         out = MseModularBuffers(C.sizeof(MseModularBuffers), 0, *(b[name].data_ptr() for name in MODULAR_BUFFER_NAMES))
+        if self.expert_labels:
+            from ._lib import MODULAR_LABEL_BUFFER_NAMES, MseModularLabelBuffers
+
+            labels = MseModularLabelBuffers(C.sizeof(MseModularLabelBuffers), 0,
+                                            *(b[name].data_ptr() for name in MODULAR_LABEL_BUFFER_NAMES))
+            with torch.cuda.device(env.device):
+                check(env.L.mse_rollout_modular_labelled(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
+                                                         self.press_seed, self.mix_seed, self._threshold, flags, C.byref(out),
+                                                         C.byref(labels), env._stream()))
+            if self.gamma is not None:
+                self._fill_returns(K)
+            return b
         with torch.cuda.device(env.device):
             check(env.L.mse_rollout_modular(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
                                             self.press_seed, flags, C.byref(out), env._stream()))
@@ -409,21 +554,42 @@ class ModularRolloutCollector(_ModularBase):
     SNAP_CURRENT_STEP = 32  # column of mse_get_state's integer record that holds the env's current_step
 
     def __init__(self, env: BatchedSortingEnv, sort_agent: MlpPolicy, press_agent: MlpPolicy, n_steps: int,
-                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True):
-        super().__init__(env, sort_agent, press_agent, n_steps, sort_seed, press_seed, press_masked)
-        self._refusal(self.n_steps, 0)  # what mse_rollout_modular would refuse on this handle, with these agents
+                 sort_seed: int = 2024, press_seed: int = 2025, press_masked: bool = True, expert_labels: bool = False,
+                 beta: float = 0.0, mix_seed: Optional[int] = None, gamma: Optional[float] = None):
+        """expert_labels=True: per step also `env.rule_actions()` with its halves // 11 and % 11, the who-steps rule on the
+        host (`mse_demo_who_steps_host`) and the step of the chosen flat action: `mse_rollout_modular_labelled`'s twin."""
+        super().__init__(env, sort_agent, press_agent, n_steps, sort_seed, press_seed, press_masked, expert_labels, beta,
+                         mix_seed, gamma)
+        self._refusal(self.n_steps, 0)  # what the fused launch would refuse on this handle, with these agents
         self._last_done = torch.empty((env.num_envs,), dtype=torch.uint8, device=env.device)
         self._sort_out = self._press_out = None
+        self._who_host = torch.empty((env.num_envs,), dtype=torch.uint8) if self.expert_labels else None
 
     def _refusal(self, K: int, flags: int) -> None:
-        """Raises what `FusedModularRollout.collect` would raise for the same arguments (`mse_rollout_modular_check`:
-        the kernel's own checks - the handle, the agents' form, an attached trace, tables that do not fit - and no
-        launch)."""
+        """Raises what `FusedModularRollout.collect` would raise for the same arguments (`mse_rollout_modular_check`, or
+        `mse_rollout_modular_labelled_check` with labels: the kernel's own checks - the handle, the agents' form, an
+        attached trace, tables that do not fit, the threshold and the mixture seed - and no launch)."""
         from ._lib import MSE_MODEL_PRESS_AGENT_MASKED, check
 
         env = self.env
+        flags |= MSE_MODEL_PRESS_AGENT_MASKED if self.press_masked else 0
+        if self.expert_labels:
+            check(env.L.mse_rollout_modular_labelled_check(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
+                                                           self.press_seed, self.mix_seed, self._threshold, flags))
+            return
         check(env.L.mse_rollout_modular_check(env._h, self.sort_agent._h, self.press_agent._h, K, self.sort_seed,
-                                              self.press_seed, flags | (MSE_MODEL_PRESS_AGENT_MASKED if self.press_masked else 0)))
+                                              self.press_seed, flags))
+
+    def _who_steps(self, t: int) -> torch.Tensor:
+        """bool[N] on the device: the expert steps env j at step counter t (`mse_demo_who_steps_host`)."""
+        import ctypes as C
+
+        from ._lib import check
+
+        env, w = self.env, self._who_host
+        check(env.L.mse_demo_who_steps_host(env.num_envs, env.index_offset, self.mix_seed, int(t), self._threshold,
+                                            C.c_void_p(w.data_ptr())))
+        return w.to(env.device).bool()
 
     def collect(self, n_steps: Optional[int] = None, sort_deterministic: bool = False, press_deterministic: bool = False,
                 check_overflow: bool = False) -> dict:
@@ -453,8 +619,17 @@ class ModularRolloutCollector(_ModularBase):
                 b[f"{who}_actions"][k].copy_(o["action"])
                 b[f"{who}_log_probs"][k].copy_(o["logp"])
                 b[f"{who}_values"][k].copy_(o["value"])
+            action = 11 * self._sort_out["action"] + self._press_out["action"]
+            if self.expert_labels:
+                rule = env.rule_actions()  # of the state the rows show; no stream is read
+                who = self._who_steps(t)
+                action = torch.where(who, rule, action)
+                b["sort_expert_actions"][k].copy_(rule // 11)
+                b["press_expert_actions"][k].copy_(rule % 11)
+                b["stepped_actions"][k].copy_(action)
+                b["expert_stepped"][k].copy_(who)
             # applied without sanitising (env_monolith.py:254-257): the masked step
-            _, rew, done, _ = env.step(11 * self._sort_out["action"] + self._press_out["action"], check_overflow=check_overflow)
+            _, rew, done, _ = env.step(action, check_overflow=check_overflow)
             b["rewards"][k].copy_(rew)
             self._last_done.copy_(done)
         t = env.policy_step
@@ -465,4 +640,6 @@ class ModularRolloutCollector(_ModularBase):
         b["sort_last_values"].copy_(last_s["value"])
         b["press_last_values"].copy_(last_p["value"])
         b["last_dones"].copy_(self._last_done)
+        if self.gamma is not None:
+            self._fill_returns(K)
         return b

@@ -1713,6 +1713,14 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
 // r_press).  No fallback draws: the env's rng_sorting / rng_pressing planes are neither read nor written.
 // LDS: [sorting agent image][pressing agent image][tables][per wave: row tile | bale ledger]
 // ==========================================================================================
+// a reference to `a` or to `b`, chosen at compile time (mse_rollout_modular_body.inc: which Params the step reads)
+template <bool FIRST, class T>
+__device__ __forceinline__ const T &mse_first_if(const T &a, const T &b)
+{
+    if constexpr (FIRST) return a;
+    else return b;
+}
+
 template <bool NOISE, int TILES>
 __global__ __launch_bounds__(512) void k_rollout_modular(Params P, uint4 *__restrict__ planes,
                                                          const uint32_t *__restrict__ table_image,
@@ -1721,159 +1729,34 @@ __global__ __launch_bounds__(512) void k_rollout_modular(Params P, uint4 *__rest
                                                          uint64_t sort_seed, uint64_t press_seed, uint64_t policy_t0,
                                                          uint32_t flags, const mse_modular_buffers out)
 {
-    using L = PolLayout<3, TILES>; // k_rollout_model's tile: wide enough for every row this kernel stages
-    constexpr int ENVS = L::ENVS, NR_SORT = msep::regs_for_actions(2), NR_PRESS = msep::regs_for_actions(11);
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
-    constexpr int kWeightBytes = L::weight_bytes * 2; // [sorting agent image][pressing agent image]
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
-    // the batch's end its last env; mirrors store nothing
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
+    // the body needs: NOISE, TILES (template parameters), LABEL, mix_seed, expert_threshold, labels and the arguments above
+    constexpr bool LABEL = false;
+    [[maybe_unused]] constexpr uint64_t mix_seed = 0;
+    [[maybe_unused]] constexpr uint32_t expert_threshold = 0;
+    [[maybe_unused]] constexpr mse_modular_label_buffers labels{};
+#include "mse_rollout_modular_body.inc"
+}
 
-    msep_copy_image(lw, sort_blob, true, tid, blockDim.x);
-    msep_copy_image(lw + msep::kLdsFloats, press_blob, true, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    load_env<3, NOISE>(e, planes, P, i);
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
-    const msep::lds_f4 wl_sort = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
-    const msep::lds_f4 wl_press = (msep::lds_f4)(__attribute__((address_space(3))) float *)(lw + msep::kLdsFloats);
-    const bool agent_masked = (flags & MSE_MODEL_PRESS_AGENT_MASKED) != 0;
-    const bool sort_det = (flags & MSE_MODULAR_SORT_DETERMINISTIC) != 0;
-    const bool press_det = (flags & MSE_MODULAR_PRESS_DETERMINISTIC) != 0;
-    const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // the agents' actions are applied unsanitised
-    // policy stream keys of the env(s) this lane serves as an MFMA column (k_rollout_policy), one pair per agent
-    const int h = lane >> 5, col = lane & 31;
-    const uint64_t g0 = (uint64_t)(P.index_offset + wave_row0 + col), g1 = g0 + 32u;
-    const uint32_t skey0 = mse_policy_key(sort_seed, g0), skey1 = mse_policy_key(sort_seed, g1);
-    const uint32_t pkey0 = mse_policy_key(press_seed, g0), pkey1 = mse_policy_key(press_seed, g1);
-    int kcur[4]; // container purities of the current state (the sorting view needs them)
-    container_purity_k(e, kcur);
-
-    float *ltile = reinterpret_cast<float *>(lwave);
-    const uint32_t lrow_sort = lds_row_address(ltile + src_lane * 13);
-    const uint32_t lrow_press = lds_row_address(ltile + src_lane * 16);
-    const uint32_t lrow_mask = lds_row_address(lwave + src_lane * 11);
-    int last_done = 0;
-    for (int s = 0; s < k_steps; ++s) {
-        const long long srow = (long long)s * P.n + wave_row0;
-        const uint64_t t = policy_t0 + (uint64_t)s;
-        // ---- the agents' views: get_sort_obs() / get_press_obs() one flow update ahead (a copy takes the update)
-        float so[32], po[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) so[j] = po[j] = 0.0f;
-        {
-            Env ec = e;
-            update_environment<false>(ec, P);
-            sort_obs<false>(ec, P, tb, kcur, so);
-            press_obs<false>(ec, P, tb, po);
-        }
-        // press_action_masks() of the state the decision is taken in (the flow update does not change it)
-        const uint32_t pbits = press_mask_bits(e, P);
-        // the rows the decisions are taken from
-        if (out.sort_obs != nullptr) wave_store_rows_f32<13, ENVS>(ltile, lrow_sort, so, out.sort_obs + srow * 13, n_valid, lane);
-        if (out.press_obs != nullptr) wave_store_rows_f32<16, ENVS>(ltile, lrow_press, po, out.press_obs + srow * 16, n_valid, lane);
-        if (out.press_masks != nullptr) wave_store_rows_mask<11, ENVS>(lwave, lrow_mask, pbits, out.press_masks + srow * 11, n_valid, lane);
-        if (live && out.episode_starts != nullptr)
-            __builtin_nontemporal_store((uint8_t)(e.step == 0 ? 1 : 0), &out.episode_starts[(long long)s * P.n + i]);
-        // ---- sorting agent: 13 -> 2, every action legal
-        int sm;
-        float s_logp, s_value;
-        {
-            float sx[2][16];
-            operands_of(so, sx);
-            const uint32_t legal[2] = {legal_of(0x3u, h), legal_of(0x3u, h)};
-            const uint32_t words[2] = {mse_policy_word(skey0, t), mse_policy_word(skey1, t)};
-            msep::TileOut p[2];
-            msep::policy_tiles<NR_SORT, true, TILES>(wl_sort, lane, sx, 2, legal, sort_det, words, nullptr, p);
-            sm = tile_pick<TILES>(h, p[0].action, p[1].action);
-            s_logp = tile_pick<TILES>(h, p[0].logp, p[1].logp);
-            s_value = tile_pick<TILES>(h, p[0].value, p[1].value);
-        }
-        // ---- pressing agent: 16 -> 11, over press_action_masks() when it is maskable and masking is on
-        int pa;
-        float p_logp, p_value;
-        {
-            float px[2][16];
-            operands_of(po, px);
-            uint32_t pb0, pb1;
-            msep::both_halves_u32(agent_masked ? pbits : 0x7FFu, pb0, pb1);
-            const uint32_t legal[2] = {legal_of(pb0, h), legal_of(pb1, h)};
-            const uint32_t words[2] = {mse_policy_word(pkey0, t), mse_policy_word(pkey1, t)};
-            msep::TileOut p[2];
-            msep::policy_tiles<NR_PRESS, true, TILES>(wl_press, lane, px, 11, legal, press_det, words, nullptr, p);
-            pa = tile_pick<TILES>(h, p[0].action, p[1].action);
-            p_logp = tile_pick<TILES>(h, p[0].logp, p[1].logp);
-            p_value = tile_pick<TILES>(h, p[0].value, p[1].value);
-        }
-        const int a = sm * 11 + pa;
-        // ---- the transition under that action, auto-reset on termination
-        float o[32];
-        StepResult r = env_step<3, NOISE, false>(e, P, tb, a, -1, step_flags, bales, kcur, o);
-        if (__builtin_expect(r.done != 0, 0)) auto_reset_env(e, P, tb, bales, kcur);
-        last_done = r.done;
-        if (live) {
-            const long long at = (long long)s * P.n + i;
-            if (out.sort_actions != nullptr) __builtin_nontemporal_store(sm, &out.sort_actions[at]);
-            if (out.press_actions != nullptr) __builtin_nontemporal_store(pa, &out.press_actions[at]);
-            if (out.sort_log_probs != nullptr) __builtin_nontemporal_store(s_logp, &out.sort_log_probs[at]);
-            if (out.press_log_probs != nullptr) __builtin_nontemporal_store(p_logp, &out.press_log_probs[at]);
-            if (out.sort_values != nullptr) __builtin_nontemporal_store(s_value, &out.sort_values[at]);
-            if (out.press_values != nullptr) __builtin_nontemporal_store(p_value, &out.press_values[at]);
-            if (out.rewards != nullptr) __builtin_nontemporal_store((float)r.reward, &out.rewards[at]);
-            if (out.rewards_sort != nullptr) __builtin_nontemporal_store((float)r.r_sort, &out.rewards_sort[at]);
-            if (out.rewards_press != nullptr) __builtin_nontemporal_store((float)r.r_press, &out.rewards_press[at]);
-        }
-    }
-    // the bootstrap values of the state the rollout ends in: each critic alone on its preview of that state
-    if (out.sort_last_values != nullptr || out.press_last_values != nullptr) {
-        float so[32], po[32];
-#pragma unroll
-        for (int j = 0; j < 32; ++j) so[j] = po[j] = 0.0f;
-        {
-            Env ec = e;
-            update_environment<false>(ec, P);
-            sort_obs<false>(ec, P, tb, kcur, so);
-            press_obs<false>(ec, P, tb, po);
-        }
-        float x[2][16], v[2];
-        if (out.sort_last_values != nullptr) {
-            operands_of(so, x);
-            msep::value_tiles<true, TILES>(wl_sort, lane, x, v);
-            if (live) out.sort_last_values[i] = tile_pick<TILES>(h, v[0], v[1]);
-        }
-        if (out.press_last_values != nullptr) {
-            operands_of(po, x);
-            msep::value_tiles<true, TILES>(wl_press, lane, x, v);
-            if (live) out.press_last_values[i] = tile_pick<TILES>(h, v[0], v[1]);
-        }
-    }
-    if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
-    if (live) store_env<3, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+// k_rollout_modular with the rule-based controller in the same launch (DESIGN.md "Labelled modular rollout"): after both
+// agents have sampled, the label rule_based_action<3>() of the state before the step - k_rollout_demo's expression, what
+// mse_rule_actions returns for that state; no stream is read - is written in its halves label / 11 and label % 11, and the
+// integer decision of mse_demo_mix.h on the word of (mix_seed, global env index, t + k) says whether the label or the agents'
+// 11 sort + press is stepped: one decision per env and step for both halves.  sort_actions / press_actions stay the agents' own
+// draws (they match the recorded log-probabilities).  expert_threshold = 0: k_rollout_modular's bits in every one of its
+// outputs - the same statements (mse_rollout_modular_body.inc).
+template <bool NOISE, int TILES>
+__global__ __launch_bounds__(512) void k_rollout_modular_labelled(Params P, uint4 *__restrict__ planes,
+                                                                  const uint32_t *__restrict__ table_image,
+                                                                  const float *__restrict__ sort_blob,
+                                                                  const float *__restrict__ press_blob, int k_steps,
+                                                                  uint64_t sort_seed, uint64_t press_seed, uint64_t mix_seed,
+                                                                  uint32_t expert_threshold, uint64_t policy_t0, uint32_t flags,
+                                                                  const mse_modular_buffers out,
+                                                                  const mse_modular_label_buffers labels)
+{
+    // the body needs: NOISE, TILES (template parameters), LABEL and the arguments above
+    constexpr bool LABEL = true;
+#include "mse_rollout_modular_body.inc"
 }
 
 // ==========================================================================================
@@ -2575,6 +2458,22 @@ static void launch_rollout_modular(mse_env *h, const mse_policy *sort_ag, const 
     }, h->noise_on, plan.tiles == 1);
 }
 
+// mse_rollout_modular_labelled's shape: mse_rollout_modular's, in both wave forms; the caller has checked that the plan fits
+// (rollout_modular_labelled_checks)
+static void launch_rollout_modular_labelled(mse_env *h, const mse_policy *sort_ag, const mse_policy *press_ag, hipStream_t s,
+                                           int k_steps, uint64_t sort_seed, uint64_t press_seed, uint64_t mix_seed,
+                                           uint32_t expert_threshold, uint32_t flags, const mse_modular_buffers &out,
+                                           const mse_modular_label_buffers &labels)
+{
+    const PolicyPlan plan = plan_policy_plain(h->P.n, h->cus, true, 2, policy_lds<3>(h->P));
+    with_flags([&](auto NOISE, auto ONE_TILE) {
+        hipLaunchKernelGGL((k_rollout_modular_labelled<NOISE, ONE_TILE ? 1 : 2>), dim3((unsigned)plan.workgroups),
+                           dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables,
+                           sort_ag->blob, press_ag->blob, k_steps, sort_seed, press_seed, mix_seed, expert_threshold,
+                           h->policy_t, flags, out, labels);
+    }, h->noise_on, plan.tiles == 1);
+}
+
 // mse_rollout_demo's shape: k_rollout_policy's plain one with one network, or with none (no actor: the f16x3 geometry)
 template <int KIND>
 static PolicyPlan plan_rollout_demo(const mse_env *h, const mse_policy *actor)
@@ -3017,6 +2916,46 @@ int mse_rollout_modular(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, i
     if (!out || out->struct_size != sizeof(mse_modular_buffers))
         return fail(MSE_ERR_INVALID_ARGUMENT, "out is NULL or mse_modular_buffers.struct_size mismatch (header/library version skew)");
     launch_rollout_modular(h, sort_ag, press_ag, static_cast<hipStream_t>(stream), k_steps, sort_seed, press_seed, flags, *out);
+    MSE_CHECK_LAUNCH();
+    h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+// everything mse_rollout_modular_labelled refuses, in the order include/mse.h gives: mse_rollout_modular's refusals in its own
+// order, the threshold's range, a mixture seed that is one of the agents', then the two structs when `with_out` is set
+// (mse_rollout_modular_labelled_check has none)
+static int rollout_modular_labelled_checks(mse_env *h, const mse_policy *sort_ag, const mse_policy *press_ag, int32_t k_steps,
+                                           uint64_t sort_seed, uint64_t press_seed, uint64_t mix_seed, uint32_t expert_threshold,
+                                           uint32_t flags, const mse_modular_buffers *out, const mse_modular_label_buffers *labels,
+                                           bool with_out)
+{
+    if (const int rc = rollout_modular_checks(h, sort_ag, press_ag, k_steps, sort_seed, press_seed, flags)) return rc;
+    if (expert_threshold > MSE_DEMO_THRESHOLD_ONE)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "expert_threshold must be in [0, 2^24]");
+    if (mix_seed == sort_seed || mix_seed == press_seed)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mix_seed equals an agent's seed: who steps and what that agent draws would come from one word");
+    if (with_out && (!out || out->struct_size != sizeof(mse_modular_buffers)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "out is NULL or mse_modular_buffers.struct_size mismatch (header/library version skew)");
+    if (with_out && (!labels || labels->struct_size != sizeof(mse_modular_label_buffers)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "labels is NULL or mse_modular_label_buffers.struct_size mismatch (header/library version skew)");
+    return MSE_OK;
+}
+
+int mse_rollout_modular_labelled_check(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, int32_t k_steps, uint64_t sort_seed,
+                                       uint64_t press_seed, uint64_t mix_seed, uint32_t expert_threshold, uint32_t flags)
+{
+    return rollout_modular_labelled_checks(h, sort_ag, press_ag, k_steps, sort_seed, press_seed, mix_seed, expert_threshold, flags,
+                                           nullptr, nullptr, false);
+}
+
+int mse_rollout_modular_labelled(mse_env *h, mse_policy *sort_ag, mse_policy *press_ag, int32_t k_steps, uint64_t sort_seed,
+                                 uint64_t press_seed, uint64_t mix_seed, uint32_t expert_threshold, uint32_t flags,
+                                 const mse_modular_buffers *out, const mse_modular_label_buffers *labels, void *stream)
+{
+    if (const int rc = rollout_modular_labelled_checks(h, sort_ag, press_ag, k_steps, sort_seed, press_seed, mix_seed,
+                                                       expert_threshold, flags, out, labels, true)) return rc;
+    launch_rollout_modular_labelled(h, sort_ag, press_ag, static_cast<hipStream_t>(stream), k_steps, sort_seed, press_seed,
+                                    mix_seed, expert_threshold, flags, *out, *labels);
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
     return MSE_OK;

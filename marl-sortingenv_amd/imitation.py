@@ -132,7 +132,7 @@ class FusedDemonstrationRollout:
     `collect()` is that launch plus the one `mse_gae` launch for `returns`, and returns `DemonstrationCollector`'s dict
     (`observations`, `action_masks`, `actions` = the labels, `stepped_actions`, `rewards`, `episode_starts`,
     `last_dones`, `returns`) plus `expert_stepped` u8[K, N]; the buffers are allocated once.  The modular views ("sort" /
-    "press" on Env_3) stay with `DemonstrationCollector`.  The env's own obs / mask tensors are not refreshed."""
+    "press" on Env_3) have a launch of their own: `FusedModularRollout(expert_labels=True).demo_view(who)`.  The env's own obs / mask tensors are not refreshed."""
 
     def __init__(self, env: BatchedSortingEnv, n_steps: int, actor: Optional[MlpPolicy] = None,
                  deterministic_actor: bool = False, beta: Optional[float] = None, gamma: float = 0.99, seed: int = 2024,

@@ -41,6 +41,16 @@
                                                           # progress_remaining, which reaches 0 in the last iteration
     python tools/train_ppo.py --time --time-section demo  # collect() of FusedDemonstrationRollout beside
                                                           # DemonstrationCollector(actor=student) and the plain policy rollout
+    python tools/train_ppo.py --kind modular --pretrain rule_based --dagger --beta-schedule linear --eval-every 10
+                                                          # the pair cloned jointly on the states it visits itself: a
+                                                          # labelled FusedModularRollout (one launch: both agents, the
+                                                          # expert's label in its two halves, the beta-mixture) and one
+                                                          # ImitationLearner per agent; then PPO
+    python tools/train_ppo.py --kind modular --pretrain rule_based --bc-coef 1 --bc-schedule linear --eval-every 10
+                                                          # the pair's PPO with each agent's half of the label in its loss
+    python tools/train_ppo.py --time --time-section modular_demo  # the labelled modular launch beside the plain one and the twin;
+                                                          # any --kind, and only when named: --time alone (section
+                                                          # 'all') does not run it
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -300,6 +310,38 @@ def time_demo(args):
             f"{name} " + " / ".join(f"{t:.3f}" for t in ts) + f" ms ({n * K / min(ts) / 1e3:.1f} M steps/s)" for name, ts in times.items()))
 
 
+def time_modular_demo(args):
+    """`collect()` of the labelled `FusedModularRollout` (beta 0 and 0.5) beside the plain one and the multi-launch twin
+    `ModularRolloutCollector(expert_labels=True)`, Env_3, K = 16, noise 0, at 65 536 and 262 144 envs: HIP events around each
+    call, one warm-up, then three timed calls each, the collectors alternating (the modular rollout's procedure)."""
+    sort_ag = M.MlpPolicy.random_init(13, 2, seed=args.seed, precision="f16x3")
+    press_ag = M.MlpPolicy.random_init(16, 11, seed=args.seed + 1, precision="f16x3")
+
+    def env(n):
+        return M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+
+    K = 16
+    for n in (65536, 262144):
+        group = {
+            "plain": M.FusedModularRollout(env(n), sort_ag, press_ag, K),
+            "labelled beta=0": M.FusedModularRollout(env(n), sort_ag, press_ag, K, expert_labels=True, beta=0.0),
+            "labelled beta=0.5": M.FusedModularRollout(env(n), sort_ag, press_ag, K, expert_labels=True, beta=0.5),
+            "labelled twin beta=0.5": M.ModularRolloutCollector(env(n), sort_ag, press_ag, K, expert_labels=True, beta=0.5),
+        }
+        times = {name: [] for name in group}
+        for r in range(4):
+            for name, col in group.items():
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                col.collect()
+                stop.record()
+                stop.synchronize()
+                if r > 0:
+                    times[name].append(start.elapsed_time(stop))
+        print(f"modular {n} envs x {K} steps: collect() " + ", ".join(
+            f"{name} " + " / ".join(f"{t:.3f}" for t in ts) + f" ms ({n * K / min(ts) / 1e3:.1f} M steps/s)" for name, ts in times.items()))
+
+
 BETA_SCHEDULES = {"one": 1.0, "linear": lambda f: 1.0 - f, "first": lambda f: 1.0 if f == 0.0 else 0.0}
 
 
@@ -329,35 +371,68 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
                     beta=BETA_SCHEDULES[args.beta_schedule] if args.dagger else None)
 
 
+def pretrain_modular_dagger(args, sort_ag, press_ag):
+    """--kind modular --pretrain rule_based --dagger: both agents cloned in ONE loop on the states the pair itself visits - a
+    labelled FusedModularRollout on envs of its own (one launch per collection: both agents act, the rule-based controller labels
+    every state in its two halves, and a beta-mixture of pair and expert steps), one ImitationLearner per agent on its
+    demo_view."""
+    env = M.BatchedSortingEnv(kind="mono", num_envs=args.envs, device=0, base_seed=args.seed + 2 * 10 ** 6,
+                              max_steps=args.max_steps, auto_reset=True)
+    col = M.FusedModularRollout(env, sort_ag, press_ag, args.steps, sort_seed=args.seed + 7, press_seed=args.seed + 8,
+                                expert_labels=True, beta=1.0, mix_seed=args.seed + 9, gamma=0.99)
+    ils = [M.ImitationLearner(pol, learning_rate=args.pretrain_lr, n_epochs=args.pretrain_epochs, batch_size=args.batch_size,
+                              seed=args.seed + i, shuffle=args.shuffle, weight_sync=args.weight_sync, arithmetic=args.arithmetic)
+           for i, pol in enumerate((sort_ag, press_ag))]
+    print(f"cloning the rule-based controller into both agents, jointly: {args.pretrain_iterations} iterations of {args.envs} envs x "
+          f"{args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}, DAgger with beta schedule "
+          f"'{args.beta_schedule}'")
+
+    def show(it, rec):
+        print(f"bc {it:3d} reward/step of the mixture {rec['reward']:+.4f} beta {rec['beta']:.3f} expert share {rec['expert_share']:.4f}")
+        for who in ("sort", "press"):
+            r = rec[who]
+            print(f"       {who:5s} loss {r['loss']:+.4f} bc {r['bc_loss']:.4f} vf {r['value_loss']:.4f} accuracy {r['accuracy']:.4f} "
+                  f"unusable {r['unusable']:.4f}")
+
+    return M.ModularTrainer(col, ils[0], ils[1]).learn(args.pretrain_iterations, callback=show,
+                                                       beta=BETA_SCHEDULES[args.beta_schedule])
+
+
 def train_modular(args):
-    """--kind modular: both agents in Env_3_Monolith, one FusedModularRollout and one PPOLearner each (ModularTrainer)."""
+    """--kind modular: both agents in Env_3_Monolith, one FusedModularRollout and one PPOLearner each (ModularTrainer).
+    --bc-coef: the rollout is labelled and each learner's loss keeps its agent's half of the rule-based label."""
     if args.time or args.resume or args.checkpoint:
         raise SystemExit("--kind modular takes neither --time nor --checkpoint / --resume")
-    if args.dagger:
-        raise SystemExit("--dagger serves a policy of the env's own dimensions: the modular views have no fused collector")
+    if args.dagger and not args.pretrain:
+        raise SystemExit("--dagger goes with --pretrain rule_based")
     sort_ag = M.MlpPolicy.random_init(13, 2, seed=args.seed, precision="f16x3")
     press_ag = M.MlpPolicy.random_init(16, 11, seed=args.seed + 1, precision="f16x3")
-    if args.pretrain:
+    if args.pretrain and args.dagger:
+        pretrain_modular_dagger(args, sort_ag, press_ag)
+    elif args.pretrain:
         pretrain(args, sort_ag, "mono", "sort", "the sorting agent")
         pretrain(args, press_ag, "mono", "press", "the pressing agent")
     env = M.BatchedSortingEnv(kind="mono", num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
-    col = M.FusedModularRollout(env, sort_ag, press_ag, args.steps, sort_seed=args.seed, press_seed=args.seed + 1)
+    col = M.FusedModularRollout(env, sort_ag, press_ag, args.steps, sort_seed=args.seed, press_seed=args.seed + 1,
+                                expert_labels=args.bc_coef is not None)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
     clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
+    bc_coef = (lambda p: args.bc_coef * p) if args.bc_coef is not None and args.bc_schedule == "linear" else args.bc_coef
     learners = [M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                              seed=args.seed + i, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
-                             arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf)
+                             arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf, bc_coef=bc_coef)
                 for i, pol in enumerate((sort_ag, press_ag))]
     print(f"Env_3_Monolith, sorting agent (13 -> 2) + pressing agent (16 -> 11), reward={args.reward}, {args.envs} envs x "
-          f"{args.steps} steps per iteration")
+          f"{args.steps} steps per iteration" + (f", bc_coef {args.bc_coef:g} {args.bc_schedule}" if args.bc_coef is not None else ""))
 
     def show(it, rec):
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} = sort {rec['reward_sort']:+.4f} + press {rec['reward_press']:+.4f}")
         for who in ("sort", "press"):
             r = rec[who]
             print(f"       {who:5s} loss {r['loss']:+.4f} pg {r['policy_loss']:+.4f} vf {r['value_loss']:.4f} "
-                  f"ent {-r['entropy_loss']:.3f} kl {r['approx_kl']:.4f} clip {r['clip_fraction']:.3f}")
+                  f"ent {-r['entropy_loss']:.3f} kl {r['approx_kl']:.4f} clip {r['clip_fraction']:.3f}"
+                  + (f" bc_loss {r['bc_loss']:.4f} bc_accuracy {r['bc_accuracy']:.4f}" if "bc_loss" in r else ""))
         if "episodes" in rec:
             print(f"       episodes {rec['episodes']:6d} ep_rew_mean {rec['ep_rew_mean']:+.3f} ep_len_mean {rec['ep_len_mean']:.1f}")
         if "eval_mean_reward" in rec:
@@ -429,8 +504,9 @@ def main():
     ap.add_argument("--bc-schedule", choices=("const", "linear"), default="const",
                     help="with --bc-coef: linear is X times progress_remaining, which reaches 0 in the last iteration")
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo"), default="all",
-                    help="with --time: run one block of the timings only")
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo", "modular_demo"), default="all",
+                    help="with --time: run one block of the timings only; 'all' is every block but modular_demo (four collectors "
+                         "at 262 144 envs, the multi-launch twin among them), which runs only when named, with any --kind")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
                     help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
     ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N",
@@ -440,13 +516,15 @@ def main():
                          "started with (a differing hyperparameter or env is refused by name)")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
-    if args.kind == "modular":
+    if args.kind == "modular" and not (args.time and args.time_section == "modular_demo"):
         return train_modular(args)
     if args.time:
         for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic),
                          ("bc", time_bc), ("demo", time_demo)):
             if args.time_section in ("all", name):
                 fn(args)
+        if args.time_section == "modular_demo":  # only by name: four collectors at 262 144 envs, the multi-launch twin among them
+            time_modular_demo(args)
         return
     D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
