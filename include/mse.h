@@ -177,6 +177,12 @@ int mse_sort_agent_obs(mse_env *env, float *obs13_out, void *stream);
 /* The same preview for a pressing agent: get_press_obs() after the coming step's flow update, which is what
  * Env_3_Monolith.step(mode='model') hands its press_agent (env_monolith.py:198-210).  obs16_out f32[N, 16]. */
 int mse_press_agent_obs(mse_env *env, float *obs16_out, void *stream);
+/* What Env_3_Monolith.step hands a stored mono_agent (env_monolith.py:144-150: get_obs() after the step's flow update =
+ * get_sort_obs() || get_press_obs()): obs29_out f32[N, 29], [:, :13] the bits of mse_sort_agent_obs and [:, 13:] the bits
+ * of mse_press_agent_obs of the same state, from one kernel over one flow-updated copy of the env.  Env_3 only
+ * (MSE_ERR_INVALID_ARGUMENT otherwise); general generator mode is served as the two previews serve it.  A preview: nothing
+ * is stored to the state. */
+int mse_mono_agent_obs(mse_env *env, float *obs29_out, void *stream);
 
 /* K fused steps with the on-device random policy (the reference's mode='random', env_monolith.py:152-164, with a
  * counter-based policy stream instead of the global np.random): uniform over the set bits of action_masks(), or -
@@ -520,6 +526,62 @@ int mse_rollout_demo_check(mse_env *env, mse_policy *actor, int32_t k_steps, uin
 /* Step 4 on the host, no device needed: out[j] = 1 iff the expert steps env index_offset + j at step counter t. */
 int mse_demo_who_steps_host(int64_t n, int64_t index_offset, uint64_t mix_seed, uint64_t t, uint32_t expert_threshold,
                             uint8_t *out);
+
+/* ---- The mono policy on the in-step view (env_monolith.py:144-150, a stored mono_agent): K steps of Env_3 in ONE launch
+ * with one 29 -> 22 network that is shown, like the modular agents, the observation AFTER the step's flow update, with the
+ * rule-based controller's label and mse_rollout_demo's mixture in the same launch.  Per step k and env i:
+ *   1. the preview: a copy of the env takes the step's flow update; observations[k,i,:] f32[K,N,29] is get_sort_obs() ||
+ *      get_press_obs() of the copy (the container purities come from the current state, as in mse_rollout_modular) - the
+ *      row mse_mono_agent_obs returns; action_masks[k,i,:] u8[K,N,22] is action_masks() of the state the decision is
+ *      taken in; episode_starts[k,i] is current_step == 0;
+ *   2. the policy: actions i32[K,N], log_probs f32[K,N], values f32[K,N] = policy(row) over the mask bits, drawn with the
+ *      word of (seed, index_offset + i, t + k); with MSE_PREVIEW_DETERMINISTIC the argmax;
+ *   3. the label: expert_actions i32[K,N], exactly what mse_rule_actions returns for the state; no stream is read;
+ *   4. who steps: mse_rollout_demo's step 4 with the word of (mix_seed, index_offset + i, t + k) against expert_threshold
+ *      in [0, 2^24] (mse_demo_who_steps_host on the host).  stepped_actions i32[K,N] is the flat action that was stepped,
+ *      expert_stepped u8[K,N] marks where it was the label; actions stays the policy's own draw whoever steps;
+ *   5. the step: as mse_step steps the action without MSE_STEP_UNMASKED (Path 2 predicts under the mask and applies the
+ *      action unsanitised, :148, :254-259), MSE_STEP_CHECK_OVERFLOW honoured, auto-reset on termination; rewards f32[K,N].
+ * After the last step: last_values f32[N] is the critic on the preview of the final state, last_dones u8[N]; the state is
+ * written back once and the policy step counter advances by K.  rng_sorting / rng_pressing are neither read nor written.
+ * Every pointer in the struct may be NULL.
+ * CONTRACTS: (a) bit-identical to K rounds of mse_mono_agent_obs, mse_action_masks, mse_rule_actions, mse_policy_forward
+ * (seed, t = the handle's policy step counter, index_offset = the env's), the who-steps rule on the host and mse_step - in
+ * every buffer, the final mse_get_state record and the step counter.  (b) With expert_threshold = 0 every non-label
+ * output, the state and the counter hold the same bits whether or not expert_actions / stepped_actions / expert_stepped
+ * are given.  (c) With expert_threshold = 2^24, rewards, stepped_actions and the final mse_get_state record equal those of
+ * mse_rollout with MSE_ROLLOUT_RULE_BASED on a twin handle.
+ * Shape: mse_rollout_policy's plain kernel with one network at every size - 32-env waves up to 256 x CUs envs in the f16x3
+ * form, 64-env waves beyond, the exact-f32 form in the 64-env shape.  There is no roles shape, whatever rollout_pipeline
+ * says (as mse_rollout_demo and mse_rollout_policy_labelled).
+ * Refusals, made before any device call, in this order.  MSE_ERR_INVALID_ARGUMENT: a NULL env, policy or out; a wrong
+ * struct_size; k_steps < 1; a handle that is not Env_3; policy dimensions other than 29 -> 22; a policy on another device;
+ * expert_threshold > 2^24; mix_seed == seed; a flag other than MSE_STEP_CHECK_OVERFLOW / MSE_PREVIEW_DETERMINISTIC
+ * (MSE_STEP_UNMASKED included); a handle without auto_reset = 1; a handle not yet reset; an attached trace; observations
+ * / action_masks not 16-byte aligned.  MSE_ERR_UNSUPPORTED_CONFIG: literal_choice; general generator mode; tables that
+ * do not fit the kernel's LDS image.  A refused call writes nothing and leaves the step counter unchanged. */
+#define MSE_PREVIEW_DETERMINISTIC 1024u
+typedef struct mse_preview_buffers {
+    uint32_t struct_size; /* = sizeof(mse_preview_buffers); ABI check */
+    uint32_t reserved0;
+    float   *observations;    /* f32[K,N,29] */
+    uint8_t *action_masks;    /* u8[K,N,22] */
+    uint8_t *episode_starts;  /* u8[K,N] */
+    int32_t *actions;         /* i32[K,N] */
+    float   *log_probs;       /* f32[K,N] */
+    float   *values;          /* f32[K,N] */
+    float   *rewards;         /* f32[K,N] */
+    int32_t *expert_actions;  /* i32[K,N] */
+    int32_t *stepped_actions; /* i32[K,N] */
+    uint8_t *expert_stepped;  /* u8[K,N] */
+    float   *last_values;     /* f32[N] */
+    uint8_t *last_dones;      /* u8[N] */
+} mse_preview_buffers;
+int mse_rollout_policy_preview(mse_env *env, mse_policy *policy, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                               uint32_t expert_threshold, uint32_t flags, const mse_preview_buffers *out, void *stream);
+/* The status mse_rollout_policy_preview would return for these arguments, its checks on `out` left out; no launch */
+int mse_rollout_policy_preview_check(mse_env *env, mse_policy *policy, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                                     uint32_t expert_threshold, uint32_t flags);
 
 /* Replaces the device image of `policy` with new weights (same flat order as mse_policy_create), repacked by the same
  * host routine, including the f16 range check: a policy in the "auto" form moves to f32 when a folded weight leaves

@@ -12,6 +12,7 @@ MSE_MODEL_NO_SORT_DRAW, MSE_MODEL_NO_PRESS_DRAW = 16, 32
 MSE_MODEL_PRESS_AGENT_MASKED = 64
 MSE_MODULAR_SORT_DETERMINISTIC, MSE_MODULAR_PRESS_DETERMINISTIC = 128, 256
 MSE_DEMO_ACTOR_DETERMINISTIC = 512
+MSE_PREVIEW_DETERMINISTIC = 1024
 MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
@@ -35,6 +36,7 @@ EXPORTS = [
     "mse_rollout_demo", "mse_rollout_demo_check", "mse_demo_who_steps_host",
     "mse_rollout_policy_labelled", "mse_rollout_policy_labelled_check",
     "mse_rollout_modular_labelled", "mse_rollout_modular_labelled_check",
+    "mse_mono_agent_obs", "mse_rollout_policy_preview", "mse_rollout_policy_preview_check",
 ]
 
 _other_libs: dict = {}
@@ -103,6 +105,16 @@ class MseModularLabelBuffers(C.Structure):
                [(name, C.c_void_p) for name in MODULAR_LABEL_BUFFER_NAMES]
 
 
+# the pointer members of struct mse_preview_buffers, in the header's order (= the keys of the preview collectors' buffer dicts)
+PREVIEW_BUFFER_NAMES = ("observations", "action_masks", "episode_starts", "actions", "log_probs", "values", "rewards",
+                        "expert_actions", "stepped_actions", "expert_stepped", "last_values", "last_dones")
+
+
+class MsePreviewBuffers(C.Structure):
+    """struct mse_preview_buffers (include/mse.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32)] + [(name, C.c_void_p) for name in PREVIEW_BUFFER_NAMES]
+
+
 _lib = None
 
 
@@ -146,6 +158,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_action_masks.argtypes = [vp, vp, vp]
     L.mse_sort_agent_obs.argtypes = [vp, vp, vp]
     L.mse_press_agent_obs.argtypes = [vp, vp, vp]
+    L.mse_mono_agent_obs.argtypes = [vp, vp, vp]
     L.mse_rollout.argtypes = [vp, i32, u64, vp, u32, vp, vp, vp, vp, vp, vp]
     L.mse_sample_actions.argtypes = [vp, u64, vp, vp]
     L.mse_rule_actions.argtypes = [vp, vp, vp]
@@ -179,6 +192,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_rollout_demo_check.argtypes = [vp, vp, i32, u64, u64, u32, u32]
     L.mse_rollout_policy_labelled.argtypes = [vp, vp, i32, u64, C.c_int, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mse_rollout_policy_labelled_check.argtypes = [vp, vp, i32, u64, C.c_int, vp, u32]
+    L.mse_rollout_policy_preview.argtypes = [vp, vp, i32, u64, u64, u32, u32, C.POINTER(MsePreviewBuffers), vp]
+    L.mse_rollout_policy_preview_check.argtypes = [vp, vp, i32, u64, u64, u32, u32]
     L.mse_demo_who_steps_host.argtypes = [i64, i64, u64, u64, u32, vp]
     L.mse_policy_set_weights.argtypes = [vp, C.POINTER(C.c_float)]
     L.mse_policy_set_weights_device.argtypes = [vp, vp, vp]

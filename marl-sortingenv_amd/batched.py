@@ -145,6 +145,14 @@ class BatchedSortingEnv:
             check(self.L.mse_press_agent_obs(self._h, _ptr(out), self._stream()))
         return out
 
+    def mono_agent_obs(self) -> torch.Tensor:
+        """f32[N, 29]: what Env_3_Monolith.step hands a stored mono_agent (env_monolith.py:144-150): get_obs() after the
+        coming step's flow update, `sort_agent_obs()` || `press_agent_obs()` on bits, in one launch.  Env_3 only."""
+        out = torch.empty((self.num_envs, 29), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.L.mse_mono_agent_obs(self._h, _ptr(out), self._stream()))
+        return out
+
     def sample_actions(self, policy_seed: int = 2024) -> torch.Tensor:
         out = torch.empty((self.num_envs,), dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):

@@ -49,8 +49,12 @@ def rollout_buffers(env, K: int, last: bool = False, names=POLICY_ROWS, dims=Non
     return {k: torch.empty(shapes.get(k, (K, n)), dtype=ROW_DTYPES[k], device=env.device) for k in names}
 
 
-def _check_policy_collector(env, policy, sort_policy) -> None:
+def _check_policy_collector(env, policy, sort_policy, view: str = "own") -> None:
     """What `PolicyRolloutCollector` and `FusedPolicyRollout` refuse at construction."""
+    if view not in ("own", "preview"):
+        raise ValueError(f"view must be 'own' or 'preview', not {view!r}")
+    if view == "preview" and env.kind != "mono":
+        raise ValueError("view='preview' is the mono policy's in-step view of Env_3 (env_monolith.py:144-150): it needs a 'mono' env")
     if policy.obs_dim != env.obs_dim or policy.n_actions != env.num_actions:
         raise ValueError("policy dimensions do not match the env")
     if sort_policy is not None and (env.kind != "press" or sort_policy.obs_dim != 13 or sort_policy.n_actions != 2):
@@ -92,16 +96,35 @@ class _CollectorState:
         self.env.load_state_dict(sd["env"])  # refreshes env.obs / env.mask, which a stepwise collect() starts from
 
 
-class PolicyRolloutCollector(_CollectorState):
+class _PolicyViewState(_CollectorState):
+    """The single-policy collectors' checkpoint surface: _CollectorState's, plus the key `view` when it is "preview" (a
+    checkpoint written before there was a view has none and is one of "own")."""
+
+    view = "own"
+
+    def _fingerprint(self) -> dict:
+        return {**super()._fingerprint(), **({"view": self.view} if self.view == "preview" else {})}
+
+    def check_state_dict(self, sd: dict) -> None:
+        saved = sd.get("view", "own")
+        if saved != self.view:
+            raise ValueError(f"{type(self).__name__}: view mismatch: the checkpoint has {saved!r}, this collector {self.view!r}")
+        super().check_state_dict(sd)
+
+
+class PolicyRolloutCollector(_PolicyViewState):
     KIND = "two_launch"
 
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, sort_policy: Optional[MlpPolicy] = None,
-                 seed: int = 2024, expert_labels: bool = False):
-        """expert_labels: `env.rule_actions()` of every state the rollout visits, taken before its step, is recorded in
+                 seed: int = 2024, expert_labels: bool = False, view: str = "own"):
+        """view="preview" (a "mono" env): the policy is shown `env.mono_agent_obs()`, the observation after the step's flow
+        update (Env_3_Monolith.step's stored mono_agent, env_monolith.py:144-150), and the bootstrap value comes from the
+        final `mono_agent_obs()`; the row names are the same.  `FusedPolicyRollout(view="preview")`'s twin.
+        expert_labels: `env.rule_actions()` of every state the rollout visits, taken before its step, is recorded in
         `buffers["expert_actions"]` (i32[K, N]): what the rule-based controller would do there, the labels of
         `PPOLearner(bc_coef=...)`.  The labels are outputs, not state: the checkpoint surface is the same."""
-        _check_policy_collector(env, policy, sort_policy)
-        self.env, self.policy, self.sort_policy = env, policy, sort_policy
+        _check_policy_collector(env, policy, sort_policy, view)
+        self.env, self.policy, self.sort_policy, self.view = env, policy, sort_policy, view
         self.n_steps, self.seed, self.t = int(n_steps), int(seed), 0
         self.expert_labels = bool(expert_labels)
         self.buffers = rollout_buffers(env, self.n_steps, names=POLICY_ROWS + (("expert_actions",) if self.expert_labels else ()))
@@ -133,8 +156,9 @@ class PolicyRolloutCollector(_CollectorState):
         """K steps; returns the buffers plus `last_values` f32[N] (the bootstrap value of the state after the last
         step) and `last_dones`, as SB3's compute_returns_and_advantage wants them."""
         env, b = self.env, self.buffers
+        preview = self.view == "preview"
         for k in range(self.n_steps):
-            obs, mask = env.obs, env.mask
+            obs, mask = (env.mono_agent_obs() if preview else env.obs), env.mask
             b["observations"][k].copy_(obs)
             b["action_masks"][k].copy_(mask)
             b["episode_starts"][k].copy_(self._last_done)
@@ -153,27 +177,32 @@ class PolicyRolloutCollector(_CollectorState):
             b["rewards"][k].copy_(rew)
             self._last_done.copy_(done)
             self.t += 1
-        last = self.policy.forward(env.obs, env.mask, seed=self.seed, t=self.t, deterministic=True,
+        last = self.policy.forward(env.mono_agent_obs() if preview else env.obs, env.mask, seed=self.seed, t=self.t, deterministic=True,
                                    index_offset=env.index_offset)
         return dict(b, last_values=last["value"], last_dones=self._last_done.clone())
 
 
-class FusedPolicyRollout(_CollectorState):
+class FusedPolicyRollout(_PolicyViewState):
     """K steps of policy forward + env transition per launch (`mse_rollout_policy`): MaskableRolloutBuffer-shaped
     device tensors [K, N, ...].  Env_2's sorting decisions: `sort_policy` (a 13 -> 2 MlpPolicy standing for the
     pre-trained sorting agent, evaluated inside the kernel), else `sort_mode` (a per-env tensor), else the reference's rule.
     Checkpoint: _CollectorState's alone - the kernel derives `episode_starts` from the env state and reads the step counter
-    from the handle (`sort_mode`, a constructor argument, is given again at construction like the policies)."""
+    from the handle (`sort_mode`, a constructor argument, is given again at construction like the policies).
+    view="preview" (a "mono" env): `collect()` is one `mse_rollout_policy_preview` launch at threshold 0 - the policy is shown
+    the observation after the step's flow update, as the modular agents are; with expert_labels the same launch fills
+    `expert_actions`.  `PolicyRolloutCollector(view="preview")`'s bits under the same row names."""
 
     KIND = "fused"
 
     def __init__(self, env: BatchedSortingEnv, policy: MlpPolicy, n_steps: int, seed: int = 2024,
-                 sort_mode: Optional[torch.Tensor] = None, sort_policy: Optional[MlpPolicy] = None, expert_labels: bool = False):
+                 sort_mode: Optional[torch.Tensor] = None, sort_policy: Optional[MlpPolicy] = None, expert_labels: bool = False,
+                 view: str = "own"):
         """expert_labels: `collect()` is one `mse_rollout_policy_labelled` launch and the buffers gain `expert_actions`
         (i32[K, N]): the rule-based controller's action in every recorded state, `PolicyRolloutCollector(expert_labels=True)`'s
         bits.  The plain kernel runs at every size (no roles shape) and there is no in-loop sorting policy.  The labels are
         outputs, not state: the checkpoint surface is the same."""
-        _check_policy_collector(env, policy, sort_policy)
+        _check_policy_collector(env, policy, sort_policy, view)
+        self.view = view
         if expert_labels and sort_policy is not None:
             raise ValueError("the one-launch labelled rollout has no in-loop sorting policy: collect with "
                              "PolicyRolloutCollector(sort_policy=..., expert_labels=True)")
@@ -201,6 +230,19 @@ class FusedPolicyRollout(_CollectorState):
         def ptr(x):
             return None if x is None else C.c_void_p(x.data_ptr())
 
+        if self.view == "preview":
+            from ._lib import MSE_PREVIEW_DETERMINISTIC, PREVIEW_BUFFER_NAMES, MsePreviewBuffers
+
+            if not use_action_masking:
+                raise ValueError("view='preview' predicts under the mask and applies the action unsanitised "
+                                 "(env_monolith.py:148, :254-259): there is no use_action_masking=False")
+            out = MsePreviewBuffers(C.sizeof(MsePreviewBuffers), 0,
+                                    *(b[name].data_ptr() if name in b else None for name in PREVIEW_BUFFER_NAMES))
+            pflags = (MSE_STEP_CHECK_OVERFLOW if check_overflow else 0) | (MSE_PREVIEW_DETERMINISTIC if deterministic else 0)
+            with torch.cuda.device(env.device):  # threshold 0: the policy always steps; the mixture seed selects nothing
+                check(env.L.mse_rollout_policy_preview(env._h, self.policy._h, K, self.seed, self.seed + 1, 0, pflags,
+                                                       C.byref(out), env._stream()))
+            return b
         if self.expert_labels:
             with torch.cuda.device(env.device):
                 check(env.L.mse_rollout_policy_labelled(env._h, self.policy._h, K, self.seed, 1 if deterministic else 0,

@@ -1885,6 +1885,150 @@ __global__ __launch_bounds__(512) void k_rollout_demo(Params P, uint4 *__restric
     }
 }
 
+// ==========================================================================================
+// Preview rollout: the mono policy on the in-step view (env_monolith.py:144-150; DESIGN.md "Preview rollout")
+//
+// k_rollout_demo's frame with an actor - one wave owns 32 TILES envs for the whole launch, one weight image and the tables
+// in LDS, the env state in registers, the same mirror lanes, phase priorities and row staging - on Env_3, with the row
+// taken as k_rollout_modular takes its two: a copy of the env takes the step's flow update and get_sort_obs() ||
+// get_press_obs() of the copy (env_obs<3> with the current state's container purities) is what the network sees; the mask
+// is action_masks() of the state itself.  The policy's action, log-probability and value are recorded whoever steps; the
+// label and the who-steps decision are k_rollout_demo's.  One entry: without label pointers and at threshold 0 the same
+// instructions run, so the other outputs cannot depend on them.
+// LDS: [weights][tables][per wave: obs tile (the mask tile reuses it) | bale ledger]
+// ==========================================================================================
+template <bool NOISE, int TILES, bool F16X3>
+__global__ __launch_bounds__(512) void k_rollout_policy_preview(Params P, uint4 *__restrict__ planes,
+                                                                const uint32_t *__restrict__ table_image,
+                                                                const float *__restrict__ weight_blob, int k_steps,
+                                                                uint64_t seed, uint64_t mix_seed, uint32_t expert_threshold,
+                                                                uint64_t policy_t0, uint32_t flags,
+                                                                const mse_preview_buffers out)
+{
+    using L = PolLayout<3, TILES>;
+    constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
+    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
+    float *lw = reinterpret_cast<float *>(lds);
+    constexpr int kWeightBytes = L::weight_bytes;
+    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
+    const int table_bytes = P.table_words * 4;
+    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
+    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
+    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
+    long long rem = P.n - wave_row0;
+    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
+    const bool wave_active = n_valid > 0;
+    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
+    // the batch's end its last env; mirrors store nothing
+    const int src_lane = TILES == 1 ? (lane & 31) : lane;
+    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
+    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
+
+    msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
+    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
+        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
+    const BaleRef bales{lbale + src_lane, ENVS};
+    if (P.track_bales && wave_active) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
+    }
+    Env e;
+    load_env<3, NOISE>(e, planes, P, i);
+    __syncthreads();
+    if (!wave_active) return;
+    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
+    const Tables tb = tables_at(ltab, P);
+    const msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
+    const bool deterministic = (flags & MSE_PREVIEW_DETERMINISTIC) != 0;
+    const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // the action is applied unsanitised: the masked step
+    int kcur[4]; // container purities of the current state (the sorting half of the view needs them)
+    container_purity_k(e, kcur);
+    // the policy's stream keys of the env(s) this lane serves as an MFMA column (k_rollout_policy); the mixture's key is
+    // the lane's own env's
+    const int h = lane >> 5, col = lane & 31;
+    const uint32_t key0 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + col));
+    const uint32_t key1 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
+    const uint32_t mix_key = mse_policy_key(mix_seed, (uint64_t)(P.index_offset + i));
+
+    const uint32_t lrow_obs = lds_row_address(reinterpret_cast<float *>(lwave) + src_lane * D);
+    const uint32_t lrow_mask = lds_row_address(lwave + src_lane * A);
+    int last_done = 0;
+    for (int s = 0; s < k_steps; ++s) {
+        __builtin_amdgcn_s_setprio(TILES == 2 ? 3 : 0); // policy phase (k_rollout_policy)
+        const long long srow = (long long)s * P.n + wave_row0;
+        const long long at = (long long)s * P.n + i;
+        const uint64_t t = policy_t0 + (uint64_t)s;
+        // ---- the view: get_obs() one flow update ahead (a copy takes the update; env_step will take the same one)
+        float o[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) o[j] = 0.0f;
+        {
+            Env ec = e;
+            update_environment<false>(ec, P);
+            env_obs<3>(ec, P, tb, kcur, o);
+        }
+        // action_masks() of the state the decision is taken in (the flow update does not change it)
+        const uint32_t mbits = action_mask_bits<3>(e, P);
+        if (out.observations != nullptr) wave_store_rows_f32<D, ENVS>(reinterpret_cast<float *>(lwave), lrow_obs, o, out.observations + srow * D, n_valid, lane);
+        if (out.action_masks != nullptr) wave_store_rows_mask<A, ENVS>(lwave, lrow_mask, mbits, out.action_masks + srow * A, n_valid, lane);
+        if (live && out.episode_starts != nullptr)
+            __builtin_nontemporal_store((uint8_t)(e.step == 0 ? 1 : 0), &out.episode_starts[at]);
+        // ---- the policy on that row, over the mask bits
+        float x[2][16];
+        operands_of(o, x);
+        uint32_t mb0, mb1;
+        msep::both_halves_u32(mbits, mb0, mb1);
+        const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
+        const uint32_t words[2] = {mse_policy_word(key0, t), mse_policy_word(key1, t)};
+        msep::TileOut p[2];
+        msep::policy_tiles<NR, F16X3, TILES>(wl, lane, x, A, legal, deterministic, words, nullptr, p);
+        const int own = tile_pick<TILES>(h, p[0].action, p[1].action);
+        const float logp = tile_pick<TILES>(h, p[0].logp, p[1].logp), value = tile_pick<TILES>(h, p[0].value, p[1].value);
+        __builtin_amdgcn_s_setprio(TILES == 2 ? 0 : 3);
+        // ---- the expert: what mse_rule_actions returns for the state (k_rollout_demo's label; no stream is read), and
+        // who steps (mse_demo_mix.h)
+        const int label = rule_based_action<3>(e, Stage<false>::rule_mode(e.st_in, tb));
+        const bool expert = mse_demo_expert_steps(mix_key, t, expert_threshold);
+        const int a = expert ? label : own;
+        // ---- the transition under that action, auto-reset on termination (the observation it returns is not the view)
+        float o_after[32];
+        StepResult r = env_step<3, NOISE, false>(e, P, tb, a, -1, step_flags, bales, kcur, o_after);
+        if (__builtin_expect(r.done != 0, 0)) auto_reset_env(e, P, tb, bales, kcur);
+        last_done = r.done;
+        if (live) {
+            if (out.actions != nullptr) __builtin_nontemporal_store(own, &out.actions[at]);
+            if (out.log_probs != nullptr) __builtin_nontemporal_store(logp, &out.log_probs[at]);
+            if (out.values != nullptr) __builtin_nontemporal_store(value, &out.values[at]);
+            if (out.rewards != nullptr) __builtin_nontemporal_store((float)r.reward, &out.rewards[at]);
+            if (out.expert_actions != nullptr) __builtin_nontemporal_store(label, &out.expert_actions[at]);
+            if (out.stepped_actions != nullptr) __builtin_nontemporal_store(a, &out.stepped_actions[at]);
+            if (out.expert_stepped != nullptr) __builtin_nontemporal_store((uint8_t)(expert ? 1 : 0), &out.expert_stepped[at]);
+        }
+    }
+    // the bootstrap value of the state the rollout ends in: the critic alone on its preview of that state
+    if (out.last_values != nullptr) {
+        float o[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) o[j] = 0.0f;
+        {
+            Env ec = e;
+            update_environment<false>(ec, P);
+            env_obs<3>(ec, P, tb, kcur, o);
+        }
+        float x[2][16], v[2];
+        operands_of(o, x);
+        msep::value_tiles<F16X3, TILES>(wl, lane, x, v);
+        if (live) out.last_values[i] = tile_pick<TILES>(h, v[0], v[1]);
+    }
+    if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
+    if (live) store_env<3, NOISE>(e, planes, P, i, false);
+    if (P.track_bales && live) {
+#pragma unroll
+        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
+    }
+}
+
 template <int KIND>
 __global__ __launch_bounds__(kBlock) void k_reset(Params P, uint4 *__restrict__ planes,
                                                   const uint32_t *__restrict__ table_image,
@@ -2010,6 +2154,32 @@ __global__ __launch_bounds__(kBlock) void k_press_agent_obs(Params P, const uint
     }
 #pragma unroll
     for (int j = 0; j < 16; ++j) obs_out[i * 16 + j] = o[j];
+}
+
+// Both previews in one row: what Env_3_Monolith.step hands a stored mono_agent (env_monolith.py:144-150: get_obs() after
+// the flow update = get_sort_obs() || get_press_obs()), from one flow-updated copy
+__global__ __launch_bounds__(kBlock) void k_mono_agent_obs(Params P, const uint4 *__restrict__ planes,
+                                                           const uint32_t *__restrict__ table_image,
+                                                           float *__restrict__ obs_out)
+{
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= P.n) return;
+    const Tables tb = tables_at(table_image, P);
+    Env e;
+    load_env<2, false>(e, planes, P, i);
+    int k[4];
+    container_purity_k(e, k);
+    float o[29];
+    if (P.gen_mode) {
+        load_gen(e, planes, P, i);
+        update_environment<true>(e, P);
+        env_obs<3, true>(e, P, tb, k, o);
+    } else {
+        update_environment<false>(e, P);
+        env_obs<3, false>(e, P, tb, k, o);
+    }
+#pragma unroll
+    for (int j = 0; j < 29; ++j) obs_out[i * 29 + j] = o[j];
 }
 
 template <int KIND>
@@ -2495,6 +2665,27 @@ static void launch_rollout_demo(mse_env *h, const mse_policy *actor, hipStream_t
                                actor != nullptr ? actor->blob : nullptr, k_steps, seed, mix_seed, expert_threshold,
                                h->policy_t, flags, out);
     }, h->noise_on, plan.tiles == 1, actor == nullptr || actor->use_f16(), actor != nullptr);
+}
+
+// mse_rollout_policy_preview's shape: k_rollout_policy's plain one with one network at every size (no roles shape, as
+// mse_rollout_demo)
+static PolicyPlan plan_rollout_policy_preview(const mse_env *h, const mse_policy *pol)
+{
+    return plan_policy_plain(h->P.n, h->cus, pol->use_f16(), 1, policy_lds<3>(h->P));
+}
+
+// the caller has checked that the plan fits (rollout_policy_preview_checks)
+static void launch_rollout_policy_preview(mse_env *h, const mse_policy *pol, hipStream_t s, int k_steps, uint64_t seed,
+                                          uint64_t mix_seed, uint32_t expert_threshold, uint32_t flags,
+                                          const mse_preview_buffers &out)
+{
+    const PolicyPlan plan = plan_rollout_policy_preview(h, pol);
+    with_flags([&](auto NOISE, auto ONE_TILE, auto F16) {
+        if constexpr (F16 || !ONE_TILE) // the forms the plan gives: exact f32 in two tiles only
+            hipLaunchKernelGGL((k_rollout_policy_preview<NOISE, ONE_TILE ? 1 : 2, F16>), dim3((unsigned)plan.workgroups),
+                               dim3((unsigned)(64 * plan.n_waves)), plan.lds_bytes, s, h->P, h->planes, h->tables, pol->blob,
+                               k_steps, seed, mix_seed, expert_threshold, h->policy_t, flags, out);
+    }, h->noise_on, plan.tiles == 1, pol->use_f16());
 }
 
 // the checks the three rollout entry points share (`fn` names the entry point in the messages)
@@ -3012,6 +3203,58 @@ int mse_rollout_demo(mse_env *h, mse_policy *actor, int32_t k_steps, uint64_t se
     return MSE_OK;
 }
 
+// everything mse_rollout_policy_preview refuses, in the order include/mse.h gives; `out` is looked at when `with_out` is set
+// (mse_rollout_policy_preview_check has none)
+static int rollout_policy_preview_checks(mse_env *h, const mse_policy *pol, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                                         uint32_t expert_threshold, uint32_t flags, const mse_preview_buffers *out, bool with_out)
+{
+    if (!h || !pol || (with_out && !out)) return fail(MSE_ERR_INVALID_ARGUMENT, "env / policy / out is NULL");
+    if (with_out && out->struct_size != sizeof(mse_preview_buffers))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_preview_buffers.struct_size mismatch (header/library version skew)");
+    if (k_steps < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "k_steps must be >= 1");
+    if (h->P.env_kind != MSE_ENV_MONO)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "the preview rollout exists on Env_3_Monolith only (env_monolith.py:144-150)");
+    if (pol->d_in != 29 || pol->n_act != 22) return fail(MSE_ERR_INVALID_ARGUMENT, "the mono policy must be a 29 -> 22 policy");
+    if (pol->device != h->device) return fail(MSE_ERR_INVALID_ARGUMENT, "policy and env live on different devices");
+    if (expert_threshold > MSE_DEMO_THRESHOLD_ONE)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "expert_threshold must be in [0, 2^24]");
+    if (mix_seed == seed)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mix_seed == seed: who steps and what the policy draws would come from one word");
+    if (flags & ~(MSE_STEP_CHECK_OVERFLOW | MSE_PREVIEW_DETERMINISTIC))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "unknown rollout flag (the policy predicts under the mask and its action is applied unsanitised: no MSE_STEP_UNMASKED)");
+    if (!h->P.auto_reset) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_policy_preview needs auto_reset=1");
+    if (!h->seeded) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_rollout_policy_preview before mse_reset(seeds)");
+    if (h->trace_rec != nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "a trace is attached (mse_trace_begin): only mse_step records, end it first");
+    if (with_out && (!aligned16(out->observations) || !aligned16(out->action_masks)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "observations / action_masks must be 16-byte aligned");
+    if (h->literal)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_policy_preview serves the integer draw path (literal_choice: alternate "
+                                                "mse_mono_agent_obs, mse_policy_forward and mse_step)");
+    if (h->P.gen_mode)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_rollout_policy_preview serves a remainder-free batch (general generator mode: "
+                                                "alternate mse_mono_agent_obs, mse_policy_forward and mse_step)");
+    if (plan_rollout_policy_preview(h, pol).status != MSE_OK)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "the preview rollout kernel's LDS image does not fit this config's tables");
+    return MSE_OK;
+}
+
+int mse_rollout_policy_preview_check(mse_env *h, mse_policy *pol, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                                     uint32_t expert_threshold, uint32_t flags)
+{
+    return rollout_policy_preview_checks(h, pol, k_steps, seed, mix_seed, expert_threshold, flags, nullptr, false);
+}
+
+int mse_rollout_policy_preview(mse_env *h, mse_policy *pol, int32_t k_steps, uint64_t seed, uint64_t mix_seed,
+                               uint32_t expert_threshold, uint32_t flags, const mse_preview_buffers *out, void *stream)
+{
+    if (const int rc = rollout_policy_preview_checks(h, pol, k_steps, seed, mix_seed, expert_threshold, flags, out, true)) return rc;
+    launch_rollout_policy_preview(h, pol, static_cast<hipStream_t>(stream), k_steps, seed, mix_seed, expert_threshold, flags, *out);
+    MSE_CHECK_LAUNCH();
+    h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
 int mse_demo_who_steps_host(int64_t n, int64_t index_offset, uint64_t mix_seed, uint64_t t, uint32_t expert_threshold,
                             uint8_t *out)
 {
@@ -3109,6 +3352,18 @@ int mse_press_agent_obs(mse_env *h, float *obs16_out, void *stream)
     if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_press_agent_obs before the first seeded mse_reset");
     hipLaunchKernelGGL(k_press_agent_obs, grid_of(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->P, h->planes,
                        h->tables, obs16_out);
+    MSE_CHECK_LAUNCH();
+    return MSE_OK;
+}
+
+int mse_mono_agent_obs(mse_env *h, float *obs29_out, void *stream)
+{
+    if (!h || !obs29_out) return fail(MSE_ERR_INVALID_ARGUMENT, "env/obs29_out is NULL");
+    if (h->P.env_kind != MSE_ENV_MONO)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_mono_agent_obs: a mono_agent exists on Env_3_Monolith only (env_monolith.py:144)");
+    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_mono_agent_obs before the first seeded mse_reset");
+    hipLaunchKernelGGL(k_mono_agent_obs, grid_of(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->P, h->planes,
+                       h->tables, obs29_out);
     MSE_CHECK_LAUNCH();
     return MSE_OK;
 }

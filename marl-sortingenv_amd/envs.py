@@ -365,9 +365,9 @@ class Env_3_Monolith(_SingleEnv):
             action = int(action)
         elif self.mono_agent is not None:                                   # env_monolith.py:144-150
             # the agent sees get_obs() AFTER this step's flow update (:113-114, 145 -> :98-104): the two previews of
-            # the coming step, concatenated; the mask does not depend on the flow update
-            obs = np.concatenate([self._batched.sort_agent_obs()[0].cpu().numpy(),
-                                  self._batched.press_agent_obs()[0].cpu().numpy()])
+            # the coming step, concatenated (mse_mono_agent_obs: one launch, one copy); the mask does not depend on the
+            # flow update
+            obs = self._batched.mono_agent_obs()[0].cpu().numpy()
             action, _ = self.mono_agent.predict(obs, deterministic=True, action_masks=self.action_masks())
             action, masked = int(action), True                              # applied without sanitising (:254-257)
         elif mode == "random":                                              # env_monolith.py:152-164

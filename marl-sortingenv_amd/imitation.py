@@ -18,14 +18,15 @@ from typing import Optional
 
 import torch
 
-from ._lib import (DEMO_BUFFER_NAMES, MSE_DEMO_ACTOR_DETERMINISTIC, MSE_STEP_CHECK_OVERFLOW, MseDemoBuffers, check)
+from ._lib import (DEMO_BUFFER_NAMES, MSE_DEMO_ACTOR_DETERMINISTIC, MSE_PREVIEW_DETERMINISTIC, MSE_STEP_CHECK_OVERFLOW,
+                   PREVIEW_BUFFER_NAMES, MseDemoBuffers, MsePreviewBuffers, check)
 from .batched import BatchedSortingEnv
 from .collector import rollout_buffers
 from .learner import PPOLearner, _ptr, _stream, training_loop
 from .policy import MlpPolicy
 
 BC_STAT_NAMES = ("loss", "bc_loss", "value_loss", "entropy_loss", "accuracy", "unusable", "_", "_")
-AGENT_DIMS = {"sort": (13, 2), "press": (16, 11)}
+AGENT_DIMS = {"sort": (13, 2), "press": (16, 11), "preview": (29, 22)}
 DEMO_ROWS = ("observations", "action_masks", "actions", "stepped_actions", "rewards", "episode_starts", "returns")
 FUSED_DEMO_ROWS = ("observations", "action_masks", "actions", "stepped_actions", "expert_stepped", "rewards", "episode_starts",
                    "last_dones", "returns")
@@ -37,8 +38,9 @@ class DemonstrationCollector:
 
     1. the observation: `env.obs` / `env.mask` for agent="own" (a policy of the env's own dimensions); on a "mono" env
        `sort_agent_obs()` and no mask for agent="sort" (13 -> 2), `press_agent_obs()` and `mask[:, :11]` for
-       agent="press" (16 -> 11);
-    2. the label: `env.rule_actions()` - the flat action a for "own", a // 11 for "sort", a % 11 for "press";
+       agent="press" (16 -> 11), `mono_agent_obs()` - the mono policy's in-step view, both previews in one row - and
+       the full `env.mask` for agent="preview" (29 -> 22);
+    2. the label: `env.rule_actions()` - the flat action a for "own" and "preview", a // 11 for "sort", a % 11 for "press";
     3. the step: with actor=None the expert's action is stepped.  With an `MlpPolicy` as `actor` that policy's action
        (sampled with `seed`, or its argmax with deterministic_actor=True) is stepped and the expert's action stays the
        label - on-policy relabelling; for "sort" / "press" the other half of the flat action stays the expert's.
@@ -51,10 +53,10 @@ class DemonstrationCollector:
 
     def __init__(self, env: BatchedSortingEnv, n_steps: int, agent: str = "own", actor: Optional[MlpPolicy] = None,
                  deterministic_actor: bool = False, gamma: float = 0.99, seed: int = 2024):
-        if agent not in ("own", "sort", "press"):
-            raise ValueError(f"agent must be 'own', 'sort' or 'press', not {agent!r}")
+        if agent not in ("own", "sort", "press", "preview"):
+            raise ValueError(f"agent must be 'own', 'sort', 'press' or 'preview', not {agent!r}")
         if agent != "own" and env.kind != "mono":
-            raise ValueError(f"agent={agent!r} is a modular agent's view of Env_3: it needs a 'mono' env")
+            raise ValueError(f"agent={agent!r} is an in-step view of Env_3: it needs a 'mono' env")
         if not env.auto_reset:
             raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
         self.obs_dim, self.n_actions = (env.obs_dim, env.num_actions) if agent == "own" else AGENT_DIMS[agent]
@@ -78,6 +80,8 @@ class DemonstrationCollector:
             return env.obs, env.mask
         if self.agent == "sort":
             return env.sort_agent_obs(), None
+        if self.agent == "preview":
+            return env.mono_agent_obs(), env.mask
         return env.press_agent_obs(), env.mask[:, :11]  # press_action_masks()
 
     def collect(self) -> dict:
@@ -89,7 +93,7 @@ class DemonstrationCollector:
                 b["action_masks"][k].copy_(mask)
             b["episode_starts"][k].copy_(self._last_done)
             rule = env.rule_actions()
-            label = rule if self.agent == "own" else (rule // 11 if self.agent == "sort" else rule % 11)
+            label = rule if self.agent in ("own", "preview") else (rule // 11 if self.agent == "sort" else rule % 11)
             b["actions"][k].copy_(label)
             if self.actor is None:
                 stepped = rule
@@ -97,7 +101,7 @@ class DemonstrationCollector:
                 self._out = self.actor.forward(obs, mask, seed=self.seed, t=self.t, deterministic=self.deterministic_actor,
                                                index_offset=env.index_offset, out=self._out)
                 a = self._out["action"]
-                stepped = a if self.agent == "own" else (11 * a + rule % 11 if self.agent == "sort" else rule - rule % 11 + a)
+                stepped = a if self.agent in ("own", "preview") else (11 * a + rule % 11 if self.agent == "sort" else rule - rule % 11 + a)
             b["stepped_actions"][k].copy_(stepped)
             _, rew, done, _ = env.step(b["stepped_actions"][k])
             b["rewards"][k].copy_(rew)
@@ -132,18 +136,29 @@ class FusedDemonstrationRollout:
     `collect()` is that launch plus the one `mse_gae` launch for `returns`, and returns `DemonstrationCollector`'s dict
     (`observations`, `action_masks`, `actions` = the labels, `stepped_actions`, `rewards`, `episode_starts`,
     `last_dones`, `returns`) plus `expert_stepped` u8[K, N]; the buffers are allocated once.  The modular views ("sort" /
-    "press" on Env_3) have a launch of their own: `FusedModularRollout(expert_labels=True).demo_view(who)`.  The env's own obs / mask tensors are not refreshed."""
+    "press" on Env_3) have a launch of their own: `FusedModularRollout(expert_labels=True).demo_view(who)`.  The env's own obs / mask tensors are not refreshed.
+
+    agent="preview" (a "mono" env, a 29 -> 22 actor): `DemonstrationCollector(agent="preview")` in one launch
+    (`mse_rollout_policy_preview`) - the student is shown `mono_agent_obs()`, the observation after the step's flow update.
+    That kernel always carries a network: actor=None is refused."""
 
     def __init__(self, env: BatchedSortingEnv, n_steps: int, actor: Optional[MlpPolicy] = None,
                  deterministic_actor: bool = False, beta: Optional[float] = None, gamma: float = 0.99, seed: int = 2024,
-                 mix_seed: Optional[int] = None, check_overflow: bool = False):
+                 mix_seed: Optional[int] = None, check_overflow: bool = False, agent: str = "own"):
+        if agent not in ("own", "preview"):
+            raise ValueError(f"agent must be 'own' or 'preview', not {agent!r}")
+        if agent == "preview" and env.kind != "mono":
+            raise ValueError("agent='preview' is the mono policy's in-step view of Env_3: it needs a 'mono' env")
+        if agent == "preview" and actor is None:
+            raise ValueError("agent='preview' with actor=None: mse_rollout_policy_preview always carries a network; collect the "
+                             "expert's own demonstrations with DemonstrationCollector(agent='preview')")
         if not env.auto_reset:
             raise ValueError("collection needs auto_reset=True (episodes end inside a rollout)")
         if int(n_steps) < 1:
             raise ValueError("n_steps must be >= 1")
         if actor is not None and (actor.obs_dim != env.obs_dim or actor.n_actions != env.num_actions):
             raise ValueError(f"the actor must be a {env.obs_dim} -> {env.num_actions} policy")
-        self.env, self.actor = env, actor
+        self.env, self.actor, self.agent = env, actor, agent
         self.deterministic_actor, self.gamma, self.check_overflow = bool(deterministic_actor), float(gamma), bool(check_overflow)
         self.n_steps, self.seed = int(n_steps), int(seed)
         self.mix_seed = self.seed + 1 if mix_seed is None else int(mix_seed)
@@ -155,8 +170,13 @@ class FusedDemonstrationRollout:
         self._zeros = torch.zeros((K + 1, n), dtype=torch.float32, device=dev)  # mse_gae's values and last_values
         self._adv = torch.empty((K, n), dtype=torch.float32, device=dev)
         b = self.buffers
-        self._out = MseDemoBuffers(C.sizeof(MseDemoBuffers), 0, *(b["actions" if name == "labels" else name].data_ptr()
-                                                                   for name in DEMO_BUFFER_NAMES))
+        if agent == "preview":  # the labels go to `actions`; the student's own draws, log-probabilities and values are not kept
+            rows = {"expert_actions": b["actions"], **{k: b[k] for k in PREVIEW_BUFFER_NAMES if k in b and k != "actions"}}
+            self._out = MsePreviewBuffers(C.sizeof(MsePreviewBuffers), 0,
+                                          *(rows[name].data_ptr() if name in rows else None for name in PREVIEW_BUFFER_NAMES))
+        else:
+            self._out = MseDemoBuffers(C.sizeof(MseDemoBuffers), 0, *(b["actions" if name == "labels" else name].data_ptr()
+                                                                       for name in DEMO_BUFFER_NAMES))
 
     @property
     def beta(self) -> float:
@@ -171,11 +191,16 @@ class FusedDemonstrationRollout:
 
     def collect(self) -> dict:
         env, b, K = self.env, self.buffers, self.n_steps
+        preview = self.agent == "preview"
         flags = (MSE_STEP_CHECK_OVERFLOW if self.check_overflow else 0) | \
-                (MSE_DEMO_ACTOR_DETERMINISTIC if self.deterministic_actor else 0)
+                ((MSE_PREVIEW_DETERMINISTIC if preview else MSE_DEMO_ACTOR_DETERMINISTIC) if self.deterministic_actor else 0)
         with torch.cuda.device(env.device):
-            check(env.L.mse_rollout_demo(env._h, None if self.actor is None else self.actor._h, K, self.seed, self.mix_seed,
-                                         self._threshold, flags, C.byref(self._out), env._stream()))
+            if preview:
+                check(env.L.mse_rollout_policy_preview(env._h, self.actor._h, K, self.seed, self.mix_seed, self._threshold,
+                                                       flags, C.byref(self._out), env._stream()))
+            else:
+                check(env.L.mse_rollout_demo(env._h, None if self.actor is None else self.actor._h, K, self.seed, self.mix_seed,
+                                             self._threshold, flags, C.byref(self._out), env._stream()))
             check(env.L.mse_gae(K, env.num_envs, _ptr(b["rewards"]), _ptr(self._zeros), _ptr(b["episode_starts"]),
                                 _ptr(self._zeros[K]), _ptr(b["last_dones"]), self.gamma, 1.0, _ptr(self._adv), _ptr(b["returns"]),
                                 env._stream()))

@@ -4,7 +4,7 @@
           marl-sortingenv_amd/csrc/mse_lib.hip -o /tmp/mse_lib.s
     python tools/check_step_loops.py /tmp/mse_lib.s
 
-For every depth-1 loop of k_rollout / k_rollout_ring / k_rollout_policy / k_rollout_policy_labelled / k_rollout_model / k_rollout_modular / k_rollout_modular_labelled / k_rollout_demo it counts global / scratch loads, vmcnt waits and
+For every depth-1 loop of k_rollout / k_rollout_ring / k_rollout_policy / k_rollout_policy_labelled / k_rollout_model / k_rollout_modular / k_rollout_modular_labelled / k_rollout_demo / k_rollout_policy_preview it counts global / scratch loads, vmcnt waits and
 scalar loads between the loop header and the function's epilogue.  The step loops must hold no global or scratch load
 and no vmcnt wait: such a wait also covers the wave's own output stores (the one global load round 2
 found there - a per-lane selection among kernel arguments - cost 3 %).  Exit status 1 if one is found."""
@@ -14,7 +14,7 @@ import sys
 path = sys.argv[1]
 lines = open(path).read().split("\n")
 KERNELS = ["_Z9k_rolloutILi", "_Z14k_rollout_ringILi", "_Z16k_rollout_policyILi", "_Z25k_rollout_policy_labelledILi", "_Z15k_rollout_modelILb",
-           "_Z17k_rollout_modularILb", "_Z26k_rollout_modular_labelledILb", "_Z14k_rollout_demoILi"]
+           "_Z17k_rollout_modularILb", "_Z26k_rollout_modular_labelledILb", "_Z14k_rollout_demoILi", "_Z24k_rollout_policy_previewILb"]
 bad = 0
 i = 0
 while i < len(lines):

@@ -51,6 +51,13 @@
     python tools/train_ppo.py --time --time-section modular_demo  # the labelled modular launch beside the plain one and the twin;
                                                           # any --kind, and only when named: --time alone (section
                                                           # 'all') does not run it
+    python tools/train_ppo.py --kind mono --view preview --pretrain rule_based --dagger --eval-every 10
+                                                          # the mono policy on the in-step view: it is shown the observation
+                                                          # after the step's flow update, as the modular agents are
+                                                          # (mse_rollout_policy_preview: cloning, DAgger, --bc-coef and the
+                                                          # evaluation all on that view)
+    python tools/train_ppo.py --time --time-section preview  # the preview launch (plain, with labels, with the mixture) beside
+                                                          # the plain policy kernel at 65 536 and 262 144 envs; only when named
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -342,6 +349,40 @@ def time_modular_demo(args):
             f"{name} " + " / ".join(f"{t:.3f}" for t in ts) + f" ms ({n * K / min(ts) / 1e3:.1f} M steps/s)" for name, ts in times.items()))
 
 
+def time_preview(args):
+    """`collect()` of `FusedPolicyRollout(view="preview")` (threshold 0, no labels) beside `FusedPolicyRollout` held to the plain
+    kernel (rollout_pipeline = 2: the same loop without the flow update on a copy and the second observation build), then the
+    preview launch with labels and with the beta = 0.5 mixture, Env_3, K = 16, f16x3, noise 0, at 65 536 and 262 144 envs: HIP
+    events around each call, one warm-up, then five timed calls each, the collectors alternating."""
+    pol = M.MlpPolicy.random_init(29, 22, seed=args.seed, precision="f16x3")
+
+    def env(n, **kw):
+        return M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True, **kw)
+
+    K = 16
+    for n in (65536, 262144):
+        group = {
+            "plain policy kernel": M.FusedPolicyRollout(env(n, rollout_pipeline=2), pol, K, seed=args.seed),
+            "preview": M.FusedPolicyRollout(env(n), pol, K, seed=args.seed, view="preview"),
+            "preview + labels": M.FusedPolicyRollout(env(n), pol, K, seed=args.seed, view="preview", expert_labels=True),
+            "preview demo beta=0.5": M.FusedDemonstrationRollout(env(n), K, actor=pol, beta=0.5, seed=args.seed, agent="preview"),
+        }
+        times = {name: [] for name in group}
+        for r in range(6):
+            for name, col in group.items():
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                col.collect()
+                stop.record()
+                stop.synchronize()
+                if r > 0:
+                    times[name].append(start.elapsed_time(stop))
+        base = min(times["plain policy kernel"])
+        print(f"mono {n} envs x {K} steps: collect() " + ", ".join(
+            f"{name} " + " / ".join(f"{t:.3f}" for t in ts) + f" ms ({n * K / min(ts) / 1e3:.1f} M steps/s, x{min(ts) / base:.3f})"
+            for name, ts in times.items()))
+
+
 BETA_SCHEDULES = {"one": 1.0, "linear": lambda f: 1.0 - f, "first": lambda f: 1.0 if f == 0.0 else 0.0}
 
 
@@ -351,7 +392,8 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
     env = M.BatchedSortingEnv(kind=env_kind, num_envs=args.envs, device=0, base_seed=args.seed + 2 * 10 ** 6,
                               max_steps=args.max_steps, auto_reset=True)
     if args.dagger:
-        col = M.FusedDemonstrationRollout(env, args.steps, actor=pol, beta=1.0, seed=args.seed + 7, mix_seed=args.seed + 8)
+        col = M.FusedDemonstrationRollout(env, args.steps, actor=pol, beta=1.0, seed=args.seed + 7, mix_seed=args.seed + 8,
+                                          agent="preview" if agent == "preview" else "own")
     else:
         col = M.DemonstrationCollector(env, args.steps, agent=agent)
     il = M.ImitationLearner(pol, learning_rate=args.pretrain_lr, n_epochs=args.pretrain_epochs, batch_size=args.batch_size,
@@ -454,6 +496,9 @@ def train_modular(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kind", choices=sorted(KINDS) + ["modular"], default="mono")
+    ap.add_argument("--view", choices=("own", "preview"), default="own",
+                    help="--kind mono: what the policy is shown - the observation the previous step returned, or (preview) the one "
+                         "after the step's flow update, as Env_3_Monolith.step shows a stored mono_agent")
     ap.add_argument("--reward", choices=("own", "team"), default="own",
                     help="--kind modular: each agent trains on its own component of the step reward, or both on the sum")
     ap.add_argument("--envs", type=int, default=4096)
@@ -504,9 +549,10 @@ def main():
     ap.add_argument("--bc-schedule", choices=("const", "linear"), default="const",
                     help="with --bc-coef: linear is X times progress_remaining, which reaches 0 in the last iteration")
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo", "modular_demo"), default="all",
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo", "modular_demo", "preview"),
+                    default="all",
                     help="with --time: run one block of the timings only; 'all' is every block but modular_demo (four collectors "
-                         "at 262 144 envs, the multi-launch twin among them), which runs only when named, with any --kind")
+                         "at 262 144 envs, the multi-launch twin among them) and preview, which run only when named, with any --kind")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
                     help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
     ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N",
@@ -516,7 +562,9 @@ def main():
                          "started with (a differing hyperparameter or env is refused by name)")
     ap.add_argument("--save", default=None, help="torch.save the trained state_dict (SB3 names) here")
     args = ap.parse_args()
-    if args.kind == "modular" and not (args.time and args.time_section == "modular_demo"):
+    if args.view == "preview" and args.kind != "mono":
+        raise SystemExit("--view preview is the mono policy's in-step view: it goes with --kind mono")
+    if args.kind == "modular" and not (args.time and args.time_section in ("modular_demo", "preview")):
         return train_modular(args)
     if args.time:
         for name, fn in (("loss_grad", time_loss_grad), ("weight_sync", time_weight_sync), ("arithmetic", time_arithmetic),
@@ -525,15 +573,15 @@ def main():
                 fn(args)
         if args.time_section == "modular_demo":  # only by name: four collectors at 262 144 envs, the multi-launch twin among them
             time_modular_demo(args)
+        if args.time_section == "preview":
+            time_preview(args)
         return
     D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
     env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
                               auto_reset=True)
-    if args.bc_coef is None:
-        col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed)
-    else:  # the rollout PPO trains on, with the rule's label of every state it visits, in one launch
-        col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed, expert_labels=True)
+    # --bc-coef: the rollout PPO trains on, with the rule's label of every state it visits, in one launch
+    col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed, expert_labels=args.bc_coef is not None, view=args.view)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
     clip = (lambda p: 0.2 * p) if args.clip_schedule == "linear" else 0.2
     bc_coef = (lambda p: args.bc_coef * p) if args.bc_coef is not None and args.bc_schedule == "linear" else args.bc_coef
@@ -541,13 +589,13 @@ def main():
     if args.eval_every > 0:
         eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
                                        auto_reset=True)
-        eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1)
+        eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1, view=args.view)
     if args.pretrain and not args.resume:  # a resumed run's weights come from its checkpoint
-        pretrain(args, pol, args.kind, "own", "the policy", eval_col if args.dagger else None)
+        pretrain(args, pol, args.kind, args.view, "the policy", eval_col if args.dagger else None)
     learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
                            arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf, bc_coef=bc_coef)
-    print(f"{KINDS[args.kind]} ({D} -> {A}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
+    print(f"{KINDS[args.kind]} ({D} -> {A}{', view=preview' if args.view == 'preview' else ''}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
           f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}, "
           f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}"
           + (f", bc_coef {args.bc_coef:g} {args.bc_schedule}" if args.bc_coef is not None else ""))
