@@ -1057,7 +1057,7 @@ __global__ __launch_bounds__(kRingThreads) void k_rollout_ring(Params P, uint4 *
 // ==========================================================================================
 template <int KIND, int TILES>
 struct PolLayout {
-    static constexpr int D = Dims<KIND>::D, A = Dims<KIND>::A;
+    static constexpr int kind = KIND, D = Dims<KIND>::D, A = Dims<KIND>::A;
     static constexpr int ENVS = 32 * TILES;                          // envs per wave
     static constexpr int weight_bytes = msep::kLdsFloats * 4;
     static constexpr int tile_bytes = (ENVS * D * 4 + 15) / 16 * 16; // >= the ENVS x A mask tile
@@ -1183,10 +1183,9 @@ __global__ __launch_bounds__(512) void k_rollout_policy(Params P, uint4 *__restr
 #include "mse_rollout_policy_body.inc"
 }
 
-// k_rollout_policy's plain shape with one more expression and one more store per step: the rule-based controller's label of
-// the state the recorded row shows, rule_based_action<KIND>(e, Stage<false>::rule_mode(e.st_in, tb)) - k_rollout_demo's label,
-// so what mse_rule_actions returns for that state; no stream is read.  Every other output, the written-back state and the
-// step counter are k_rollout_policy's bits: the same statements (mse_rollout_policy_body.inc).  One network: no SORTPOL.
+// k_rollout_policy with one more expression and one more store per step: the rule-based controller's label of the state the
+// recorded row shows, rule_based_action<KIND>(e, Stage<false>::rule_mode(e.st_in, tb)) - k_rollout_demo's label, what
+// mse_rule_actions returns for it; no stream is read.  All else is k_rollout_policy's bits (the same statements).  No SORTPOL.
 template <int KIND, bool NOISE, int TILES, bool F16X3>
 __global__ __launch_bounds__(512) void k_rollout_policy_labelled(Params P, uint4 *__restrict__ planes,
                                                                  const uint32_t *__restrict__ table_image,
@@ -1556,11 +1555,10 @@ __global__ __launch_bounds__(RING ? 768 : 512) void k_rollout_policy_roles(Param
 // argmax on get_sort_obs() after the step's flow update, or rng_sorting.choice([0, 1]); the press part the pressing
 // agent's argmax on get_press_obs() after the flow update (press_action_masks() as its mask when it is maskable and
 // masking is on), or rng_pressing.choice(flatnonzero(press_action_masks())) / choice(11).  The flat action is applied
-// without sanitising (:254-257).  Shaped like k_rollout_policy: one wave owns 32 TILES envs for the whole launch, the
-// two agents' weight images and the tables are in LDS, the env state stays in registers.  Per step a copy of the env
-// takes the flow update for both previews (env_step takes the same step), the agents run their actors only (no
-// critic), the lane's own PCG64 streams draw what no agent decides (the code of k_model_actions), env_step applies
-// the action.  The streams' planes are only read and written by the instantiations that draw from them.
+// without sanitising (:254-257).  k_rollout_policy's plain shape (mse_plain_frame.inc) with the two agents' weight images.
+// Per step a copy of the env takes the flow update for both previews (env_step takes the same step), the agents run their
+// actors only (no critic), the lane's own PCG64 streams draw what no agent decides (the code of k_model_actions), env_step
+// applies the action.  The streams' planes are only read and written by the instantiations that draw from them.
 // LDS: [sorting agent image][pressing agent image][tables][per wave: row tile | bale ledger]
 // ==========================================================================================
 template <bool NOISE, bool SORT_AG, bool PRESS_AG, int TILES>
@@ -1575,42 +1573,18 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
 {
     using L = PolLayout<3, TILES>; // the row tile holds an observation row (29 floats) or a mask row
     constexpr int D = L::D, A = L::A, ENVS = L::ENVS, NR = msep::regs_for_actions(11);
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
     constexpr int kWeightBytes = L::weight_bytes * 2; // [sorting agent image][pressing agent image]
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
-    // the batch's end its last env; mirrors store nothing
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
-
+#define MSE_PLAIN_FRAME_PART 1
+#include "mse_plain_frame.inc"
     if (SORT_AG) msep_copy_image(lw, sort_blob, true, tid, blockDim.x);
     if (PRESS_AG) msep_copy_image(lw + msep::kLdsFloats, press_blob, true, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    load_env<3, NOISE>(e, planes, P, i);
+#define MSE_PLAIN_FRAME_PART 2
+#include "mse_plain_frame.inc"
     Rng32 srt, prs; // rng_sorting (seed+2), rng_pressing (seed+3): the fallback draws (k_model_actions)
     if (!SORT_AG && wave_active) srt.load_sortrng(planes, P, i);
     if (!PRESS_AG && wave_active) prs.load_press(planes, P, i, e);
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
+#define MSE_PLAIN_FRAME_PART 3
+#include "mse_plain_frame.inc"
     const msep::lds_f4 wl_sort = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
     const msep::lds_f4 wl_press = (msep::lds_f4)(__attribute__((address_space(3))) float *)(lw + msep::kLdsFloats);
     const bool unmasked_draw = (flags & MSE_STEP_UNMASKED) != 0;
@@ -1694,23 +1668,19 @@ __global__ __launch_bounds__(512) void k_rollout_model(Params P, uint4 *__restri
     if (live) store_env<3, NOISE>(e, planes, P, i, false);
     if (live && !SORT_AG) srt.store_sortrng(planes, P, i);
     if (live && !PRESS_AG) prs.store_press_state(planes, P, i);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+#define MSE_PLAIN_FRAME_PART 4
+#include "mse_plain_frame.inc"
 }
 
 // ==========================================================================================
 // Env_3 modular collection: the sorting and the pressing agent act side by side in the env they are deployed in, and
 // the launch records what a learner of each needs (DESIGN.md "Modular rollout")
 //
-// k_rollout_model's shape - one wave owns 32 TILES envs for the whole launch, both agents' weight images and the tables
-// in LDS, the env state in registers, the row tile reused for the 13- and 16-float rows and the 11-byte mask row - with
-// both whole networks instead of two actors: per step a copy of the env takes the flow update for both previews
-// (env_step takes the same step), each agent samples (or, with its DETERMINISTIC flag, takes the argmax), scores and
-// values its own row through msep::policy_tiles with a draw word of its own seed, the flat action 11 sort + press goes
-// through env_step<3> unsanitised, and the step's reward is recorded whole and in its two parts (StepResult::r_sort,
-// r_press).  No fallback draws: the env's rng_sorting / rng_pressing planes are neither read nor written.
+// k_rollout_model's shape and previews (mse_plain_frame.inc; the row tile reused for the 13- and 16-float rows and the 11-byte
+// mask row) with both whole networks instead of two actors: each agent samples (or, with its DETERMINISTIC flag, takes the
+// argmax), scores and values its own row through msep::policy_tiles with a draw word of its own seed, the flat action
+// 11 sort + press goes through env_step<3> unsanitised, and the step's reward is recorded whole and in its two parts
+// (StepResult::r_sort, r_press).  No fallback draws: the env's rng_sorting / rng_pressing planes are neither read nor written.
 // LDS: [sorting agent image][pressing agent image][tables][per wave: row tile | bale ledger]
 // ==========================================================================================
 // a reference to `a` or to `b`, chosen at compile time (mse_rollout_modular_body.inc: which Params the step reads)
@@ -1763,9 +1733,8 @@ __global__ __launch_bounds__(512) void k_rollout_modular_labelled(Params P, uint
 // Demonstration rollout: the rule-based controller labels every state a student (or a mixture of student and expert)
 // visits, K steps per launch (DESIGN.md "Demonstration rollout")
 //
-// k_rollout_policy's plain shape - one wave owns 32 TILES envs for the whole launch, the weight image and the tables in
-// LDS, the env state in registers, the same mirror lanes, phase priorities and row staging - with three things per
-// step instead of one: the label rule_based_action() of the state (what mse_rule_actions returns for it; no stream is
+// k_rollout_policy's plain shape (mse_plain_frame.inc), phase priorities and row staging, with three things per step
+// instead of one: the label rule_based_action() of the state (what mse_rule_actions returns for it; no stream is
 // read), the student's action through msep::policy_tiles on the word of (seed, global env index, t + k), and the
 // integer decision of mse_demo_mix.h on the word of (mix_seed, global env index, t + k) which of the two is stepped.
 // ACTOR = false (no student): no weight image in LDS, no MFMA; the expert's action is stepped at every step.
@@ -1780,38 +1749,14 @@ __global__ __launch_bounds__(512) void k_rollout_demo(Params P, uint4 *__restric
 {
     using L = PolLayout<KIND, TILES>;
     constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
     constexpr int kWeightBytes = ACTOR ? L::weight_bytes : 0;
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
-    // the batch's end its last env; mirrors store nothing
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
-
+#define MSE_PLAIN_FRAME_PART 1
+#include "mse_plain_frame.inc"
     if (ACTOR) msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    load_env<KIND, NOISE>(e, planes, P, i);
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
+#define MSE_PLAIN_FRAME_PART 2
+#include "mse_plain_frame.inc"
+#define MSE_PLAIN_FRAME_PART 3
+#include "mse_plain_frame.inc"
     const msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
     const bool deterministic = (flags & MSE_DEMO_ACTOR_DETERMINISTIC) != 0;
     const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // stepped as mse_step steps it, masked
@@ -1824,8 +1769,7 @@ __global__ __launch_bounds__(512) void k_rollout_demo(Params P, uint4 *__restric
     container_purity_k(e, kcur);
     env_obs<KIND>(e, P, tb, kcur, o);
     uint32_t mbits = action_mask_bits<KIND>(e, P);
-    // the student's stream keys of the env(s) this lane serves as an MFMA column (k_rollout_policy); the mixture's key
-    // is the lane's own env's
+    // the student's stream keys (k_rollout_policy's, of the lane's MFMA columns); the mixture's key is the lane's own env's
     const int h = lane >> 5, col = lane & 31;
     const uint32_t key0 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + col));
     const uint32_t key1 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
@@ -1879,17 +1823,14 @@ __global__ __launch_bounds__(512) void k_rollout_demo(Params P, uint4 *__restric
     }
     if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
     if (live) store_env<KIND, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+#define MSE_PLAIN_FRAME_PART 4
+#include "mse_plain_frame.inc"
 }
 
 // ==========================================================================================
 // Preview rollout: the mono policy on the in-step view (env_monolith.py:144-150; DESIGN.md "Preview rollout")
 //
-// k_rollout_demo's frame with an actor - one wave owns 32 TILES envs for the whole launch, one weight image and the tables
-// in LDS, the env state in registers, the same mirror lanes, phase priorities and row staging - on Env_3, with the row
+// k_rollout_demo with an actor (mse_plain_frame.inc, the same phase priorities and row staging) on Env_3, with the row
 // taken as k_rollout_modular takes its two: a copy of the env takes the step's flow update and get_sort_obs() ||
 // get_press_obs() of the copy (env_obs<3> with the current state's container purities) is what the network sees; the mask
 // is action_masks() of the state itself.  The policy's action, log-probability and value are recorded whoever steps; the
@@ -1907,45 +1848,20 @@ __global__ __launch_bounds__(512) void k_rollout_policy_preview(Params P, uint4 
 {
     using L = PolLayout<3, TILES>;
     constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
     constexpr int kWeightBytes = L::weight_bytes;
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
-    // the batch's end its last env; mirrors store nothing
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
-
+#define MSE_PLAIN_FRAME_PART 1
+#include "mse_plain_frame.inc"
     msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    load_env<3, NOISE>(e, planes, P, i);
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
+#define MSE_PLAIN_FRAME_PART 2
+#include "mse_plain_frame.inc"
+#define MSE_PLAIN_FRAME_PART 3
+#include "mse_plain_frame.inc"
     const msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
     const bool deterministic = (flags & MSE_PREVIEW_DETERMINISTIC) != 0;
     const uint32_t step_flags = flags & MSE_STEP_CHECK_OVERFLOW; // the action is applied unsanitised: the masked step
     int kcur[4]; // container purities of the current state (the sorting half of the view needs them)
     container_purity_k(e, kcur);
-    // the policy's stream keys of the env(s) this lane serves as an MFMA column (k_rollout_policy); the mixture's key is
-    // the lane's own env's
+    // the policy's stream keys (k_rollout_policy's, of the lane's MFMA columns); the mixture's key is the lane's own env's
     const int h = lane >> 5, col = lane & 31;
     const uint32_t key0 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + col));
     const uint32_t key1 = mse_policy_key(seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
@@ -2023,10 +1939,8 @@ __global__ __launch_bounds__(512) void k_rollout_policy_preview(Params P, uint4 
     }
     if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
     if (live) store_env<3, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+#define MSE_PLAIN_FRAME_PART 4
+#include "mse_plain_frame.inc"
 }
 
 template <int KIND>

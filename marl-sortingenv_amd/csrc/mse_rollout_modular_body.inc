@@ -2,42 +2,18 @@
 // k_rollout_modular (LABEL = false) and k_rollout_modular_labelled (LABEL = true), whose further arguments must stay out of
 // k_rollout_modular's.  Text and not a function for the reason mse_ppo_grad_body.inc gives.  The including function provides
 // the template parameters NOISE and TILES, the constant LABEL, the kernel's arguments and `mix_seed`, `expert_threshold`,
-// `labels` (mse_modular_label_buffers; never read with LABEL = false).
+// `labels` (mse_modular_label_buffers; never read with LABEL = false).  Frame: mse_plain_frame.inc.
     using L = PolLayout<3, TILES>; // k_rollout_model's tile: wide enough for every row this kernel stages
     constexpr int ENVS = L::ENVS, NR_SORT = msep::regs_for_actions(2), NR_PRESS = msep::regs_for_actions(11);
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
     constexpr int kWeightBytes = L::weight_bytes * 2; // [sorting agent image][pressing agent image]
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // every lane of an active wave steps an env (k_rollout_policy): TILES = 1 lanes 32-63 mirror lanes 0-31, lanes past
-    // the batch's end its last env; mirrors store nothing
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
-
+#define MSE_PLAIN_FRAME_PART 1
+#include "mse_plain_frame.inc"
     msep_copy_image(lw, sort_blob, true, tid, blockDim.x);
     msep_copy_image(lw + msep::kLdsFloats, press_blob, true, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
-    load_env<3, NOISE>(e, planes, P, i);
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
+#define MSE_PLAIN_FRAME_PART 2
+#include "mse_plain_frame.inc"
+#define MSE_PLAIN_FRAME_PART 3
+#include "mse_plain_frame.inc"
     const msep::lds_f4 wl_sort = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
     const msep::lds_f4 wl_press = (msep::lds_f4)(__attribute__((address_space(3))) float *)(lw + msep::kLdsFloats);
     const bool agent_masked = (flags & MSE_MODEL_PRESS_AGENT_MASKED) != 0;
@@ -181,7 +157,5 @@
     }
     if (live && out.last_dones != nullptr) out.last_dones[i] = (uint8_t)last_done;
     if (live) store_env<3, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+#define MSE_PLAIN_FRAME_PART 4
+#include "mse_plain_frame.inc"

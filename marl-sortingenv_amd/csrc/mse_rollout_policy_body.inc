@@ -2,46 +2,20 @@
 // k_rollout_policy (LABEL = false) and k_rollout_policy_labelled (LABEL = true), whose one more argument must stay out of
 // k_rollout_policy's.  Text and not a function for the reason mse_ppo_grad_body.inc gives.  The including function provides
 // the template parameters KIND, NOISE, TILES, F16X3, the constants SORTPOL and LABEL, the kernel's arguments and `expert_out`
-// (i32[K, N]; never read with LABEL = false).
+// (i32[K, N]; never read with LABEL = false).  Frame: mse_plain_frame.inc.
     using L = PolLayout<KIND, TILES>;
     constexpr int D = L::D, A = L::A, NR = msep::regs_for_actions(A), ENVS = L::ENVS;
-    uint8_t *lds = reinterpret_cast<uint8_t *>(mse_dyn_lds);
-    float *lw = reinterpret_cast<float *>(lds);
     constexpr int kWeightBytes = L::weight_bytes * (SORTPOL ? 2 : 1); // [policy image][sorting policy image]
-    uint32_t *ltab = reinterpret_cast<uint32_t *>(lds + kWeightBytes);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n_waves = blockDim.x >> 6;
-    const int table_bytes = P.table_words * 4;
-    uint8_t *lwave = lds + kWeightBytes + table_bytes + wave * L::wave_bytes;
-    uint4 *lbale = reinterpret_cast<uint4 *>(lwave + L::tile_bytes);
-    const long long wave_row0 = ((long long)blockIdx.x * n_waves + wave) * ENVS;
-    long long rem = P.n - wave_row0;
-    const int n_valid = rem >= ENVS ? ENVS : (rem > 0 ? (int)rem : 0);
-    const bool wave_active = n_valid > 0;
-    // Every lane of an active wave steps an env, so that the step loop has no per-lane "is there an env here" region
-    // (the compiler kept two copies of the env's ~90 registers around one and moved them back and forth every step):
-    // TILES = 1: lanes 32-63 mirror lanes 0-31; lanes past the batch's end mirror its last env.  Mirrors compute what
-    // their original computes and store nothing.
-    const int src_lane = TILES == 1 ? (lane & 31) : lane;
-    const bool live = wave_active && lane < ENVS && wave_row0 + lane < P.n;
-    const long long i = wave_active ? (wave_row0 + src_lane < P.n ? wave_row0 + src_lane : P.n - 1) : 0;
-
+#define MSE_PLAIN_FRAME_PART 1
+#include "mse_plain_frame.inc"
     msep_copy_image(lw, weight_blob, F16X3, tid, blockDim.x);
     if (SORTPOL) msep_copy_image(lw + msep::kLdsFloats, sort_weight_blob, F16X3, tid, blockDim.x);
-    for (int w = tid; w < P.table_words / 4; w += blockDim.x)
-        reinterpret_cast<uint4 *>(ltab)[w] = reinterpret_cast<const uint4 *>(table_image)[w];
-    const BaleRef bales{lbale + src_lane, ENVS};
-    if (P.track_bales && wave_active) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) lbale[m * ENVS + src_lane] = planes[(long long)(PL_BALE0 + m) * P.n_pad + i];
-    }
-    Env e;
+#define MSE_PLAIN_FRAME_PART 2
+#include "mse_plain_frame.inc"
     int sm = -1;
-    load_env<KIND, NOISE>(e, planes, P, i);
     if (KIND == 2 && sort_mode != nullptr) sm = sort_mode[i];
-    __syncthreads();
-    if (!wave_active) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): nothing but stores inside the step loop
-    const Tables tb = tables_at(ltab, P);
+#define MSE_PLAIN_FRAME_PART 3
+#include "mse_plain_frame.inc"
     msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
 
     // the observation and mask of the current state (what reset / the previous launch left)
@@ -147,7 +121,5 @@
     }
     if (live && last_done_out != nullptr) last_done_out[i] = (uint8_t)last_done;
     if (live) store_env<KIND, NOISE>(e, planes, P, i, false);
-    if (P.track_bales && live) {
-#pragma unroll
-        for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = lbale[m * ENVS + lane];
-    }
+#define MSE_PLAIN_FRAME_PART 4
+#include "mse_plain_frame.inc"

@@ -15,7 +15,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests import replay
+from tests.rollout_checks import bits_equal, cus, guarded, inside, lib, overflow_config
 from tests.test_demo_mixture_cpu import MIX_SEED, ONE, who_steps
 from tests.test_gpu_model_rollout import _state_equal
 
@@ -27,8 +27,6 @@ DIMS = {"sort": (13, 2), "press": (16, 11), "mono": (29, 22)}
 SNAP_CURRENT_STEP = 32  # column of mse_get_state's integer record that holds the env's current_step
 LAUNCHES = (5, 1, 4)
 GAMMA = 0.97
-# a container overflows inside a three-step episode at this capacity (config.yml: 700)
-OVERFLOW_OVERRIDES = {"pressing_station": {"container_capacity": 30}}
 
 
 def _env(kind, n, noise=0.05, max_steps=3, base_seed=11, **kw):
@@ -37,11 +35,6 @@ def _env(kind, n, noise=0.05, max_steps=3, base_seed=11, **kw):
     kw.setdefault("auto_reset", True)
     return M.BatchedSortingEnv(kind=kind, num_envs=n, device=0, base_seed=base_seed, max_steps=max_steps,
                                noise_sorting=noise, balesize=200, **kw)
-
-
-def _overflow_config(noise):
-    meta = dict(config_overrides=OVERFLOW_OVERRIDES)
-    return replay.sorting_config(meta).with_overrides({"sorting_station": {"noise": noise}})
 
 
 @functools.lru_cache(maxsize=None)
@@ -57,31 +50,6 @@ def _actor(kind, precision="f16x3", head_gain=20.0, seed=3):
     p = M.MlpPolicy(d, a, {k: v.reshape(sh) for (k, v), sh in zip(w.items(), _shapes(d, a))}, precision=precision)
     assert p.precision == precision
     return p
-
-
-def _lib():
-    import marl_sortingenv_amd as M
-
-    return M.load_library()
-
-
-def _cus():
-    import torch
-
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _bits_equal(tag, got, exp, keys=KEYS):
-    import torch
-
-    for key in keys:
-        x, y = got[key], exp[key]
-        assert x.shape == y.shape and x.dtype == y.dtype, (tag, key)
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        if not torch.equal(x, y):
-            bad = torch.nonzero((x != y).reshape(-1))
-            raise AssertionError(f"{tag}: {key} differs at {bad.shape[0]} elements, first flat index {int(bad[0])}")
 
 
 def hand_collect(env, K, actor=None, seed=SEED, mix_seed=MIX_SEED, threshold=ONE, deterministic=False,
@@ -158,7 +126,7 @@ def _compare_with_twin(tag, kind, n, noise, max_steps, mode, launches=LAUNCHES, 
             twin.t = b.policy_step
             twin._last_done.copy_(last_dones)
         got, exp = fused.collect(), twin.collect()
-        _bits_equal(f"{tag} K={K}", got, exp)
+        bits_equal(f"{tag} K={K}", got, exp, KEYS)
         _state_equal(f"{tag} K={K}", a, b)
         assert a.policy_step == t0 + K
         assert bool((got["expert_stepped"] == (1 if actor is None else 0)).all())
@@ -191,7 +159,7 @@ def test_fused_demo_rollout_matches_twin(kind, n, mode):
 @pytest.mark.parametrize("mode", ["expert", "sampled_f16x3", "sampled_f32"])
 def test_fused_demo_rollout_matches_twin_in_64_env_waves(mode):
     """256 x CUs + 1 envs: the smallest batch plan_policy_plain gives two tiles per wave in the f16x3 form."""
-    _compare_with_twin(f"tiles=2 {mode}", "mono", 256 * _cus() + 1, 0.05, 3, mode, launches=(2,))
+    _compare_with_twin(f"tiles=2 {mode}", "mono", 256 * cus() + 1, 0.05, 3, mode, launches=(2,))
 
 
 def test_fused_demo_rollout_on_a_shard():
@@ -219,14 +187,14 @@ def test_fused_demo_rollout_check_overflow(kind, mode):
     actor = None if mode == "expert" else _actor(kind)
     for n in (33, 257):
         for noise in (0.0, 0.05):
-            cfg = _overflow_config(noise)
+            cfg = overflow_config(noise)
             a, b = _env(kind, n, noise, config=cfg), _env(kind, n, noise, config=cfg)
             hits = 0
             for K in LAUNCHES:
                 fused = M.FusedDemonstrationRollout(a, K, actor=actor, gamma=GAMMA, seed=SEED, mix_seed=MIX_SEED, check_overflow=True)
                 got = fused.collect()
                 exp = hand_collect(b, K, actor, threshold=ONE if actor is None else 0, check_overflow=True)
-                _bits_equal(f"{kind} {mode} n={n} noise={noise} K={K}", got, exp, KEYS + ("expert_stepped",))
+                bits_equal(f"{kind} {mode} n={n} noise={noise} K={K}", got, exp, KEYS + ("expert_stepped",))
                 _state_equal(f"{kind} {mode} n={n} noise={noise} K={K}", a, b)
                 hits += int((got["rewards"] == float(pen)).sum())
             assert hits >= 1, "no episode ended by overflow"
@@ -254,7 +222,7 @@ def test_mixture_matches_the_hand_loop(kind, n, deterministic):
                                             seed=SEED, mix_seed=MIX_SEED)
         got = fused.collect()
         exp = hand_collect(b, K, actor, threshold=1 << 23, deterministic=deterministic)
-        _bits_equal(f"{kind} n={n} K={K}", got, exp, KEYS + ("expert_stepped",))
+        bits_equal(f"{kind} n={n} K={K}", got, exp, KEYS + ("expert_stepped",))
         _state_equal(f"{kind} n={n} K={K}", a, b)
         want = np.stack([who_steps(n, 0, MIX_SEED, t + k, 1 << 23) for k in range(K)])
         assert np.array_equal(got["expert_stepped"].cpu().numpy(), want)
@@ -283,13 +251,13 @@ def test_mixture_ends(n, precision):
     envs = [_env(kind, n) for _ in range(4)]
     zero = M.FusedDemonstrationRollout(envs[0], K, actor=actor, beta=0.0, gamma=GAMMA, seed=SEED, mix_seed=MIX_SEED).collect()
     twin = M.DemonstrationCollector(envs[1], K, actor=actor, gamma=GAMMA, seed=SEED).collect()
-    _bits_equal("threshold 0", zero, twin)
+    bits_equal("threshold 0", zero, twin, KEYS)
     _state_equal("threshold 0", envs[0], envs[1])
     assert not bool(zero["expert_stepped"].any())
     assert bool((zero["stepped_actions"] != zero["actions"]).any()), "an untrained actor does not act like the expert"
     one = M.FusedDemonstrationRollout(envs[2], K, actor=actor, beta=1.0, gamma=GAMMA, seed=SEED, mix_seed=MIX_SEED).collect()
     none = M.FusedDemonstrationRollout(envs[3], K, actor=None, gamma=GAMMA).collect()
-    _bits_equal("threshold 2^24", one, none, KEYS + ("expert_stepped",))
+    bits_equal("threshold 2^24", one, none, KEYS + ("expert_stepped",))
     _state_equal("threshold 2^24", envs[2], envs[3])
     assert bool((one["expert_stepped"] == 1).all()) and bool((one["stepped_actions"] == one["actions"]).all())
     assert all(e.policy_step == K for e in envs)
@@ -337,28 +305,17 @@ def _sizes(kind, n, K):
             "stepped_actions": K * n * 4, "expert_stepped": K * n, "rewards": K * n * 4, "last_dones": n}
 
 
-def _guarded(kind, n, K):
-    """Every output inside one byte tensor, 64 guard bytes (0xA5) before and after each -> (raw, {name: (offset, bytes)})."""
-    import torch
-
-    at, off = {}, 64
-    for name, size in _sizes(kind, n, K).items():
-        at[name] = (off, size)
-        off += (size + 15) // 16 * 16 + 64
-    return torch.full((off,), 0xA5, dtype=torch.uint8, device="cuda:0"), at
-
-
 def _raw_call(env, actor, K, flags, ptrs, seed=SEED, mix_seed=MIX_SEED, threshold=1 << 23, struct_size=None, no_out=False):
     from marl_sortingenv_amd._lib import DEMO_BUFFER_NAMES, MseDemoBuffers
 
     out = MseDemoBuffers(C.sizeof(MseDemoBuffers) if struct_size is None else struct_size, 0,
                          *(ptrs.get(name) for name in DEMO_BUFFER_NAMES))
-    return _lib().mse_rollout_demo(None if env is None else env._h, None if actor is None else actor._h, K, seed, mix_seed,
+    return lib().mse_rollout_demo(None if env is None else env._h, None if actor is None else actor._h, K, seed, mix_seed,
                                   threshold, flags, None if no_out else C.byref(out), None)
 
 
 def _check_call(env, actor, K, flags=0, seed=SEED, mix_seed=MIX_SEED, threshold=1 << 23):
-    return _lib().mse_rollout_demo_check(None if env is None else env._h, None if actor is None else actor._h, K, seed,
+    return lib().mse_rollout_demo_check(None if env is None else env._h, None if actor is None else actor._h, K, seed,
                                         mix_seed, threshold, flags)
 
 
@@ -376,14 +333,12 @@ def test_fused_demo_rollout_memory(kind, with_actor):
     actor = _actor(kind) if with_actor else None
     env = _env(kind, n, base_seed=9)
     rng_before = env.get_state()[2].clone()
-    raw, at = _guarded(kind, n, K)
+    raw, at = guarded(_sizes(kind, n, K))
     ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
     assert _raw_call(env, actor, K, 0, ptrs) == 0
     torch.cuda.synchronize()
-    inside = torch.zeros(raw.numel(), dtype=torch.bool, device=raw.device)
-    for name, (off, size) in at.items():
-        inside[off:off + size] = True
-    assert bool((raw[~inside] == 0xA5).all()), "a guard byte was written"
+    within = inside(raw, at)
+    assert bool((raw[~within] == 0xA5).all()), "a guard byte was written"
     first = raw.clone()
     twin = _env(kind, n, base_seed=9)
     exp = hand_collect(twin, K, actor, threshold=1 << 23)
@@ -400,7 +355,7 @@ def test_fused_demo_rollout_memory(kind, with_actor):
     for name in DEMO_BUFFER_NAMES:
         assert _raw_call(env, actor, 1, 0, {name: ptrs[name]}) == 0, name
     torch.cuda.synchronize()
-    assert bool((raw[~inside] == 0xA5).all())
+    assert bool((raw[~within] == 0xA5).all())
     assert not torch.equal(raw, first)  # (the single outputs were rewritten)
     assert env.policy_step == K + K + len(DEMO_BUFFER_NAMES) and env.error_count() == 0
     env.close()
@@ -431,7 +386,7 @@ def test_fused_demo_rollout_refusals():
 
     try:
         env = keep(_env(kind, n))
-        raw, at = _guarded(kind, n, K)
+        raw, at = guarded(_sizes(kind, n, K))
         ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
         assert _check_call(env, actor, K) == 0 and env.policy_step == 0  # the check launches nothing
         assert _raw_call(env, actor, K, 0, ptrs) == 0
@@ -487,7 +442,7 @@ def test_fused_demo_rollout_refusals():
         assert _raw_call(small_big, actor, K, 0, ptrs) == 0
         torch.cuda.synchronize()
         filled = raw.clone()
-        big = keep(_env(kind, 256 * _cus() + 1, config=big_cfg))
+        big = keep(_env(kind, 256 * cus() + 1, config=big_cfg))
         big_state = [x.clone() for x in big.get_state()]
         refused(UNSUPPORTED, e=big)
         assert b"LDS image does not fit" in big.L.mse_last_error()

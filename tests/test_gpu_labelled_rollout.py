@@ -15,7 +15,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.test_gpu_demo_rollout import BIG_TABLES, GEN, _actor, _bits_equal, _cus, _env, _overflow_config
+from tests.rollout_checks import bits_equal, cus, guarded, inside, overflow_config
+from tests.test_gpu_demo_rollout import BIG_TABLES, DIMS, GEN, _actor, _env
 from tests.test_gpu_model_rollout import _state_equal
 
 pytestmark = pytest.mark.gpu
@@ -55,7 +56,7 @@ def _compare(tag, kind, n, noise, max_steps, precision, det, launches=LAUNCHES, 
         got = M.FusedPolicyRollout(a, pol, K, seed=SEED, expert_labels=True).collect(deterministic=det, **collect_kw)
         exp = M.FusedPolicyRollout(b, pol, K, seed=SEED).collect(deterministic=det, **collect_kw)
         assert "expert_actions" not in exp and got["expert_actions"].dtype == torch.int32 and got["expert_actions"].shape == (K, n)
-        _bits_equal(f"{tag} K={K}", got, exp, keys=NINE)
+        bits_equal(f"{tag} K={K}", got, exp, keys=NINE)
         _state_equal(f"{tag} K={K}", a, b)
         assert a.policy_step == t0 + K
         if not collect_kw:  # the twin offers neither flag; the hand loop serves those
@@ -64,7 +65,7 @@ def _compare(tag, kind, n, noise, max_steps, precision, det, launches=LAUNCHES, 
                 twin.t = t0
                 twin._last_done.copy_(last_dones)
             tw = twin.collect(deterministic=det)
-            _bits_equal(f"{tag} K={K} twin", got, tw, keys=NINE[:7] + ("expert_actions", "last_values", "last_dones"))
+            bits_equal(f"{tag} K={K} twin", got, tw, keys=NINE[:7] + ("expert_actions", "last_values", "last_dones"))
             last_dones = tw["last_dones"]
             assert torch.equal(got["expert_actions"], hand_labels(d, got["actions"])), f"{tag} K={K}: labels against the hand loop"
         labels.append(got["expert_actions"].clone())
@@ -95,7 +96,7 @@ def test_labelled_rollout_matches_the_plain_rollout_the_twin_and_the_hand_loop(k
 
 @pytest.mark.parametrize("precision", ["f16x3", "f32"])
 def test_labelled_rollout_in_64_env_waves(precision):
-    _compare(f"tiles=2 {precision}", "mono", 256 * _cus() + 1, 0.05, 3, precision, False, launches=(2,))
+    _compare(f"tiles=2 {precision}", "mono", 256 * cus() + 1, 0.05, 3, precision, False, launches=(2,))
 
 
 def test_labelled_rollout_on_a_shard():
@@ -112,7 +113,7 @@ def test_labelled_rollout_flags(kind):
     import marl_sortingenv_amd as M
 
     pol = _actor(kind)
-    for collect_kw, env_kw in ((dict(use_action_masking=False), {}), (dict(check_overflow=True), dict(config=_overflow_config(0.05)))):
+    for collect_kw, env_kw in ((dict(use_action_masking=False), {}), (dict(check_overflow=True), dict(config=overflow_config(0.05)))):
         _compare(f"{kind} {collect_kw}", kind, 97, 0.05, 3, "f16x3", False, flags=collect_kw, **env_kw)
         # the labels under the flag: a hand loop that steps the recorded actions with the same flag
         a, d = _env(kind, 97, **env_kw), _env(kind, 97, **env_kw)
@@ -154,21 +155,13 @@ def test_the_twin_labels_with_a_sort_policy_and_the_fused_collector_refuses_it()
 OUTS = NINE[:7] + ("last_values", "last_dones", "expert_actions")
 
 
-def _guarded(kind, n, K):
-    """Every output inside one byte tensor, 64 guard bytes (0xA5) before and after each -> (raw, {name: (offset, bytes)})"""
-    import torch
-
-    from tests.test_gpu_demo_rollout import DIMS
-
+def _sizes(kind, n, K):
     D, A = DIMS[kind]
     sizes = {"observations": K * n * D * 4, "action_masks": K * n * A, "actions": K * n * 4, "log_probs": K * n * 4,
              "values": K * n * 4, "rewards": K * n * 4, "episode_starts": K * n, "last_values": n * 4, "last_dones": n,
              "expert_actions": K * n * 4}
-    at, off = {}, 64
-    for name in OUTS:
-        at[name] = (off, sizes[name])
-        off = (off + sizes[name] + 64 + 15) // 16 * 16
-    return torch.full((off + 64,), 0xA5, dtype=torch.uint8, device="cuda"), at
+    assert tuple(sizes) == OUTS
+    return sizes
 
 
 def _raw_call(env, pol, K, flags, ptrs, seed=SEED, det=0, sort_mode=None):
@@ -194,14 +187,12 @@ def test_labelled_rollout_memory(kind):
     n, K = 97, 4
     pol = _actor(kind)
     env = _env(kind, n)
-    raw, at = _guarded(kind, n, K)
+    raw, at = guarded(_sizes(kind, n, K))
     ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
     assert _raw_call(env, pol, K, 0, ptrs) == 0
     torch.cuda.synchronize()
-    inside = torch.zeros(raw.numel(), dtype=torch.bool, device="cuda")
-    for off, size in at.values():
-        inside[off:off + size] = True
-    assert bool((raw[~inside] == 0xA5).all()), "a guard byte was written"
+    within = inside(raw, at)
+    assert bool((raw[~within] == 0xA5).all()), "a guard byte was written"
     full = raw.clone()
     for name in NINE:  # each optional output NULL in turn
         e2 = _env(kind, n)
@@ -210,9 +201,9 @@ def test_labelled_rollout_memory(kind):
         torch.cuda.synchronize()
         off, size = at[name]
         assert bool((raw[off:off + size] == 0xA5).all()), name
-        keep = inside.clone()
+        keep = within.clone()
         keep[off:off + size] = False
-        assert torch.equal(raw[keep], full[keep]) and bool((raw[~inside] == 0xA5).all()), name
+        assert torch.equal(raw[keep], full[keep]) and bool((raw[~within] == 0xA5).all()), name
         _state_equal(f"{name} NULL", env, e2)
         e2.close()
     env.close()
@@ -234,7 +225,7 @@ def test_labelled_rollout_refusals():
 
     try:
         env = keep(_env(kind, n))
-        raw, at = _guarded(kind, n, K)
+        raw, at = guarded(_sizes(kind, n, K))
         ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
         assert _check_call(env, pol, K) == 0 and env.policy_step == 0  # the check launches nothing
         assert _raw_call(env, pol, K, 0, ptrs) == 0
@@ -283,7 +274,7 @@ def test_labelled_rollout_refusals():
         assert _check_call(small_big, pol, K) == 0 and _raw_call(small_big, pol, K, 0, ptrs) == 0
         torch.cuda.synchronize()
         filled = raw.clone()
-        big = keep(_env(kind, 256 * _cus() + 1, config=big_cfg))
+        big = keep(_env(kind, 256 * cus() + 1, config=big_cfg))
         refused(UNSUPPORTED, e=big)
         assert b"LDS image does not fit" in pol.L.mse_last_error() and big.policy_step == 0
         with pytest.raises(M.MseError):

@@ -15,6 +15,7 @@ import pytest
 
 from oracle.oracle import OracleEnv
 from tests import replay
+from tests.rollout_checks import cus
 from tests.test_gpu_full_size_oracle import _COL_IDX, _COL_NAME, _check_reward, _same
 from tests.test_gpu_golden import SKIP_COLS, _skip_words
 
@@ -225,18 +226,12 @@ def _final_state(tag, env, envs, orcs, noise, gen=False):
         _same(f"{tag}: env {i} PCG64 words", rng[i, words][None], R[words][None])
 
 
-def _cus():
-    import torch
-
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
 @pytest.mark.parametrize("run", ["both_maskable_n5", "sort_unmasked_n0"])
 @pytest.mark.parametrize("per_cu", [256, 512], ids=["k_rollout_model_tiles1", "k_rollout_model_tiles2"])
 def test_fused_model_rollout_matches_oracle_at_size(per_cu, run):
     import torch
 
-    n, base = per_cu * _cus(), 5000
+    n, base = per_cu * cus(), 5000
     combo, noise, masking = ("both_maskable", 0.05, True) if run == "both_maskable_n5" else ("sort", 0.0, False)
     sort_ag, press_ag, maskable = _agents(combo, seed=7, head_gain=20.0)
     env = _env(n, noise, 25, base_seed=base)

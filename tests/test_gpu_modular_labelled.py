@@ -17,10 +17,11 @@ import numpy as np
 import pytest
 
 from tests import replay
+from tests.rollout_checks import bits_equal, cus, guarded, inside, overflow_config, who_host
 from tests.test_gpu_labelled_rollout import hand_labels
-from tests.test_gpu_model_rollout import _cus, _state_equal
-from tests.test_gpu_modular_rollout import (BIG_TABLES_META, GEN_META, MODES, PRESS_SEED, SORT_SEED, TWIN_KEYS, _bits_equal, _dones,
-                                            _env, _guarded, _overflow_config, _pair)
+from tests.test_gpu_model_rollout import _state_equal
+from tests.test_gpu_modular_rollout import (BIG_TABLES_META, GEN_META, MODES, PRESS_SEED, SORT_SEED, TWIN_KEYS, _dones, _env, _pair,
+                                            _sizes)
 
 pytestmark = pytest.mark.gpu
 
@@ -29,13 +30,6 @@ ONE = 1 << 24
 LABEL_KEYS = ("sort_expert_actions", "press_expert_actions", "stepped_actions", "expert_stepped")
 PLAIN_KEYS = TWIN_KEYS + ("rewards_sort", "rewards_press")  # every member of mse_modular_buffers
 LAUNCHES = (5, 1, 4)
-
-
-def _who_host(env, n, off, t, threshold, mix_seed=MIX_SEED):
-    """mse_demo_who_steps_host -> u8[n]"""
-    out = np.zeros(n, dtype=np.uint8)
-    assert env.L.mse_demo_who_steps_host(n, off, mix_seed, t, threshold, C.c_void_p(out.ctypes.data)) == 0
-    return out
 
 
 def _labelled(cls, env, K, press_masked=True, beta=0.0, **kw):
@@ -68,7 +62,7 @@ def _compare_with_plain(tag, n, noise, press_masked, launches, **kw):
     for K in launches:
         t0 = a.policy_step
         got, exp = lab.collect(K), plain.collect(K)
-        _bits_equal(f"{tag} K={K}", got, exp, PLAIN_KEYS, K)
+        bits_equal(f"{tag} K={K}", got, exp, PLAIN_KEYS, K)
         _state_equal(f"{tag} K={K}", a, b)
         assert a.policy_step == t0 + K
         assert not bool(got["expert_stepped"][:K].any())
@@ -92,7 +86,7 @@ def test_labelled_at_beta_0_is_the_plain_rollout(n, noise, press_masked):
 @pytest.mark.parametrize("noise", [0.0, 0.05], ids=["n0", "n5"])
 def test_labelled_at_beta_0_is_the_plain_rollout_in_64_env_waves(noise):
     """256 x CUs + 1 envs: the smallest batch plan_policy_plain gives two tiles per wave."""
-    _compare_with_plain("tiles=2", 256 * _cus() + 1, noise, True, (2,))
+    _compare_with_plain("tiles=2", 256 * cus() + 1, noise, True, (2,))
 
 
 # ---- 2. fused == twin ------------------------------------------------------------------------------------------------------
@@ -110,13 +104,13 @@ def _compare_with_twin(tag, n, noise, press_masked, beta, launches, mode="sample
     for K in launches:
         t0 = a.policy_step
         got, exp = fused.collect(K, **MODES[mode]), twin.collect(K, **MODES[mode])
-        _bits_equal(f"{tag} K={K}", got, exp, keys, K)
+        bits_equal(f"{tag} K={K}", got, exp, keys, K)
         _state_equal(f"{tag} K={K}", a, b)
         assert a.policy_step == t0 + K
         _label_rows_consistent(got, K)
         who = got["expert_stepped"][:K].cpu().numpy()
         for k in range(K):
-            assert np.array_equal(who[k], _who_host(a, n, index_offset, t0 + k, threshold)), (tag, K, k)
+            assert np.array_equal(who[k], who_host(a, MIX_SEED, t0 + k, threshold)), (tag, K, k)
         shares.append(who)
         rows.append({key: got[key][:K].clone() for key in PLAIN_KEYS[:11] + LABEL_KEYS} | {"last_dones": got["last_dones"].clone()})
     a.close()
@@ -140,7 +134,7 @@ def test_labelled_rollout_matches_twin(n, noise, beta):
 def test_labelled_rollout_matches_twin_in_64_env_waves(noise, beta):
     """256 x CUs + 1 envs, two tiles per wave: the pair steps every env (beta 0, the label keys still against the twin), the
     mixture, and the label path on every step (beta 1)."""
-    share, _ = _compare_with_twin(f"tiles=2 beta={beta}", 256 * _cus() + 1, noise, True, beta, (2,))
+    share, _ = _compare_with_twin(f"tiles=2 beta={beta}", 256 * cus() + 1, noise, True, beta, (2,))
     if beta == 0.5:
         assert 0.45 < share < 0.55  # 131 074 draws at one half
     else:
@@ -217,7 +211,7 @@ def test_labels_in_long_episodes():
     assert len(np.unique(p)) >= 2
     assert forbidden.any()
     got = _labelled(M.FusedModularRollout, a, K, True, 0.5).collect()
-    _bits_equal("long episodes", got, exp, TWIN_KEYS + LABEL_KEYS, K)
+    bits_equal("long episodes", got, exp, TWIN_KEYS + LABEL_KEYS, K)
     _state_equal("long episodes", a, b)
     a.close()
     b.close()
@@ -241,7 +235,7 @@ def test_labelled_rollout_on_a_shard():
 @pytest.mark.parametrize("mode", [m for m in MODES if m != "sampled"])
 @pytest.mark.parametrize("noise", [0.0, 0.05], ids=["n0", "n5"])
 def test_labelled_rollout_modes_match_twin(noise, mode):
-    kw = dict(config=_overflow_config(noise)) if mode == "overflow" else {}
+    kw = dict(config=overflow_config(noise)) if mode == "overflow" else {}
     share, rows = _compare_with_twin(f"noise={noise} {mode}", 257, noise, True, 0.5, LAUNCHES, mode=mode, **kw)
     assert 0.0 < share < 1.0
     if mode == "overflow":
@@ -266,26 +260,8 @@ def _raw_call(env, sort_ag, press_ag, K, flags, ptrs, lptrs, sort_seed=SORT_SEED
                                               None if no_labels else C.byref(labels), None)
 
 
-def _guarded_labels(n, K):
-    """The four label outputs inside one byte tensor, 64 guard bytes (0xA5) around each -> (raw, {name: (offset, bytes)})."""
-    import torch
-
-    sizes = {"sort_expert_actions": K * n * 4, "press_expert_actions": K * n * 4, "stepped_actions": K * n * 4,
-             "expert_stepped": K * n}
-    at, off = {}, 64
-    for name, size in sizes.items():
-        at[name] = (off, size)
-        off += (size + 15) // 16 * 16 + 64
-    return torch.full((off,), 0xA5, dtype=torch.uint8, device="cuda:0"), at
-
-
-def _inside(raw, at, rows=None):
-    import torch
-
-    inside = torch.zeros(raw.numel(), dtype=torch.bool, device=raw.device)
-    for name, (off, size) in at.items():
-        inside[off:off + (size if rows is None else rows(name, size))] = True
-    return inside
+def _label_sizes(n, K):
+    return {"sort_expert_actions": K * n * 4, "press_expert_actions": K * n * 4, "stepped_actions": K * n * 4, "expert_stepped": K * n}
 
 
 def test_labelled_rollout_memory():
@@ -297,21 +273,21 @@ def test_labelled_rollout_memory():
     sort_ag, press_ag = _pair()
     env = _env(n, 0.05, base_seed=9)
     rng_before = env.get_state()[2].clone()
-    raw, at = _guarded(n, K)
-    lraw, lat = _guarded_labels(n, K)
+    raw, at = guarded(_sizes(n, K))
+    lraw, lat = guarded(_label_sizes(n, K))
     ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
     lptrs = {name: lraw.data_ptr() + off for name, (off, _) in lat.items()}
     # K - 1 steps into buffers of K rows: the last row of every [K, N, ...] buffer stays untouched, like the guards
     per_env = ("sort_last_values", "press_last_values", "last_dones")
     assert _raw_call(env, sort_ag, press_ag, K - 1, 64, ptrs, lptrs) == 0
     torch.cuda.synchronize()
-    short = _inside(raw, at, lambda name, size: size if name in per_env else size // K * (K - 1))
-    lshort = _inside(lraw, lat, lambda name, size: size // K * (K - 1))
+    short = inside(raw, at, lambda name, size: size if name in per_env else size // K * (K - 1))
+    lshort = inside(lraw, lat, lambda name, size: size // K * (K - 1))
     assert bool((raw[~short] == 0xA5).all()) and bool((lraw[~lshort] == 0xA5).all()), "a byte past the first K - 1 rows was written"
     assert _raw_call(env, sort_ag, press_ag, K, 64, ptrs, lptrs) == 0
     torch.cuda.synchronize()
-    inside, linside = _inside(raw, at), _inside(lraw, lat)
-    assert bool((raw[~inside] == 0xA5).all()) and bool((lraw[~linside] == 0xA5).all()), "a guard byte was written"
+    within, lwithin = inside(raw, at), inside(lraw, lat)
+    assert bool((raw[~within] == 0xA5).all()) and bool((lraw[~lwithin] == 0xA5).all()), "a guard byte was written"
     # rng_sorting (words 18-23) and rng_pressing (words 12-17) are not touched, whoever steps
     assert torch.equal(rng_before[:, 12:24], env.get_state()[2][:, 12:24])
     # every output NULL, then one at a time with the others as they were
@@ -359,8 +335,8 @@ def test_labelled_rollout_refusals():
 
     try:
         env = keep(_env(n, 0.05))
-        raw, at = _guarded(n, K)
-        lraw, lat = _guarded_labels(n, K)
+        raw, at = guarded(_sizes(n, K))
+        lraw, lat = guarded(_label_sizes(n, K))
         ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
         lptrs = {name: lraw.data_ptr() + off for name, (off, _) in lat.items()}
         assert _check_call(env, sort_ag, press_ag, K) == 0 and env.policy_step == 0  # the check launches nothing
@@ -406,7 +382,7 @@ def test_labelled_rollout_refusals():
         big_cfg = replay.sorting_config(BIG_TABLES_META)
         small_big = keep(_env(n, 0.05, config=big_cfg))
         assert _check_call(small_big, sort_ag, press_ag, K) == 0
-        big = keep(_env(256 * _cus() + 1, 0.05, config=big_cfg))
+        big = keep(_env(256 * cus() + 1, 0.05, config=big_cfg))
         refused(UNSUPPORTED, e=big, message=b"LDS image does not fit")
         # an earlier refusal wins over a later one: the plain kernel's before the threshold's, the threshold's before the seed's
         refused(INVALID, k=0, threshold=ONE + 1, message=b"k_steps")

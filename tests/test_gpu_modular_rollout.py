@@ -20,8 +20,9 @@ from oracle.oracle import OracleEnv
 from tests import policy_head_reference as R
 from tests import policy_stream as ps
 from tests import replay
+from tests.rollout_checks import OVERFLOW_OVERRIDES, bits_equal, cus, guarded, inside, overflow_config
 from tests.test_gpu_full_size_oracle import _check_reward, _same
-from tests.test_gpu_model_rollout import _agents, _cus, _state_equal
+from tests.test_gpu_model_rollout import _agents, _state_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -34,13 +35,7 @@ TWIN_KEYS = ("sort_obs", "press_obs", "press_masks", "episode_starts", "sort_act
 TRACE_R_SORT, TRACE_R_PRESS, TRACE_REWARD, TRACE_OVERFLOW = 1, 2, 32, 37
 # at this capacity (config.yml: 700) a container overflows in the third step of every episode the CPU oracle was
 # tried on, whatever the actions
-OVERFLOW_META = dict(kind="mono", max_steps=MAX_STEPS, noise_sorting=0.0, balesize=200,
-                     config_overrides={"pressing_station": {"container_capacity": 30}})
-
-
-def _overflow_config(noise):
-    """OVERFLOW_META's config with the sorting noise a test runs at written into it."""
-    return replay.sorting_config(dict(OVERFLOW_META, noise_sorting=noise)).with_overrides({"sorting_station": {"noise": noise}})
+OVERFLOW_META = dict(kind="mono", max_steps=MAX_STEPS, noise_sorting=0.0, balesize=200, config_overrides=OVERFLOW_OVERRIDES)
 
 
 def _env(n, noise, base_seed=0, **kw):
@@ -59,20 +54,6 @@ def _pair(seed=0, head_gain=20.0):
     (no test changes their weights)."""
     sort_ag, press_ag, _ = _agents("both_maskable", seed=seed, head_gain=head_gain)
     return sort_ag, press_ag
-
-
-def _bits_equal(tag, got, exp, keys, K):
-    import torch
-
-    for key in keys:
-        x, y = got[key], exp[key]
-        if x.dim() > 1:
-            x, y = x[:K], y[:K]
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        if not torch.equal(x, y):
-            bad = torch.nonzero((x != y).reshape(x.shape[0], -1).any(dim=1) if x.dim() == 1 else (x != y).reshape(K, x.shape[1], -1).any(dim=2))
-            raise AssertionError(f"{tag}: {key} differs at {bad.shape[0]} rows, first {bad[0].tolist()}")
 
 
 def _dones(b, K):
@@ -119,7 +100,7 @@ def _compare_with_twin(tag, n, noise, press_masked, mode, launches, config=None,
     for K in launches:
         t0 = a.policy_step
         got, exp = fused.collect(K, **MODES[mode]), twin.collect(K, **MODES[mode])
-        _bits_equal(f"{tag} K={K}", got, exp, TWIN_KEYS, K)
+        bits_equal(f"{tag} K={K}", got, exp, TWIN_KEYS, K)
         _state_equal(f"{tag} K={K}", a, b)
         assert a.policy_step == t0 + K
         dones = _dones(got, K)
@@ -137,7 +118,7 @@ def _compare_with_twin(tag, n, noise, press_masked, mode, launches, config=None,
 def test_fused_modular_rollout_matches_twin(n, noise, press_masked, mode):
     """A lone lane, a ragged second tile, a second workgroup with one env; launches of 5, 1 and 4 steps on the same
     handles."""
-    config = _overflow_config(noise) if mode == "overflow" else None
+    config = overflow_config(noise) if mode == "overflow" else None
     n_done, n_early = _compare_with_twin(f"n={n} noise={noise} masked={press_masked} {mode}", n, noise, press_masked, mode,
                                          (5, 1, 4), config=config)
     assert n_done >= 2 * n
@@ -150,7 +131,7 @@ def test_fused_modular_rollout_matches_twin(n, noise, press_masked, mode):
 # ---- 2. the second wave shape ----------------------------------------------------------------------------------------
 def test_fused_modular_rollout_matches_twin_in_64_env_waves():
     """256 x CUs + 1 envs: the smallest batch plan_policy_plain gives two tiles per wave."""
-    _compare_with_twin("tiles=2", 256 * _cus() + 1, 0.05, True, "sampled", (2,))
+    _compare_with_twin("tiles=2", 256 * cus() + 1, 0.05, True, "sampled", (2,))
 
 
 # ---- 3. the oracle ---------------------------------------------------------------------------------------------------
@@ -192,7 +173,7 @@ def test_fused_modular_rollout_overflow_parts_match_oracle():
 
     n, K, base = 33, 6, 40
     sort_ag, press_ag = _pair()
-    env = _env(n, 0.0, base_seed=base, config=_overflow_config(0.0))
+    env = _env(n, 0.0, base_seed=base, config=overflow_config(0.0))
     orcs = [OracleEnv(kind="mono", seed=base + i, cfg=replay.oracle_config(OVERFLOW_META)) for i in range(n)]
     for i, o in enumerate(orcs):
         o.reset(base + i)
@@ -357,20 +338,11 @@ def _raw_call(env, sort_ag, press_ag, K, flags, ptrs, sort_seed=SORT_SEED, press
                                      C.byref(out), None)
 
 
-def _guarded(n, K):
-    """Every output inside one byte tensor, 64 guard bytes (0xA5) before and after each -> (raw, {name: (offset, bytes)})."""
-    import torch
-
-    sizes = {"sort_obs": K * n * 13 * 4, "press_obs": K * n * 16 * 4, "press_masks": K * n * 11, "episode_starts": K * n,
-             "sort_actions": K * n * 4, "press_actions": K * n * 4, "sort_log_probs": K * n * 4, "press_log_probs": K * n * 4,
-             "sort_values": K * n * 4, "press_values": K * n * 4, "rewards": K * n * 4, "rewards_sort": K * n * 4,
-             "rewards_press": K * n * 4, "sort_last_values": n * 4, "press_last_values": n * 4, "last_dones": n}
-    at, off = {}, 64
-    for name, size in sizes.items():
-        at[name] = (off, size)
-        off += (size + 15) // 16 * 16 + 64
-    raw = torch.full((off,), 0xA5, dtype=torch.uint8, device="cuda:0")
-    return raw, at
+def _sizes(n, K):
+    return {"sort_obs": K * n * 13 * 4, "press_obs": K * n * 16 * 4, "press_masks": K * n * 11, "episode_starts": K * n,
+            "sort_actions": K * n * 4, "press_actions": K * n * 4, "sort_log_probs": K * n * 4, "press_log_probs": K * n * 4,
+            "sort_values": K * n * 4, "press_values": K * n * 4, "rewards": K * n * 4, "rewards_sort": K * n * 4,
+            "rewards_press": K * n * 4, "sort_last_values": n * 4, "press_last_values": n * 4, "last_dones": n}
 
 
 def test_fused_modular_rollout_memory():
@@ -382,14 +354,12 @@ def test_fused_modular_rollout_memory():
     sort_ag, press_ag = _pair()
     env = _env(n, 0.05, base_seed=9)
     rng_before = env.get_state()[2].clone()
-    raw, at = _guarded(n, K)
+    raw, at = guarded(_sizes(n, K))
     ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
     assert _raw_call(env, sort_ag, press_ag, K, 64, ptrs) == 0
     torch.cuda.synchronize()
-    inside = torch.zeros(raw.numel(), dtype=torch.bool, device=raw.device)
-    for name, (off, size) in at.items():
-        inside[off:off + size] = True
-    assert bool((raw[~inside] == 0xA5).all()), "a guard byte was written"
+    within = inside(raw, at)
+    assert bool((raw[~within] == 0xA5).all()), "a guard byte was written"
     # rng_sorting (words 18-23) and rng_pressing (words 12-17) are not touched: there are no fallback draws
     rng_after = env.get_state()[2]
     assert torch.equal(rng_before[:, 12:24], rng_after[:, 12:24])
@@ -398,7 +368,7 @@ def test_fused_modular_rollout_memory():
     for name in MODULAR_BUFFER_NAMES:
         assert _raw_call(env, sort_ag, press_ag, 1, 64, {name: ptrs[name]}) == 0, name
     torch.cuda.synchronize()
-    assert bool((raw[~inside] == 0xA5).all())
+    assert bool((raw[~within] == 0xA5).all())
     assert env.policy_step == K + K + len(MODULAR_BUFFER_NAMES) and env.error_count() == 0
     env.close()
 
@@ -434,7 +404,7 @@ def test_fused_modular_rollout_refusals():
 
     try:
         env = keep(_env(n, 0.05))
-        raw, at = _guarded(n, K)
+        raw, at = guarded(_sizes(n, K))
         ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
         assert _check_call(env, sort_ag, press_ag, K) == 0 and env.policy_step == 0  # the check launches nothing
         assert _raw_call(env, sort_ag, press_ag, K, 0, ptrs) == 0
@@ -491,7 +461,7 @@ def test_fused_modular_rollout_refusals():
         assert _raw_call(small_big, sort_ag, press_ag, K, 0, ptrs) == 0
         torch.cuda.synchronize()
         filled = raw.clone()
-        big = keep(_env(256 * _cus() + 1, 0.05, config=big_cfg))
+        big = keep(_env(256 * cus() + 1, 0.05, config=big_cfg))
         big_state = [x.clone() for x in big.get_state()]
         refused(UNSUPPORTED, e=big)
         assert b"LDS image does not fit" in big.L.mse_last_error()
@@ -543,12 +513,12 @@ def test_twin_reads_episode_starts_off_the_state():
     twin = M.ModularRolloutCollector(b, sort_ag, press_ag, K, SORT_SEED, PRESS_SEED)  # ... when the twin first sees it
     got, exp = fused.collect(), twin.collect()
     assert not bool(exp["episode_starts"][0].any()) and bool(exp["episode_starts"][1:].any())
-    _bits_equal("stepped handle", got, exp, TWIN_KEYS, K)
+    bits_equal("stepped handle", got, exp, TWIN_KEYS, K)
     sd = twin.state_dict()
     assert sd["collector"] == "modular_twin" and "last_done" not in sd
     other = M.ModularRolloutCollector(c, sort_ag, press_ag, K, SORT_SEED, PRESS_SEED)
     other.load_state_dict(sd)
-    _bits_equal("restored handle", fused.collect(), other.collect(), TWIN_KEYS, K)
+    bits_equal("restored handle", fused.collect(), other.collect(), TWIN_KEYS, K)
     _state_equal("restored handle", a, c)
     for e in (a, b, c):
         e.close()

@@ -5,8 +5,9 @@ Then the collector's checkpoint surface (the key `view`) and every constructor r
 import numpy as np
 import pytest
 
+from tests.rollout_checks import bits_equal, who_host
 from tests.test_gpu_demo_rollout import _actor
-from tests.test_gpu_preview_rollout import MIX_SEED, SEED, _bits_equal, _env, _who_host
+from tests.test_gpu_preview_rollout import MIX_SEED, SEED, _env
 
 pytestmark = pytest.mark.gpu
 
@@ -77,7 +78,7 @@ class _HandPreviewDemo:
             obs, mask = c._view()
             rule = env.rule_actions()
             a = self.actor.forward(obs, mask, seed=SEED, t=t, index_offset=env.index_offset)["action"]
-            who = torch.from_numpy(_who_host(env, t, threshold)).to(env.device)
+            who = torch.from_numpy(who_host(env, MIX_SEED, t, threshold)).to(env.device)
             b["observations"][k].copy_(obs)
             b["action_masks"][k].copy_(mask)
             b["episode_starts"][k].copy_(c._last_done)
@@ -135,7 +136,7 @@ def test_fused_preview_demo_at_the_ends_is_the_demonstration_collector(beta):
     for launch in range(2):
         got, exp = fused.collect(), twin.collect()
         assert set(got) == set(exp) | {"expert_stepped"}
-        _bits_equal(f"beta={beta} launch {launch}", got, exp, tuple(exp))
+        bits_equal(f"beta={beta} launch {launch}", got, exp, tuple(exp))
         assert bool((got["expert_stepped"] == int(beta)).all())
         assert got["observations"].shape == (K, N, 29) and got["action_masks"].shape == (K, N, 22)
         for x, y in zip(a.get_state(), b.get_state()):
@@ -203,7 +204,7 @@ def test_checkpoint_round_trip_and_view_mismatch():
         assert sd["view"] == "preview" and sd["collector"] == cls.KIND
         two = cls(b, pol, K, seed=SEED, view="preview")
         two.load_state_dict(sd)
-        _bits_equal(f"{cls.__name__} resumed", one.collect(), two.collect(),
+        bits_equal(f"{cls.__name__} resumed", one.collect(), two.collect(),
                     ("observations", "action_masks", "actions", "log_probs", "values", "rewards", "episode_starts", "last_values",
                      "last_dones"))
         own = cls(c, pol, K, seed=SEED)

@@ -17,11 +17,11 @@ import pytest
 
 from oracle.oracle import OracleEnv
 from tests import policy_head_reference as R
-from tests import replay
+from tests.rollout_checks import bits_equal, cus, guarded, inside, overflow_config, who_host
 from tests.test_demo_mixture_cpu import who_steps
 from tests.test_gpu_demo_rollout import BIG_TABLES, GEN, _actor
 from tests.test_gpu_full_size_oracle import _check_reward, _same
-from tests.test_gpu_model_rollout import _cus, _final_state, _state_equal
+from tests.test_gpu_model_rollout import _final_state, _state_equal
 from tests.test_gpu_modular_rollout import _w64
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +35,6 @@ LABEL_KEYS = ("expert_actions", "stepped_actions", "expert_stepped")
 COLLECTOR_KEYS = ("observations", "action_masks", "actions", "log_probs", "values", "rewards", "episode_starts", "expert_actions",
                   "last_values", "last_dones")
 SNAP_CURRENT_STEP = 32  # column of mse_get_state's integer record that holds the env's current_step
-OVERFLOW_OVERRIDES = {"pressing_station": {"container_capacity": 30}}  # a container overflows inside a short episode
 
 
 def _env(n, noise=0.05, max_steps=MAX_STEPS, base_seed=11, **kw):
@@ -44,10 +43,6 @@ def _env(n, noise=0.05, max_steps=MAX_STEPS, base_seed=11, **kw):
     kw.setdefault("auto_reset", True)
     return M.BatchedSortingEnv(kind="mono", num_envs=n, device=0, base_seed=base_seed, max_steps=max_steps,
                                noise_sorting=noise, balesize=200, **kw)
-
-
-def _overflow_config(noise):
-    return replay.sorting_config(dict(config_overrides=OVERFLOW_OVERRIDES)).with_overrides({"sorting_station": {"noise": noise}})
 
 
 def _buffers(n, K, names=KEYS):
@@ -83,12 +78,6 @@ def fused(env, pol, K, threshold=0, flags=0, names=KEYS):
     return b
 
 
-def _who_host(env, t, threshold):
-    out = np.zeros(env.num_envs, dtype=np.uint8)
-    assert env.L.mse_demo_who_steps_host(env.num_envs, env.index_offset, MIX_SEED, t, threshold, C.c_void_p(out.ctypes.data)) == 0
-    return out
-
-
 def hand_collect(env, pol, K, threshold=0, deterministic=False, check_overflow=False):
     """The header's sentence: K rounds of mse_mono_agent_obs, the mask read, mse_rule_actions, mse_policy_forward (SEED, t =
     the handle's counter, index_offset = the env's), the host who-steps rule, mse_step; then the critic on the preview of the
@@ -102,7 +91,7 @@ def hand_collect(env, pol, K, threshold=0, deterministic=False, check_overflow=F
         obs, mask = env.mono_agent_obs(), env.action_masks()
         rule = env.rule_actions()
         out = pol.forward(obs, mask, seed=SEED, t=t, deterministic=deterministic, index_offset=env.index_offset)
-        who = torch.from_numpy(_who_host(env, t, threshold)).to(env.device)
+        who = torch.from_numpy(who_host(env, MIX_SEED, t, threshold)).to(env.device)
         stepped = torch.where(who != 0, rule, out["action"])
         for key, v in (("observations", obs), ("action_masks", mask), ("episode_starts", last_done), ("actions", out["action"]),
                        ("log_probs", out["logp"]), ("values", out["value"]), ("expert_actions", rule), ("stepped_actions", stepped),
@@ -115,21 +104,6 @@ def hand_collect(env, pol, K, threshold=0, deterministic=False, check_overflow=F
                                        index_offset=env.index_offset)["value"])
     b["last_dones"].copy_(last_done)
     return b
-
-
-def _bits_equal(tag, got, exp, keys, K=None):
-    import torch
-
-    for key in keys:
-        x, y = got[key], exp[key]
-        if K is not None and x.dim() > 1:
-            x, y = x[:K], y[:K]
-        assert x.shape == y.shape and x.dtype == y.dtype, (tag, key)
-        if x.dtype == torch.float32:
-            x, y = x.view(torch.int32), y.view(torch.int32)
-        if not torch.equal(x, y):
-            bad = torch.nonzero((x != y).reshape(-1))
-            raise AssertionError(f"{tag}: {key} differs at {bad.shape[0]} elements, first flat index {int(bad[0])}")
 
 
 def _n_done(b):
@@ -147,11 +121,11 @@ def _compare_all(tag, n, noise, K, precision="f16x3", deterministic=False, **kw)
     col = M.FusedPolicyRollout(a, pol, K, seed=SEED, view="preview", expert_labels=True)
     twin = M.PolicyRolloutCollector(b, pol, K, seed=SEED, view="preview", expert_labels=True)
     got, exp = col.collect(deterministic=deterministic), twin.collect(deterministic=deterministic)
-    _bits_equal(f"{tag} twin", got, exp, COLLECTOR_KEYS)
+    bits_equal(f"{tag} twin", got, exp, COLLECTOR_KEYS)
     raw = fused(c, pol, K, 0, DETERMINISTIC if deterministic else 0)
     hand = hand_collect(d, pol, K, 0, deterministic)
-    _bits_equal(f"{tag} hand", raw, hand, KEYS)
-    _bits_equal(f"{tag} collector vs raw", got, raw, COLLECTOR_KEYS)
+    bits_equal(f"{tag} hand", raw, hand, KEYS)
+    bits_equal(f"{tag} collector vs raw", got, raw, COLLECTOR_KEYS)
     for other, name in ((b, "twin"), (c, "raw"), (d, "hand")):
         _state_equal(f"{tag} {name}", a, other)
     assert a.policy_step == K and a.error_count() == 0
@@ -179,7 +153,7 @@ def test_preview_rollout_matches_twin_and_hand_loop(n, noise):
 @pytest.mark.parametrize("noise", [0.0, 0.05], ids=["n0", "n5"])
 def test_preview_rollout_in_64_env_waves(noise):
     """256 x CUs + 1 envs: the smallest batch plan_policy_plain gives two tiles per wave in the f16x3 form."""
-    _compare_all("tiles=2", 256 * _cus() + 1, noise, 3)
+    _compare_all("tiles=2", 256 * cus() + 1, noise, 3)
 
 
 @pytest.mark.parametrize("noise", [0.0, 0.05], ids=["n0", "n5"])
@@ -217,11 +191,11 @@ def test_preview_mixture_matches_the_hand_loop(n, beta):
     t = 0
     for K in (5, 1, K17):
         got, exp = fused(a, pol, K, threshold), hand_collect(b, pol, K, threshold)
-        _bits_equal(f"n={n} beta={beta} K={K}", got, exp, KEYS)
+        bits_equal(f"n={n} beta={beta} K={K}", got, exp, KEYS)
         _state_equal(f"n={n} beta={beta} K={K}", a, b)
         who = got["expert_stepped"].cpu().numpy()
         for k in range(K):  # the library's host rule, and the numpy restatement of it
-            assert np.array_equal(who[k], _who_host(a, t + k, threshold)), (K, k)
+            assert np.array_equal(who[k], who_host(a, MIX_SEED, t + k, threshold)), (K, k)
             assert np.array_equal(who[k], who_steps(n, 0, MIX_SEED, t + k, threshold)), (K, k)
         es = got["expert_stepped"] != 0
         assert torch.equal(got["stepped_actions"], torch.where(es, got["expert_actions"], got["actions"]))
@@ -256,11 +230,11 @@ def test_preview_rollout_check_overflow(noise):
 
     pen = np.float32(SortingEnvConfig().overflow_termination_penalty)
     pol, n = _actor("mono"), 257
-    cfg = _overflow_config(noise)
+    cfg = overflow_config(noise)
     a, b = _env(n, noise, config=cfg), _env(n, noise, config=cfg)
     got = fused(a, pol, K17, 1 << 23, CHECK_OVERFLOW)
     exp = hand_collect(b, pol, K17, 1 << 23, check_overflow=True)
-    _bits_equal(f"overflow noise={noise}", got, exp, KEYS)
+    bits_equal(f"overflow noise={noise}", got, exp, KEYS)
     _state_equal(f"overflow noise={noise}", a, b)
     assert int((got["rewards"] == float(pen)).sum()) >= 1, "no episode ended by overflow"
     a.close()
@@ -322,7 +296,7 @@ def test_contract_b_label_pointers_change_nothing_at_threshold_0(n):
     plain_keys = tuple(k for k in KEYS if k not in LABEL_KEYS)
     for K in (5, K17):
         with_labels, without = fused(a, pol, K), fused(b, pol, K, names=plain_keys)
-        _bits_equal(f"n={n} K={K}", with_labels, without, plain_keys)
+        bits_equal(f"n={n} K={K}", with_labels, without, plain_keys)
         _state_equal(f"n={n} K={K}", a, b)
     assert a.policy_step == b.policy_step == 22
     a.close()
@@ -348,28 +322,12 @@ def test_contract_c_threshold_one_is_the_rule_based_rollout(noise):
 
 
 # ---- 5. memory -----------------------------------------------------------------------------------------------------------------
-def _guarded(n, K):
-    """Every output inside one byte tensor, 64 guard bytes (0xA5) before and after each -> (raw, {name: (offset, bytes)})."""
-    import torch
-
+def _sizes(n, K):
     sizes = {"observations": K * n * 29 * 4, "action_masks": K * n * 22, "episode_starts": K * n, "actions": K * n * 4,
              "log_probs": K * n * 4, "values": K * n * 4, "rewards": K * n * 4, "expert_actions": K * n * 4,
              "stepped_actions": K * n * 4, "expert_stepped": K * n, "last_values": n * 4, "last_dones": n}
     assert tuple(sizes) == KEYS
-    at, off = {}, 64
-    for name, size in sizes.items():
-        at[name] = (off, size)
-        off += (size + 15) // 16 * 16 + 64
-    return torch.full((off,), 0xA5, dtype=torch.uint8, device="cuda:0"), at
-
-
-def _inside(raw, at, rows=None):
-    import torch
-
-    inside = torch.zeros(raw.numel(), dtype=torch.bool, device=raw.device)
-    for name, (off, size) in at.items():
-        inside[off:off + (size if rows is None else rows(name, size))] = True
-    return inside
+    return sizes
 
 
 @pytest.mark.parametrize("n", [97, 65])
@@ -381,18 +339,18 @@ def test_preview_rollout_memory(n):
     pol = _actor("mono", "f16x3" if n == 97 else "f32")
     env = _env(n, base_seed=9, max_steps=3)
     rng_before = env.get_state()[2].clone()
-    raw, at = _guarded(n, K)
+    raw, at = guarded(_sizes(n, K))
     ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
     per_env = ("last_values", "last_dones")
     # K - 1 steps into buffers of K rows: the last row of every [K, N, ...] buffer stays untouched, like the guards
     assert _launch(env, pol, K - 1, ptrs, 1 << 23) == 0
     torch.cuda.synchronize()
-    short = _inside(raw, at, lambda name, size: size if name in per_env else size // K * (K - 1))
+    short = inside(raw, at, lambda name, size: size if name in per_env else size // K * (K - 1))
     assert bool((raw[~short] == 0xA5).all()), "a byte past the first K - 1 rows was written"
     assert _launch(env, pol, K, ptrs, 1 << 23) == 0
     torch.cuda.synchronize()
-    inside = _inside(raw, at)
-    assert bool((raw[~inside] == 0xA5).all()), "a guard byte was written"
+    within = inside(raw, at)
+    assert bool((raw[~within] == 0xA5).all()), "a guard byte was written"
     # rng_pressing (words 12-17) and rng_sorting (words 18-23) are neither read nor written, whoever steps
     assert torch.equal(rng_before[:, 12:24], env.get_state()[2][:, 12:24])
     # every output NULL, then each output NULL in turn with the others given: the others hold what a twin launch with every
@@ -413,7 +371,7 @@ def test_preview_rollout_memory(n):
                 o2, s2 = at[other]
                 rows = s2 if other in per_env else s2 // K * 2
                 assert torch.equal(raw[o2:o2 + rows], exp[other].reshape(-1).view(torch.uint8)), (name, other)
-        assert bool((raw[~inside] == 0xA5).all())
+        assert bool((raw[~within] == 0xA5).all())
         _state_equal(name, env, twin)
     assert torch.equal(rng_before[:, 12:24], env.get_state()[2][:, 12:24])
     assert env.policy_step == (K - 1) + K + K + 2 * len(KEYS) and env.error_count() == 0
@@ -440,7 +398,7 @@ def test_preview_rollout_refusals():
 
     try:
         env = keep(_env(n))
-        raw, at = _guarded(n, K)
+        raw, at = guarded(_sizes(n, K))
         ptrs = {name: raw.data_ptr() + off for name, (off, _) in at.items()}
         assert _check_call(env, pol, K) == 0 and env.policy_step == 0  # the check launches nothing
         assert _launch(env, pol, K, ptrs) == 0
@@ -514,7 +472,7 @@ def test_preview_rollout_refusals():
         big_cfg = M.SortingEnvConfig().with_overrides(BIG_TABLES)
         small_big = keep(_env(n, config=big_cfg))
         assert _check_call(small_big, pol, K) == 0
-        big = keep(_env(256 * _cus() + 1, config=big_cfg))
+        big = keep(_env(256 * cus() + 1, config=big_cfg))
         big_state = [x.clone() for x in big.get_state()]
         big_bufs = _buffers(big.num_envs, K, ("rewards", "last_dones"))
         assert _check_call(big, pol, K) == UNSUPPORTED and b"LDS image does not fit" in big.L.mse_last_error()
@@ -530,7 +488,7 @@ def test_preview_rollout_refusals():
         assert _check_call(env, pol, K, ONE, CHECK_OVERFLOW | DETERMINISTIC) == 0
         # the served big-table handle gives the hand loop's rows
         hand = hand_collect(keep(_env(n, config=big_cfg)), pol, K)
-        _bits_equal("big tables, 32-env waves", fused(small_big, pol, K), hand, KEYS)
+        bits_equal("big tables, 32-env waves", fused(small_big, pol, K), hand, KEYS)
     finally:
         for e in opened:
             e.close()
