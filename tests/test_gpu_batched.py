@@ -182,7 +182,7 @@ def test_pipelined_rollout_equals_single_role_rollout(kind, noise, pipeline):
     kw = dict(base_seed=321, max_steps=20, noise_sorting=noise, balesize=200, auto_reset=True)
     a = _mk(kind, n, rollout_pipeline=pipeline, **kw)
     b = _mk(kind, n, rollout_pipeline=2, **kw)
-    sm = (torch.arange(n, dtype=torch.int32, device="cuda") % 3 - 1) if kind == "press" else None  # -1 = rule
+    sm = (torch.arange(n, dtype=torch.int32, device="cuda") % 4 - 1) if kind == "press" else None  # -1 = rule, 2 = no boost
     for chunk, ovf in ((K, False), (7, True), (1, False), (16, False)):
         ra = a.rollout(chunk, policy_seed=11, sort_mode=sm, check_overflow=ovf)
         rb = b.rollout(chunk, policy_seed=11, sort_mode=sm, check_overflow=ovf)
