@@ -734,6 +734,78 @@ int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev
                             int32_t *control_dev /* NULL: no gate */, int arithmetic /* 0 fma, 1 matrix */,
                             const float *old_values /* f32[n_rows] or NULL */, double clip_range_vf);
 
+/* mse_ppo_loss_grad_vclip for ONE minibatch whose rows live in several places ("shards": the ranks of a data-parallel
+ * learner, each with the rollout rows it collected).  The call is cut at the two points where the other shards' numbers
+ * enter, and what crosses is small: four doubles, then mse_ppo_shard_partial_len(D, A) doubles.  Per minibatch every shard runs
+ *   1. mse_ppo_shard_moments      -> moments_out; the caller SUMS the shards' moments element-wise (an all-reduce)
+ *   2. mse_ppo_shard_loss_grad    on the summed moments -> partial_out; the caller SUMS the shards' partials element-wise
+ *   3. mse_ppo_shard_finish       on the summed partial and the summed moments -> grad_out, stats_out, the target_kl gate
+ * then mse_ppo_adam_step[_gated], unchanged.  Every shard that is given the same sums computes the same bits in step 3 and so
+ * takes the same decision.  The PPO head only (either arithmetic, with or without old_values); the behaviour-cloning and
+ * imitation-term losses have no sharded form.  As everywhere here: caller-owned device memory, all work on `stream`, nothing
+ * allocates or synchronises, every argument is checked before any device call, no atomics and fixed orders, so equal inputs give
+ * bit-equal outputs.  The result is NOT independent of how the rows are cut into shards: the sums are formed in another
+ * order, so two splits of the same rows agree within rounding, as the two arithmetics do.
+ *
+ * mse_ppo_shard_moments: n_rows, rows_dev, advantages are mse_ppo_loss_grad's, with its clamping of row indices (row_at).
+ *   batch_local  >= 0 rows of this shard in the minibatch; 0 is legal: zeros are written and no row is read (rows_dev, which
+ *                is otherwise i64[batch_local] or NULL for rows 0 .. batch_local - 1, may then be NULL)
+ *   moments_out  f64[4], 8-byte aligned: {batch_local, sum a, sum a^2, 0} over this shard's rows a = advantages[row], in
+ *                double: lanes add their rows in order, a fixed tree inside a group of 256 lanes, the min(256, ceil(batch_local
+ *                / 1024)) groups' pairs (in the workspace) added in index order by one lane
+ *   workspace    mse_ppo_workspace_bytes(D, A) bytes of any D, A (4 KiB are used), 16-byte aligned
+ *   control_dev  i32[2] or NULL, mse_ppo_loss_grad_gated's block: with stopped != 0 on entry nothing is written
+ * The rule the sums serve, B being the global row count: mean = sum a / B; unbiased variance = (sum a^2 - (sum a)^2 / B) /
+ * (B - 1), in double, clamped at 0; std = sqrt(variance); mean and std rounded to float32 once; a row's advantage becomes
+ * (a - mean) / (std + 1e-8) in float32, as in mse_ppo_loss_grad.
+ * Checks, in this order: null advantages, moments_out or workspace; n_rows < 1, batch_local < 0 or batch_local > n_rows
+ * without rows_dev; workspace not 16-byte aligned, then moments_out not 8-byte aligned (MSE_ERR_ALIGNMENT); no device
+ * (MSE_ERR_NO_DEVICE).  The others are MSE_ERR_INVALID_ARGUMENT.
+ *
+ * mse_ppo_shard_loss_grad: the first 13 arguments are mse_ppo_loss_grad's, `batch` being batch_local >= 0.
+ *   global_batch B >= max(1, batch_local): the rows of the minibatch over all shards.  Every per-row term is scaled by 1 / B
+ *                where mse_ppo_loss_grad scales by 1 / batch
+ *   moments_dev  f64[4], device memory, 8-byte aligned: the SUM of all shards' moments_out.  Advantages are normalised by the
+ *                rule above when normalize_advantage != 0 and B >= 2 (mse_ppo_loss_grad's rule on the global count)
+ *   partial_out  f64[mse_ppo_shard_partial_len(D, A)], 8-byte aligned, in DOUBLE: the W gradient sums in the flat order,
+ *                then the five statistic sums of the gradient kernels' slabs, not divided (surrogate, squared value error,
+ *                entropy, kl, clipped), then zeros up to a multiple of 4.  Each is the sum of the shard's slabs in slab order
+ *   workspace    mse_ppo_workspace_bytes(D, A) bytes, 16-byte aligned
+ *   control_dev  i32[2] or NULL: with stopped != 0 on entry partial_out is not written (the workspace gets one marker cell)
+ *   arithmetic, old_values, clip_range_vf   mse_ppo_loss_grad_vclip's
+ * Two launches: the SHARD instantiation of the gradient kernel of either arithmetic (the grid rule is mse_ppo_loss_grad's on
+ * batch_local), then the slab sums.  batch_local = 0 launches no gradient kernel and writes zeros.
+ * Checks, in this order: null arguments (rows_dev, mask, control_dev and old_values may be NULL); dimensions outside 1..32;
+ * struct_size; n_rows < 1, batch_local < 0 or batch_local > n_rows without rows_dev; global_batch < max(1, batch_local);
+ * clip_range / ent_coef / vf_coef; workspace not 16-byte aligned, then moments_dev or partial_out not 8-byte aligned
+ * (MSE_ERR_ALIGNMENT); arithmetic outside {0, 1}; with old_values, a clip_range_vf that is not finite and > 0; no device
+ * (MSE_ERR_NO_DEVICE).  The others are MSE_ERR_INVALID_ARGUMENT.
+ *
+ * mse_ppo_shard_finish: one launch of one workgroup.
+ *   reduced_dev  f64[mse_ppo_shard_partial_len(D, A)]: the SUM of all shards' partial_out;  moments_dev as above
+ *   grad_out     f32[W]: grad_out[i] = (float)reduced[i]
+ *   stats_out    f32[8]: exactly mse_ppo_loss_grad's eight, from the statistic sums divided by global_batch in double; [6], [7]
+ *                are the mean and std that were used, 0 and 1 when not normalised
+ *   target_kl, control_dev   mse_ppo_loss_grad_matrix's (NULL: no gate, target_kl unread): a gate that was closed on entry
+ *                writes nothing; otherwise one lane counts the minibatch and sets stopped on
+ *                (double)stats_out[4] > 1.5 * target_kl.  Every lane reads the gate before that lane writes it.
+ * Checks, in this order: a NaN target_kl beside a control block; null reduced_dev, moments_dev, params, grad_out or
+ * stats_out; dimensions; struct_size; global_batch < 1; ent_coef or vf_coef not finite; reduced_dev or moments_dev not 8-byte
+ * aligned (MSE_ERR_ALIGNMENT); no device (MSE_ERR_NO_DEVICE).  The others are MSE_ERR_INVALID_ARGUMENT. */
+int64_t mse_ppo_shard_partial_len(int obs_dim, int n_actions); /* in doubles; 0 for dimensions outside 1..32; needs no device */
+int mse_ppo_shard_moments(int64_t n_rows, const int64_t *rows_dev, int64_t batch_local, const float *advantages,
+                          double *moments_out /* f64[4] */, void *workspace, void *stream,
+                          const int32_t *control_dev /* NULL: no gate */);
+int mse_ppo_shard_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch_local, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, int64_t global_batch,
+                            const double *moments_dev /* f64[4], summed */, double *partial_out, void *workspace, void *stream,
+                            const int32_t *control_dev /* NULL: no gate */, int arithmetic /* 0 fma, 1 matrix */,
+                            const float *old_values /* f32[n_rows] or NULL */, double clip_range_vf);
+int mse_ppo_shard_finish(int obs_dim, int n_actions, int64_t global_batch, const double *reduced_dev /* summed */,
+                         const double *moments_dev /* f64[4], summed */, const mse_ppo_params *params, float *grad_out,
+                         float *stats_out /* f32[8] */, void *stream, double target_kl, int32_t *control_dev /* NULL: no gate */);
+
 /* Behaviour cloning: the cross-entropy of DEMONSTRATED actions (the rule-based controller's, mse_rule_actions) under the
  * policy's masked softmax, its statistics and the gradient of its loss, for one minibatch.  weights_dev, n_rows, rows_dev,
  * batch, obs, mask, grad_out, workspace and stream are mse_ppo_loss_grad's, with its clamping of row indices.

@@ -37,6 +37,7 @@ EXPORTS = [
     "mse_rollout_policy_labelled", "mse_rollout_policy_labelled_check",
     "mse_rollout_modular_labelled", "mse_rollout_modular_labelled_check",
     "mse_mono_agent_obs", "mse_rollout_policy_preview", "mse_rollout_policy_preview_check",
+    "mse_ppo_shard_partial_len", "mse_ppo_shard_moments", "mse_ppo_shard_loss_grad", "mse_ppo_shard_finish",
 ]
 
 _other_libs: dict = {}
@@ -212,6 +213,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_ppo_adam_step_gated.argtypes = L.mse_ppo_adam_step.argtypes + [vp]
     L.mse_ppo_loss_grad_matrix.argtypes = L.mse_ppo_loss_grad_gated.argtypes
     L.mse_ppo_loss_grad_vclip.argtypes = L.mse_ppo_loss_grad_gated.argtypes + [C.c_int, vp, C.c_double]
+    L.mse_ppo_shard_partial_len.argtypes = [C.c_int, C.c_int]
+    L.mse_ppo_shard_partial_len.restype = i64
+    L.mse_ppo_shard_moments.argtypes = [i64, vp, i64, vp, vp, vp, vp, vp]
+    L.mse_ppo_shard_loss_grad.argtypes = L.mse_ppo_loss_grad.argtypes[:13] + [i64, vp, vp, vp, vp, vp, C.c_int, vp, C.c_double]
+    L.mse_ppo_shard_finish.argtypes = [C.c_int, C.c_int, i64, vp, vp, C.POINTER(MsePpoParams), vp, vp, vp, C.c_double, vp]
     L.mse_ppo_bc_workspace_bytes.argtypes = [C.c_int, C.c_int]
     L.mse_ppo_bc_workspace_bytes.restype = i64
     L.mse_ppo_bc_loss_grad.argtypes = L.mse_ppo_loss_grad_vclip.argtypes + [vp, C.c_double]

@@ -1,6 +1,7 @@
 // The second half of PPO on the device: returns and advantages (mse_gae), the clipped-surrogate loss of one minibatch
 // with its gradient w.r.t. all weights (mse_ppo_loss_grad; with SB3's clip_range_vf, mse_ppo_loss_grad_vclip; the behaviour-
-// cloning loss of demonstrated actions in the same kernels' BC instantiations, mse_bc_loss_grad), clip_grad_norm_
+// cloning loss of demonstrated actions in the same kernels' BC instantiations, mse_bc_loss_grad; one minibatch whose rows live
+// in several places as three phases around the SHARD instantiations, mse_ppo_shard_moments / _loss_grad / _finish), clip_grad_norm_
 // + Adam (mse_ppo_adam_step), the counter-based permutation that orders an epoch's rows into minibatches (mse_ppo_shuffle, and
 // its host twin) and SB3's train/explained_variance of a rollout (mse_explained_variance, and its host twin).  The
 // per-row arithmetic lives in mse_ppo_math.h (host + device); this file holds the kernels and the C ABI.  gfx950 only.
@@ -198,9 +199,10 @@ __global__ __launch_bounds__(256) void k_ppo_grad(GradArgs G, const float *__res
                                                   const double *__restrict__ adv_partial, float *__restrict__ slabs,
                                                   const int *__restrict__ control, const float *__restrict__ old_values)
 {
-    // the body needs: DP, AP, VCLIP, BC (template parameters), KICK, K and the arguments above
-    constexpr bool KICK = false;
+    // the body needs: DP, AP, VCLIP, BC (template parameters), KICK, K, SHARD, S and the arguments above
+    constexpr bool KICK = false, SHARD = false;
     [[maybe_unused]] const KickArgs K{nullptr, 0.0f};
+    [[maybe_unused]] const ShardArgs S{0, nullptr};
 #include "mse_ppo_grad_body.inc"
 }
 
@@ -217,8 +219,28 @@ __global__ __launch_bounds__(256) void k_ppo_grad_kick(GradArgs G, const float *
                                                        const int *__restrict__ control, const float *__restrict__ old_values,
                                                        KickArgs K)
 {
-    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K and the arguments above
-    constexpr bool BC = false, KICK = true;
+    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K, SHARD, S and the arguments above
+    constexpr bool BC = false, KICK = true, SHARD = false;
+    [[maybe_unused]] const ShardArgs S{0, nullptr};
+#include "mse_ppo_grad_body.inc"
+}
+
+// SHARD: one shard of a minibatch whose rows live in several places (mse_ppo_shard_loss_grad).  G.batch is the number of LOCAL
+// rows (the tile loop's bound and the row clamp are unchanged), every per-row term is scaled by 1 / S.global_batch, and the
+// advantage mean and std come from S.moments, the sums over all shards (G.n_adv_partial is only the "normalise" flag;
+// adv_partial is not an argument).  The slab is the other kernels'.  Everything else is the same statements.
+template <int DP, int AP, bool VCLIP>
+__global__ __launch_bounds__(256) void k_ppo_grad_shard(GradArgs G, const float *__restrict__ weights, const long long *__restrict__ rows,
+                                                        const float *__restrict__ obs, const uint8_t *__restrict__ mask,
+                                                        const int *__restrict__ actions, const float *__restrict__ old_logp,
+                                                        const float *__restrict__ adv, const float *__restrict__ ret,
+                                                        float *__restrict__ slabs, const int *__restrict__ control,
+                                                        const float *__restrict__ old_values, ShardArgs S)
+{
+    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K, SHARD, S and the arguments above
+    constexpr bool BC = false, KICK = false, SHARD = true;
+    [[maybe_unused]] const KickArgs K{nullptr, 0.0f};
+    [[maybe_unused]] const double *adv_partial = nullptr; // named by the branch SHARD discards
 #include "mse_ppo_grad_body.inc"
 }
 
@@ -293,6 +315,103 @@ __global__ __launch_bounds__(256) void k_ppo_reduce_kick(GradArgs G, int n_slabs
                                                          float *__restrict__ stats_out, Gate gate, float bc_coef)
 {
     ppo_reduce_body<true>(G, n_slabs, w_total, slabs, rows, adv, adv_partial, grad_out, stats_out, gate, bc_coef);
+}
+
+// ---- the three phases of a sharded minibatch (mse_ppo_shard_*) ---------------------------------------------------------------
+// partial[2 g], partial[2 g + 1]: sum a and sum a^2 of workgroup g's rows, in double (no pivot: shards must add up)
+__global__ __launch_bounds__(256) void k_ppo_shard_moments_partial(long long batch, long long n_rows, const long long *__restrict__ rows,
+                                                                   const float *__restrict__ adv, double *__restrict__ partial,
+                                                                   const int *__restrict__ control)
+{
+    __shared__ double sh[2][256];
+    if (gate_closed(control)) return;
+    double s = 0.0, q = 0.0;
+    for (long long b = (long long)blockIdx.x * 256 + threadIdx.x; b < batch; b += (long long)gridDim.x * 256) {
+        const double a = (double)adv[row_at(rows, b, n_rows)];
+        s += a;
+        q += a * a;
+    }
+    sh[0][threadIdx.x] = s;
+    sh[1][threadIdx.x] = q;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { // fixed tree
+        if ((int)threadIdx.x < w) {
+            sh[0][threadIdx.x] += sh[0][threadIdx.x + w];
+            sh[1][threadIdx.x] += sh[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = sh[0][0];
+        partial[2 * blockIdx.x + 1] = sh[1][0];
+    }
+}
+
+// one lane adds the partials in index order: moments_out = {count, sum a, sum a^2, 0}; n_partial = 0 (no local row) gives zeros
+__global__ __launch_bounds__(64) void k_ppo_shard_moments_finish(long long batch, int n_partial, const double *__restrict__ partial,
+                                                                 double *__restrict__ moments_out, const int *__restrict__ control)
+{
+    if (gate_closed(control) || threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0, q = 0.0;
+    for (int g = 0; g < n_partial; ++g) {
+        s += partial[2 * g];
+        q += partial[2 * g + 1];
+    }
+    moments_out[0] = (double)batch;
+    moments_out[1] = s;
+    moments_out[2] = q;
+    moments_out[3] = 0.0;
+}
+
+// partial_out[i] = sum over the slabs, in slab order, in double, for the W gradient cells and the kStatSums statistic cells
+// behind them (which sit behind each other in a slab too); the padding cells are 0.  n_slabs = 0 (no local row) writes zeros.
+// Nothing of this launch or the gradient launch before it writes the control block, so the gate is read as it stands.
+__global__ __launch_bounds__(256) void k_ppo_shard_reduce(int n_slabs, int w_total, const float *__restrict__ slabs,
+                                                          double *__restrict__ partial_out, const int *__restrict__ control)
+{
+    if (gate_closed(control)) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int)shard_partial_len(w_total)) return;
+    const long long stride = slab_stride(w_total);
+    double s = 0.0;
+    if (i < w_total + kStatSums) {
+#pragma unroll 8
+        for (int g = 0; g < n_slabs; ++g) s += (double)slabs[(long long)g * stride + i];
+    }
+    partial_out[i] = s;
+}
+
+// ONE workgroup (a policy has at most 4 791 weights), so that every lane has read the gate before the one lane that may close
+// it writes: grad_out[i] = (float)reduced[i]; lane 0 turns the statistic sums into stats_out exactly as k_ppo_reduce does,
+// counts the minibatch and takes the target_kl decision.
+__global__ __launch_bounds__(1024) void k_ppo_shard_finish(GradArgs G, int w_total, const double *__restrict__ reduced,
+                                                           const double *__restrict__ moments, float *__restrict__ grad_out,
+                                                           float *__restrict__ stats_out, Gate gate)
+{
+    const bool closed = gate_closed(gate.control);
+    __syncthreads(); // every lane holds the gate as it was on entry
+    if (closed) return;
+    for (int i = threadIdx.x; i < w_total; i += 1024) grad_out[i] = (float)reduced[i];
+    if (threadIdx.x == 0) {
+        double sums[kStatSums];
+#pragma unroll
+        for (int k = 0; k < kStatSums; ++k) sums[k] = reduced[w_total + k] / (double)G.batch;
+        float mean = 0.0f, std = 1.0f;
+        if (G.n_adv_partial > 0) shard_mean_std(moments, G.batch, mean, std);
+        const double policy_loss = sums[0], value_loss = sums[1], entropy_loss = -sums[2];
+        stats_out[0] = (float)(policy_loss + (double)G.P.ent_coef * entropy_loss + (double)G.P.vf_coef * value_loss);
+        stats_out[1] = (float)policy_loss;
+        stats_out[2] = (float)value_loss;
+        stats_out[3] = (float)entropy_loss;
+        stats_out[4] = (float)sums[3];
+        stats_out[5] = (float)sums[4];
+        stats_out[6] = mean;
+        stats_out[7] = std;
+        if (gate.control != nullptr) {
+            gate.control[1] = gate.control[1] + 1;
+            if (gate.kl_limit > 0.0 && (double)stats_out[4] > gate.kl_limit) gate.control[0] = 1; // k_ppo_reduce's rule
+        }
+    }
 }
 
 // ---- clip_grad_norm_ + Adam, one workgroup ----------------------------------------------------------------------------
@@ -395,6 +514,21 @@ void launch_grad_kick(const GradArgs &G, int n_slabs, hipStream_t s, const float
     else
         hipLaunchKernelGGL((k_ppo_grad_kick<DP, AP, false>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask, actions,
                            old_logp, adv, ret, adv_partial, slabs, control, old_values, K);
+}
+
+// enqueues the SHARD entry of the same body: no adv_partial, one more argument
+template <int DP, int AP>
+void launch_grad_shard(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                       const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret, float *slabs,
+                       const int *control, const float *old_values, const ShardArgs &S)
+{
+    const size_t lds = (size_t)(Padded<DP, AP>::total + 4 * kStageFloats + kMiscFloats) * sizeof(float);
+    if (old_values != nullptr)
+        hipLaunchKernelGGL((k_ppo_grad_shard<DP, AP, true>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
+                           actions, old_logp, adv, ret, slabs, control, old_values, S);
+    else
+        hipLaunchKernelGGL((k_ppo_grad_shard<DP, AP, false>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
+                           actions, old_logp, adv, ret, slabs, control, old_values, S);
 }
 
 // enqueues the BC instantiation of k_ppo_grad: no old log-probabilities, advantages, gate or old values
@@ -584,6 +718,125 @@ int mse_ppo_loss_grad_vclip(int obs_dim, int n_actions, const float *weights_dev
                      advantages, returns, params, grad_out, stats_out, workspace, stream,
                      control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl}, arithmetic, old_values,
                      clip_range_vf);
+}
+
+// ---- mse_ppo_loss_grad_vclip for a minibatch whose rows live in several places: moments, partial, finish -----------------------
+int64_t mse_ppo_shard_partial_len(int obs_dim, int n_actions)
+{
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32) return 0;
+    return (int64_t)shard_partial_len(flat_layout(obs_dim, n_actions).total);
+}
+
+int mse_ppo_shard_moments(int64_t n_rows, const int64_t *rows_dev, int64_t batch_local, const float *advantages, double *moments_out,
+                          void *workspace, void *stream, const int32_t *control_dev)
+{
+    auto fail = [](int status, const char *why) { return mse_internal_fail(status, (std::string("mse_ppo_shard_moments: ") + why).c_str()); };
+    if (advantages == nullptr || moments_out == nullptr || workspace == nullptr) return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_rows < 1 || batch_local < 0 || (rows_dev == nullptr && batch_local > n_rows))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need 0 <= batch_local (<= n_rows without rows_dev)");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(MSE_ERR_ALIGNMENT, "workspace must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(moments_out) & 7u) != 0) return fail(MSE_ERR_ALIGNMENT, "moments_out must be 8-byte aligned");
+    if (cu_count() <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *partial = static_cast<double *>(workspace);
+    int n_partial = 0;
+    if (batch_local > 0) {
+        const long long g1 = (batch_local + 1023) / 1024;
+        n_partial = (int)(g1 > kMaxAdvPartials ? kMaxAdvPartials : g1);
+        hipLaunchKernelGGL(k_ppo_shard_moments_partial, dim3((unsigned)n_partial), dim3(256), 0, s, (long long)batch_local, (long long)n_rows,
+                           reinterpret_cast<const long long *>(rows_dev), advantages, partial, control_dev);
+    }
+    hipLaunchKernelGGL(k_ppo_shard_moments_finish, dim3(1), dim3(64), 0, s, (long long)batch_local, n_partial, partial, moments_out,
+                       control_dev);
+    if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_ppo_shard_loss_grad(int obs_dim, int n_actions, const float *weights_dev, int64_t n_rows, const int64_t *rows_dev,
+                            int64_t batch_local, const float *obs, const uint8_t *mask, const int32_t *actions, const float *old_logp,
+                            const float *advantages, const float *returns, const mse_ppo_params *params, int64_t global_batch,
+                            const double *moments_dev, double *partial_out, void *workspace, void *stream, const int32_t *control_dev,
+                            int arithmetic, const float *old_values, double clip_range_vf)
+{
+    auto fail = [](int status, const char *why) { return mse_internal_fail(status, (std::string("mse_ppo_shard_loss_grad: ") + why).c_str()); };
+    if (weights_dev == nullptr || obs == nullptr || actions == nullptr || old_logp == nullptr || advantages == nullptr ||
+        returns == nullptr || params == nullptr || moments_dev == nullptr || partial_out == nullptr || workspace == nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "obs_dim and n_actions must be in 1..32");
+    if (params->struct_size != sizeof(mse_ppo_params)) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_params.struct_size mismatch");
+    if (n_rows < 1 || batch_local < 0 || (rows_dev == nullptr && batch_local > n_rows))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need 0 <= batch_local (<= n_rows without rows_dev)");
+    if (global_batch < 1 || global_batch < batch_local)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "need global_batch >= max(1, batch_local)");
+    if (!(params->clip_range >= 0.0f) || !std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "bad clip_range / ent_coef / vf_coef");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15u) != 0) return fail(MSE_ERR_ALIGNMENT, "workspace must be 16-byte aligned");
+    if (((reinterpret_cast<uintptr_t>(moments_dev) | reinterpret_cast<uintptr_t>(partial_out)) & 7u) != 0)
+        return fail(MSE_ERR_ALIGNMENT, "moments_dev and partial_out must be 8-byte aligned");
+    if (arithmetic != 0 && arithmetic != 1) return fail(MSE_ERR_INVALID_ARGUMENT, "arithmetic must be 0 (fma) or 1 (matrix)");
+    const float c_vf = old_values != nullptr ? (float)clip_range_vf : 0.0f; // without old_values clip_range_vf is not read
+    if (old_values != nullptr && !(std::isfinite(clip_range_vf) && c_vf > 0.0f && std::isfinite(c_vf)))
+        return fail(MSE_ERR_INVALID_ARGUMENT, "clip_range_vf must be finite and > 0 (as a float32) with old_values");
+    const int cus = cu_count();
+    if (cus <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *slabs = reinterpret_cast<float *>(static_cast<double *>(workspace) + 2 * kMaxAdvPartials); // mse_ppo_loss_grad's layout
+    const long long *rows = reinterpret_cast<const long long *>(rows_dev);
+    // G.batch bounds the local rows; n_adv_partial is the "normalise" flag: the existing rule applied to the global count
+    const GradArgs G{obs_dim, n_actions, (long long)n_rows, (long long)batch_local,
+                     params->normalize_advantage != 0 && global_batch > 1 ? 1 : 0,
+                     Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage, c_vf}};
+    const ShardArgs S{(long long)global_batch, moments_dev};
+    const int n_slabs = batch_local > 0 ? (int)grad_groups(batch_local, cus) : 0;
+    hipError_t e = hipSuccess;
+    if (n_slabs == 0) {
+        // no local row: no gradient launch, the reduction below writes zeros
+    } else if (arithmetic == 1) {
+        e = mse_ppo_launch_grad_matrix_shard(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, slabs,
+                                             control_dev, old_values, S);
+    } else {
+#define MSE_PPO_LAUNCH_SHARD(DP, AP)                                                                                                  \
+    launch_grad_shard<DP, AP>(G, n_slabs, s, weights_dev, rows, obs, mask, actions, old_logp, advantages, returns, slabs, control_dev, \
+                              old_values, S)
+        MSE_PPO_DISPATCH(select_grad_shape(obs_dim, n_actions), MSE_PPO_LAUNCH_SHARD);
+#undef MSE_PPO_LAUNCH_SHARD
+    }
+    if (e == hipSuccess) {
+        const int w_total = flat_layout(obs_dim, n_actions).total;
+        const int len = (int)shard_partial_len(w_total);
+        hipLaunchKernelGGL(k_ppo_shard_reduce, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, n_slabs, w_total, slabs, partial_out,
+                           control_dev);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
+}
+
+int mse_ppo_shard_finish(int obs_dim, int n_actions, int64_t global_batch, const double *reduced_dev, const double *moments_dev,
+                         const mse_ppo_params *params, float *grad_out, float *stats_out, void *stream, double target_kl,
+                         int32_t *control_dev)
+{
+    auto fail = [](int status, const char *why) { return mse_internal_fail(status, (std::string("mse_ppo_shard_finish: ") + why).c_str()); };
+    if (control_dev != nullptr && target_kl != target_kl) return fail(MSE_ERR_INVALID_ARGUMENT, "target_kl is NaN");
+    if (reduced_dev == nullptr || moments_dev == nullptr || params == nullptr || grad_out == nullptr || stats_out == nullptr)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "null argument");
+    if (obs_dim < 1 || obs_dim > 32 || n_actions < 1 || n_actions > 32)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "obs_dim and n_actions must be in 1..32");
+    if (params->struct_size != sizeof(mse_ppo_params)) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_ppo_params.struct_size mismatch");
+    if (global_batch < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "need global_batch >= 1");
+    if (!std::isfinite(params->ent_coef) || !std::isfinite(params->vf_coef)) return fail(MSE_ERR_INVALID_ARGUMENT, "bad ent_coef / vf_coef");
+    if (((reinterpret_cast<uintptr_t>(reduced_dev) | reinterpret_cast<uintptr_t>(moments_dev)) & 7u) != 0)
+        return fail(MSE_ERR_ALIGNMENT, "reduced_dev and moments_dev must be 8-byte aligned");
+    if (cu_count() <= 0) return fail(MSE_ERR_NO_DEVICE, "no HIP device (there is no CPU path)");
+    // batch = the global count (the divisor of the statistic sums); n_adv_partial = the "normalise" flag, mse_ppo_shard_loss_grad's
+    const GradArgs G{obs_dim, n_actions, 0, (long long)global_batch, params->normalize_advantage != 0 && global_batch > 1 ? 1 : 0,
+                     Params{params->clip_range, params->ent_coef, params->vf_coef, params->normalize_advantage, 0.0f}};
+    const Gate gate = control_dev == nullptr ? Gate{nullptr, 0.0} : Gate{control_dev, 1.5 * target_kl};
+    hipLaunchKernelGGL(k_ppo_shard_finish, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), G,
+                       flat_layout(obs_dim, n_actions).total, reduced_dev, moments_dev, grad_out, stats_out, gate);
+    if (hipGetLastError() != hipSuccess) return fail(MSE_ERR_HIP, "kernel launch failed");
+    return MSE_OK;
 }
 
 int64_t mse_ppo_bc_workspace_bytes(int obs_dim, int n_actions)

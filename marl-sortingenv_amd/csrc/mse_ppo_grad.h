@@ -124,6 +124,40 @@ __device__ __forceinline__ void publish_adv_mean_std(const GradArgs &G, const lo
     }
 }
 
+// ---- a minibatch whose rows live in several places (mse_ppo_shard_*) -----------------------------------------
+// What a SHARD instantiation reads beyond the other kernels' arguments; {0, NULL} for those, which never read it.  In a SHARD
+// launch G.batch is the LOCAL row count (the tile loop's bound), every per-row term is scaled by 1 / global_batch, and
+// G.n_adv_partial is only a flag (0 or 1): the mean and std come from `moments`, not from k_ppo_adv_partial's partials.
+struct ShardArgs {
+    long long global_batch; // B: rows of the minibatch over all shards
+    const double *moments;  // f64[4]: {count, sum a, sum a^2, 0} over all shards
+};
+
+// the shard partial: W gradient sums, kStatSums statistic sums (not divided), padding to a multiple of 4; all double
+__host__ __device__ constexpr long long shard_partial_len(long long w) { return (w + kStatSums + 3) / 4 * 4; }
+
+// mean and unbiased std of the whole minibatch from its moments; every caller gets the same bits
+__device__ __forceinline__ void shard_mean_std(const double *moments, long long batch, float &mean, float &std)
+{
+    const double s = moments[1], q = moments[2];
+    const double var = (q - s * s / (double)batch) / (double)(batch - 1);
+    mean = (float)(s / (double)batch);
+    std = (float)sqrt(var > 0.0 ? var : 0.0);
+}
+
+// publish_adv_mean_std of a SHARD instantiation
+__device__ __forceinline__ void publish_shard_mean_std(const GradArgs &G, const ShardArgs &S, float *misc, int wave, int lane)
+{
+    if (wave == 0) {
+        float mean = 0.0f, std = 1.0f;
+        if (G.n_adv_partial > 0) shard_mean_std(S.moments, S.global_batch, mean, std);
+        if (lane == 0) {
+            misc[0] = mean;
+            misc[1] = std;
+        }
+    }
+}
+
 // an action outside the head is clamped into it, never followed
 __device__ __forceinline__ int clamped_action(int action, int A) { return action < 0 ? 0 : (action >= A ? A - 1 : action); }
 
@@ -197,6 +231,12 @@ hipError_t mse_ppo_launch_grad_matrix(const mseppo::GradArgs &G, int n_slabs, hi
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
                                       const float *old_logp, const float *adv, const float *ret, const double *adv_partial,
                                       float *slabs, const int *control, const float *old_values);
+// ... the SHARD entry (mse_ppo_shard_loss_grad): G.batch local rows, terms scaled by 1 / S.global_batch, mean and std from
+// S.moments; it writes what k_ppo_grad_shard writes
+hipError_t mse_ppo_launch_grad_matrix_shard(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+                                            const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
+                                            const float *old_logp, const float *adv, const float *ret, float *slabs,
+                                            const int *control, const float *old_values, const mseppo::ShardArgs &S);
 // ... the BC instantiation of k_ppo_grad_matrix (behaviour cloning: `actions` are the demonstrated ones; ret may be NULL, the
 // critic then takes no tile); it writes what the BC instantiation of k_ppo_grad writes
 hipError_t mse_ppo_launch_grad_matrix_bc(const mseppo::GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,

@@ -2,7 +2,9 @@
 // k_ppo_grad (KICK = false) and k_ppo_grad_kick (KICK = true), whose two more arguments must stay out of k_ppo_grad's.  It is
 // text and not a function, because no helper form kept k_ppo_grad's instructions (tools/same_isa.py): an inlined body moves the
 // kernel's exit and its register allocation.  The including function provides the template parameters DP, AP, VCLIP, the
-// constants BC and KICK, the kernel's arguments and `K` (KickArgs; never read with KICK = false).
+// constants BC and KICK, the kernel's arguments and `K` (KickArgs; never read with KICK = false).  Likewise k_ppo_grad_shard
+// (SHARD = true) with `S` (ShardArgs; never read with SHARD = false): G.batch bounds the local rows, S.global_batch scales the
+// per-row terms, the advantage mean and std come from S.moments.
     typedef Padded<DP, AP> PW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if (gate_closed(control)) { // grid-uniform
@@ -18,11 +20,14 @@
     for (int i = tid; i < PW::total; i += 256) wl0[i] = 0.0f;
     __syncthreads();
     for (int f = tid; f < F.total; f += 256) wl0[padded_index<DP, AP>(f, D, A)] = weights[f];
-    publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
+    if constexpr (SHARD)
+        publish_shard_mean_std(G, S, misc, wave, lane);
+    else
+        publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
     __syncthreads();
     const bool normalize = G.n_adv_partial > 0;
     const float mean = misc[0], std = misc[1];
-    const float inv_b_all = 1.0f / (float)G.batch;
+    const float inv_b_all = 1.0f / (float)(SHARD ? S.global_batch : G.batch); // SHARD: G.batch is the local row bound
     const bool critic = (wave & 1) != 0;
     float *strip = strips + wave * kStageFloats;
     LayerAcc L1 = {}, L2 = {}, L3 = {}; // first, second hidden layer, head

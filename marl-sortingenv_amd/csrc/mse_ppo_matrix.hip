@@ -166,9 +166,10 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix(GradArgs G, const float
                                                          float *__restrict__ slabs, const int *__restrict__ control,
                                                          const float *__restrict__ old_values)
 {
-    // the body needs: DP, AP, VCLIP, BC (template parameters), KICK, K and the arguments above
-    constexpr bool KICK = false;
+    // the body needs: DP, AP, VCLIP, BC (template parameters), KICK, K, SHARD, S and the arguments above
+    constexpr bool KICK = false, SHARD = false;
     [[maybe_unused]] const KickArgs K{nullptr, 0.0f};
+    [[maybe_unused]] const ShardArgs S{0, nullptr};
 #include "mse_ppo_matrix_body.inc"
 }
 
@@ -183,8 +184,27 @@ __global__ __launch_bounds__(256) void k_ppo_grad_matrix_kick(GradArgs G, const 
                                                               float *__restrict__ slabs, const int *__restrict__ control,
                                                               const float *__restrict__ old_values, KickArgs K)
 {
-    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K and the arguments above
-    constexpr bool BC = false, KICK = true;
+    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K, SHARD, S and the arguments above
+    constexpr bool BC = false, KICK = true, SHARD = false;
+    [[maybe_unused]] const ShardArgs S{0, nullptr};
+#include "mse_ppo_matrix_body.inc"
+}
+
+// SHARD: one shard of a minibatch, as in k_ppo_grad_shard: G.batch local rows, per-row terms scaled by 1 / S.global_batch, the
+// advantage mean and std from S.moments; everything else is the same statements (mse_ppo_matrix_body.inc)
+template <int DP, int AP, bool VCLIP>
+__global__ __launch_bounds__(256) void k_ppo_grad_matrix_shard(GradArgs G, const float *__restrict__ weights,
+                                                               const long long *__restrict__ rows, const float *__restrict__ obs,
+                                                               const uint8_t *__restrict__ mask, const int *__restrict__ actions,
+                                                               const float *__restrict__ old_logp, const float *__restrict__ adv,
+                                                               const float *__restrict__ ret, float *__restrict__ slabs,
+                                                               const int *__restrict__ control, const float *__restrict__ old_values,
+                                                               ShardArgs S)
+{
+    // the body needs: DP, AP, VCLIP (template parameters), BC, KICK, K, SHARD, S and the arguments above
+    constexpr bool BC = false, KICK = false, SHARD = true;
+    [[maybe_unused]] const KickArgs K{nullptr, 0.0f};
+    [[maybe_unused]] const double *adv_partial = nullptr; // named by the branch SHARD discards
 #include "mse_ppo_matrix_body.inc"
 }
 
@@ -229,7 +249,38 @@ hipError_t launch_kick(const GradArgs &G, int n_slabs, hipStream_t s, const floa
     return hipGetLastError();
 }
 
+template <int DP, int AP, bool VCLIP>
+hipError_t launch_shard(const GradArgs &G, int n_slabs, hipStream_t s, const float *weights, const long long *rows, const float *obs,
+                        const uint8_t *mask, const int *actions, const float *old_logp, const float *adv, const float *ret, float *slabs,
+                        const int *control, const float *old_values, const ShardArgs &S)
+{
+    constexpr size_t lds = (size_t)kLdsFloats * sizeof(float);
+    static std::atomic<bool> allowed[64];
+    const hipError_t e = allow_lds(reinterpret_cast<const void *>(&k_ppo_grad_matrix_shard<DP, AP, VCLIP>), lds, allowed);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_ppo_grad_matrix_shard<DP, AP, VCLIP>), dim3((unsigned)n_slabs), dim3(256), lds, s, G, weights, rows, obs, mask,
+                       actions, old_logp, adv, ret, slabs, control, old_values, S);
+    return hipGetLastError();
+}
+
 } // namespace
+
+hipError_t mse_ppo_launch_grad_matrix_shard(const GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
+                                            const long long *rows, const float *obs, const uint8_t *mask, const int *actions,
+                                            const float *old_logp, const float *adv, const float *ret, float *slabs,
+                                            const int *control, const float *old_values, const ShardArgs &S)
+{
+    hipError_t e = hipErrorInvalidValue;
+#define MSE_SHARD_MATRIX_LAUNCH(DP, AP)                                                                                              \
+    e = old_values != nullptr                                                                                                        \
+            ? launch_shard<DP, AP, true>(G, n_slabs, stream, weights, rows, obs, mask, actions, old_logp, adv, ret, slabs, control, \
+                                         old_values, S)                                                                              \
+            : launch_shard<DP, AP, false>(G, n_slabs, stream, weights, rows, obs, mask, actions, old_logp, adv, ret, slabs, control, \
+                                          old_values, S)
+    MSE_PPO_DISPATCH(select_grad_shape(G.D, G.A), MSE_SHARD_MATRIX_LAUNCH);
+#undef MSE_SHARD_MATRIX_LAUNCH
+    return e;
+}
 
 hipError_t mse_ppo_launch_grad_matrix(const GradArgs &G, int n_slabs, hipStream_t stream, const float *weights,
                                       const long long *rows, const float *obs, const uint8_t *mask, const int *actions,

@@ -1,7 +1,8 @@
 // mse_ppo_matrix_body.inc -- the statements of k_ppo_grad_matrix's body (mse_ppo_matrix.hip), included once per __global__
 // entry of the kernel: k_ppo_grad_matrix (KICK = false) and k_ppo_grad_matrix_kick (KICK = true).  Text and not a function for
 // the reason mse_ppo_grad_body.inc gives.  The including function provides the template parameters DP, AP, VCLIP, the
-// constants BC and KICK, the kernel's arguments and `K` (KickArgs; never read with KICK = false).
+// constants BC and KICK, the kernel's arguments and `K` (KickArgs; never read with KICK = false).  Likewise
+// k_ppo_grad_matrix_shard (SHARD = true) with `S` (ShardArgs; never read with SHARD = false), as in mse_ppo_grad_body.inc.
     constexpr int KS1 = DP / 2;          // k-steps of the first layer: units 0 .. DP - 1
     constexpr int KSA = ksteps_for(AP);  // k-steps of the head's back-propagation: actions 0 .. AP - 1
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -24,11 +25,14 @@
         const int tr = matrix_index_transposed(f, D, A);
         if (tr >= 0) wl0[tr] = w;
     }
-    publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
+    if constexpr (SHARD)
+        publish_shard_mean_std(G, S, misc, wave, lane);
+    else
+        publish_adv_mean_std(G, rows, adv, adv_partial, misc, wave, lane);
     __syncthreads();
     const bool normalize = G.n_adv_partial > 0;
     const float mean = misc[0], std = misc[1];
-    const float inv_b_all = 1.0f / (float)G.batch;
+    const float inv_b_all = 1.0f / (float)(SHARD ? S.global_batch : G.batch); // SHARD: G.batch is the local row bound
     const bool critic = (wave & 1) != 0;
     float *strip = strips + wave * kStripFloats;
     LayerGrad L1, L2, L3; // first, second hidden layer, head

@@ -221,7 +221,9 @@ class ImitationLearner(PPOLearner):
 
     def __init__(self, policy: MlpPolicy, learning_rate: float = 1e-3, n_epochs: int = 1, batch_size: Optional[int] = None,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, adam_eps: float = 1e-5,
-                 seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", arithmetic: str = "fma"):
+                 seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", arithmetic: str = "fma", exchange=None):
+        if exchange is not None:
+            raise ValueError("ImitationLearner cannot be combined with an exchange: mse_bc_loss_grad has no sharded form")
         super().__init__(policy, learning_rate=float(learning_rate), n_epochs=n_epochs, batch_size=batch_size, ent_coef=ent_coef,
                          vf_coef=vf_coef, max_grad_norm=max_grad_norm, normalize_advantage=False, adam_eps=adam_eps, seed=seed,
                          shuffle=shuffle, weight_sync=weight_sync, arithmetic=arithmetic)

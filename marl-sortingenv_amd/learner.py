@@ -17,6 +17,9 @@ states, `data["expert_actions"]`, in the same gradient launch), so that fine-tun
 `EpisodeStats` over the training rollouts, and `EvalCallback`'s periodic `evaluate_policy` with the best weights kept.
 `state_dict` / `load_state_dict` carry everything of a run that lives here, and `learn(first_iteration=...,
 checkpoint_path=..., checkpoint_freq=...)` writes and continues whole runs (checkpoint.py): a resumed run is the same run.
+`exchange` (a `sharding.GradientExchange`) makes the update data-parallel: every rank keeps the rollout rows it collected and
+a minibatch is cut into three phases (`mse_ppo_shard_moments`, `mse_ppo_shard_loss_grad`, `mse_ppo_shard_finish`) with one
+all-reduce of four doubles and one of the gradient sums between them; no rollout row crosses a link.
 """
 from __future__ import annotations
 
@@ -163,15 +166,34 @@ class PPOLearner:
     kickstarting).  Every `loss_grad` then goes through `mse_ppo_bc_loss_grad`, with either arithmetic, gated or not, with
     or without `clip_range_vf`, and reads `data["expert_actions"]` (i32, one per row: the collectors' `expert_labels=True`).
     A row whose label the mask forbids adds nothing to that term.  The statistics have twelve columns (PPO_BC_STAT_NAMES).
-    With None everything is exactly what it was without the argument."""
+    With None everything is exactly what it was without the argument.
+
+    `exchange` (None = off; a `sharding.GradientExchange`): a data-parallel update over the ranks of its group.  Every rank
+    constructs the learner over its own policy and passes `update()` the rollout of its own envs (`ShardedSortingEnv.env`
+    under a `FusedPolicyRollout`); GAE stays local, because it is per env.  The constructor broadcasts rank 0's weights, so
+    all ranks start alike (`m` and `v` are zero everywhere), and the shuffle seed becomes `(seed + rank) mod 2^64`, so ranks
+    do not permute alike (`permutation()` and the CPU generator use that seed).  `batch_size` counts rows PER RANK; the
+    minibatches of an epoch are `shard_minibatch_plan(totals, batch_size)` over the ranks' row counts, so with ragged shards
+    a rank meets short and empty minibatches and still makes every collective call.  Per minibatch: `shard_moments` ->
+    `all_reduce_sum` -> `shard_partial` -> `all_reduce_sum` -> `shard_finish` -> the Adam step; every rank finishes from the
+    same summed bits, so weights, `m`, `v`, the `target_kl` decision and the returned statistics (the GLOBAL minibatch's) are
+    identical on all ranks without ever being exchanged.  A checkpoint is per rank.
+    RESULTS ARE NOT INDEPENDENT OF THE NUMBER OF RANKS (unlike the env engine's rollouts, which are): which rows share a
+    minibatch is decided per rank, and the sums are formed in another order.  A given world size is reproducible bit for bit.
+    `bc_coef` and `update(explained_variance=True)` are refused together with an exchange.
+    With None the learner is exactly what it was without the argument."""
 
     bc_coef: Optional[float] = None  # off unless the constructor sets it
+    exchange = None  # off unless the constructor sets it
 
     def __init__(self, policy: MlpPolicy, learning_rate: Schedule = 3e-4, n_epochs: int = 10, batch_size: Optional[int] = None,
                  gamma: float = 0.99, gae_lambda: float = 0.95, clip_range: Schedule = 0.2, ent_coef: float = 0.0,
                  vf_coef: float = 0.5, max_grad_norm: float = 0.5, normalize_advantage: bool = True, adam_eps: float = 1e-5,
                  seed: int = 0, shuffle: str = "cpu", weight_sync: str = "host", target_kl: Optional[float] = None,
-                 arithmetic: str = "fma", clip_range_vf: Optional[Schedule] = None, bc_coef: Optional[Schedule] = None):
+                 arithmetic: str = "fma", clip_range_vf: Optional[Schedule] = None, bc_coef: Optional[Schedule] = None,
+                 exchange=None):
+        if exchange is not None and bc_coef is not None:
+            raise ValueError("bc_coef cannot be combined with an exchange: mse_ppo_bc_loss_grad has no sharded form")
         if shuffle not in ("cpu", "device"):
             raise ValueError(f"shuffle must be 'cpu' or 'device', not {shuffle!r}")
         if weight_sync not in ("host", "device"):
@@ -199,6 +221,9 @@ class PPOLearner:
         self.beta1, self.beta2 = 0.9, 0.999
         self.params = MsePpoParams(C.sizeof(MsePpoParams), float(clip_range), float(ent_coef), float(vf_coef),
                                    1 if normalize_advantage else 0)
+        self.exchange = exchange
+        if exchange is not None:  # ranks must not permute alike
+            seed = (int(seed) + int(exchange.rank)) & (2 ** 64 - 1)
         self.shuffle, self.seed = shuffle, int(seed) & (2 ** 64 - 1)
         self.generator = torch.Generator(device="cpu").manual_seed(int(seed))
         dev = policy.device
@@ -220,6 +245,12 @@ class PPOLearner:
         self.episode_stats = None  # learn(episode_stats=True): the EpisodeStats whose carry spans the iterations
         self.best_mean_reward = float("-inf")  # learn(eval_collector=...): EvalCallback's best model so far
         self.best_weights = None  # f32[W] on the device, a copy of `weights` at the best evaluation
+        self._shard_buffers = None  # (moments f64[4], partial f64[partial_len]) of the phase methods, made on first use
+        self._shard_totals = None  # exchange: (this rank's row count, every rank's), gathered once per rollout size
+        if exchange is not None:
+            exchange.broadcast(self.weights)  # all ranks start from rank 0's weights
+            self._hand_over()
+            self.policy.sync()
 
     def loss_grad(self, data: dict, rows: Optional[torch.Tensor], batch: int, stats_out: torch.Tensor,
                   weights: Optional[torch.Tensor] = None, grad_out: Optional[torch.Tensor] = None,
@@ -270,6 +301,75 @@ class PPOLearner:
                 check(self.L.mse_ppo_loss_grad_gated(*args, float(target_kl), _ptr(control)))
         return g
 
+    # ---- a minibatch in three phases (include/mse.h: mse_ppo_shard_*) ---------------------------------------------------
+    def _shard_args(self, data: dict):
+        if self.bc_coef is not None:
+            raise ValueError("bc_coef has no sharded form: the phase methods serve the PPO loss only")
+        obs = data["observations"]
+        n_rows = obs.shape[0] * obs.shape[1] if obs.dim() == 3 else obs.shape[0]
+        if self._shard_buffers is None:
+            n = int(self.L.mse_ppo_shard_partial_len(self.policy.obs_dim, self.policy.n_actions))
+            self._shard_buffers = (torch.zeros(4, dtype=torch.float64, device=self.device),
+                                   torch.zeros(n, dtype=torch.float64, device=self.device))
+        return obs, n_rows
+
+    def shard_moments(self, data: dict, rows: Optional[torch.Tensor], batch_local: int, control: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Phase 1, `mse_ppo_shard_moments`: {batch_local, sum a, sum a^2, 0} over this shard's minibatch rows of
+        `data["advantages"]` -> f64[4] on the device (`out`, or a buffer the learner keeps).  rows: i64 device tensor, or
+        None for rows 0 .. batch_local - 1; batch_local may be 0.  The caller sums the shards' results."""
+        _, n_rows = self._shard_args(data)
+        m = self._shard_buffers[0] if out is None else out
+        if not data["advantages"].is_contiguous():
+            raise ValueError("advantages must be contiguous")
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_shard_moments(n_rows, _ptr(rows), int(batch_local), _ptr(data["advantages"]), _ptr(m),
+                                               _ptr(self.workspace), _stream(self.device), _ptr(control)))
+        return m
+
+    def shard_partial(self, data: dict, rows: Optional[torch.Tensor], batch_local: int, global_batch: int, moments: torch.Tensor,
+                      control: Optional[torch.Tensor] = None, target_kl: float = 0.0, weights: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Phase 2, `mse_ppo_shard_loss_grad`: this shard's gradient and statistic sums of a minibatch of `global_batch`
+        rows over all shards, with the advantages normalised by `moments` (f64[4], device: the SUM of all shards' phase 1)
+        -> f64[partial_len] on the device (`out`, or a buffer the learner keeps).  `arithmetic` and `clip_range_vf` (with
+        `data["values"]`) apply as in `loss_grad`.  target_kl is not read here (the gate's decision is phase 3's).  The
+        caller sums the shards' results."""
+        p = self.policy
+        obs, n_rows = self._shard_args(data)
+        out = self._shard_buffers[1] if out is None else out
+        w = self.weights if weights is None else weights
+        for name in ("observations", "actions", "log_probs", "advantages", "returns"):
+            if not data[name].is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+        old = None
+        if self.clip_range_vf is not None:
+            old = data["values"]
+            if old.dtype != torch.float32 or not old.is_contiguous() or old.numel() != n_rows or old.device != obs.device:
+                raise ValueError("clip_range_vf needs data['values']: contiguous f32, one per rollout row, on the rollout's device")
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_shard_loss_grad(
+                p.obs_dim, p.n_actions, _ptr(w), n_rows, _ptr(rows), int(batch_local), _ptr(obs), _ptr(data.get("action_masks")),
+                _ptr(data["actions"]), _ptr(data["log_probs"]), _ptr(data["advantages"]), _ptr(data["returns"]),
+                C.byref(self.params), int(global_batch), _ptr(moments), _ptr(out), _ptr(self.workspace), _stream(self.device),
+                _ptr(control), 1 if self.arithmetic == "matrix" else 0, _ptr(old), float(self.clip_range_vf or 0.0)))
+        return out
+
+    def shard_finish(self, global_batch: int, reduced: torch.Tensor, moments: torch.Tensor, stats_out: torch.Tensor,
+                     control: Optional[torch.Tensor] = None, target_kl: float = 0.0,
+                     grad_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Phase 3, `mse_ppo_shard_finish`: the summed partial and moments -> the gradient (f32[W]: `grad_out`, or
+        `self.grad`) and stats_out f32[8]; with `control` it counts the minibatch and takes the `target_kl` decision.
+        Returns the gradient tensor; `adam_step` follows."""
+        if self.bc_coef is not None:
+            raise ValueError("bc_coef has no sharded form: the phase methods serve the PPO loss only")
+        g = self.grad if grad_out is None else grad_out
+        with torch.cuda.device(self.device):
+            check(self.L.mse_ppo_shard_finish(self.policy.obs_dim, self.policy.n_actions, int(global_batch), _ptr(reduced),
+                                              _ptr(moments), C.byref(self.params), _ptr(g), _ptr(stats_out), _stream(self.device),
+                                              float(target_kl), _ptr(control)))
+        return g
+
     def adam_step(self, control: Optional[torch.Tensor] = None):
         """One Adam step; with `control`, `mse_ppo_adam_step_gated`: nothing happens on the device once it says stopped
         (`step` still advances here: `update()` corrects it from the control block)."""
@@ -308,6 +408,12 @@ class PPOLearner:
     def _minibatches(self, total: int, bs: int):
         """Yields the device row indices of every minibatch of an update, in order: n_epochs permutations of `total` rows
         (`shuffle`; `last_permutations` / `last_epochs` record them), each cut into runs of `bs`, the last maybe short."""
+        for perm in self._epoch_permutations(total):
+            for start in range(0, total, bs):
+                yield perm[start:start + bs]
+
+    def _epoch_permutations(self, total: int):
+        """Yields the device permutation of `total` rows of each of the n_epochs epochs of an update."""
         self.last_permutations, self.last_epochs = [], []
         for _ in range(self.n_epochs):
             if self.shuffle == "device":
@@ -316,8 +422,35 @@ class PPOLearner:
                 perm_cpu = torch.randperm(total, generator=self.generator)
                 self.last_permutations.append(perm_cpu)
                 perm = perm_cpu.to(self.device)
-            for start in range(0, total, bs):
-                yield perm[start:start + bs]
+            yield perm
+
+    def _shard_plan(self, total: int):
+        """-> (batch size per rank, `shard_minibatch_plan` of one epoch) for a rollout of `total` rows on this rank: one
+        all-gather of the ranks' row counts as host integers, repeated only when this rank's rollout size changes."""
+        from .sharding import shard_minibatch_plan
+
+        if self._shard_totals is None or self._shard_totals[0] != total:
+            self._shard_totals = (total, self.exchange.all_gather_ints(total))
+        totals = self._shard_totals[1]
+        bs = self.batch_size if self.batch_size is not None else (max(totals) + 3) // 4
+        bs = max(1, min(int(bs), max(totals)))
+        return bs, shard_minibatch_plan(totals, bs)
+
+    def _sharded_minibatches(self, data: dict, total: int, bs: int, plan: list, stats: torch.Tensor, control) -> None:
+        """The minibatch loop of `update()` with an exchange: the three phases with the two all-reduces between them."""
+        ex, i = self.exchange, 0
+        for perm in self._epoch_permutations(total):
+            for j, sizes in enumerate(plan):
+                b_local, b_global = sizes[ex.rank], sum(sizes)
+                rows = perm[j * bs:j * bs + b_local] if b_local > 0 else None
+                # A closed gate still makes both collective calls on every rank (a rank that skipped one would hang the
+                # others): the kernels then write nothing, so the buffers that are summed are simply stale, and phase 3,
+                # which is closed too, never reads them.
+                moments = ex.all_reduce_sum(self.shard_moments(data, rows, b_local, control=control))
+                partial = ex.all_reduce_sum(self.shard_partial(data, rows, b_local, b_global, moments, control=control))
+                self.shard_finish(b_global, partial, moments, stats[i], control=control, target_kl=self.target_kl or 0.0)
+                self.adam_step(control)
+                i += 1
 
     def _resolve_schedules(self) -> None:
         """What SB3 does at the top of train(): the scheduled values at `progress_remaining`, once per update."""
@@ -349,7 +482,8 @@ class PPOLearner:
         """Everything the constructor fixes that changes results, as plain data: the dims, the constructor's numbers and
         modes, `scheduled` (the names of the fields that are schedules) and the plain values of the other ones of
         `learning_rate`, `clip_range`, `clip_range_vf`.  `ent_coef` / `vf_coef` are read back from `params`, i.e. as the
-        f32 the kernels get.  `bc_coef` is there (as a value, or under `scheduled`) only when it is set."""
+        f32 the kernels get.  `bc_coef` is there (as a value, or under `scheduled`) only when it is set, `exchange_world` and
+        `exchange_rank` only with an exchange (a checkpoint is per rank)."""
         hp = {"obs_dim": self.policy.obs_dim, "n_actions": self.policy.n_actions, "n_epochs": self.n_epochs,
               "batch_size": None if self.batch_size is None else int(self.batch_size), "gamma": self.gamma,
               "gae_lambda": self.gae_lambda, "ent_coef": float(self.params.ent_coef), "vf_coef": float(self.params.vf_coef),
@@ -362,6 +496,9 @@ class PPOLearner:
                 hp[name] = getattr(self, name)
         if self.bc_coef is not None and "bc_coef" not in self.schedules:
             hp["bc_coef"] = self.bc_coef
+        exchange = getattr(self, "exchange", None)
+        if exchange is not None:  # `seed` above is already (seed + rank) mod 2^64
+            hp.update(exchange_world=int(exchange.world), exchange_rank=int(exchange.rank))
         return hp
 
     def state_dict(self) -> dict:
@@ -464,7 +601,12 @@ class PPOLearner:
         progress_remaining: sets `self.progress_remaining` first; the schedules are then evaluated once, here.
         explained_variance=True: one `mse_explained_variance` over the rollout's values / returns behind GAE and before
         the first minibatch; its f32 comes to the host in the copy that brings the statistics, and the result gains
-        "explained_variance" (SB3's train/explained_variance; NaN when the returns are constant)."""
+        "explained_variance" (SB3's train/explained_variance; NaN when the returns are constant).
+        With an `exchange`: `data` is this rank's rollout, `batch_size` counts rows per rank, a minibatch is the three phases
+        with two all-reduces between them (class docstring), and "stats" / "mean" are those of the global minibatches,
+        identical on every rank; explained_variance=True is refused (it would be this rank's rows only)."""
+        if self.exchange is not None and explained_variance:
+            raise ValueError("explained_variance cannot be combined with an exchange: it would cover this rank's rows only")
         if progress_remaining is not None:
             self.progress_remaining = float(progress_remaining)
         self._resolve_schedules()
@@ -474,6 +616,9 @@ class PPOLearner:
         bs = self.batch_size if self.batch_size is not None else (total + 3) // 4
         bs = max(1, min(int(bs), total))
         per_epoch = (total + bs - 1) // bs
+        if self.exchange is not None:
+            bs, plan = self._shard_plan(total)
+            per_epoch = len(plan)
         n_mb = self.n_epochs * per_epoch
         gated = self.target_kl is not None
         names = STAT_NAMES if self.bc_coef is None else PPO_BC_STAT_NAMES[:11]
@@ -490,9 +635,12 @@ class PPOLearner:
         else:
             stats, control = torch.zeros((n_mb, w), dtype=torch.float32, device=self.device), None
         step0 = self.step
-        for i, rows in enumerate(self._minibatches(total, bs)):
-            self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
-            self.adam_step(control)
+        if self.exchange is not None:
+            self._sharded_minibatches(data, total, bs, plan, stats, control)
+        else:
+            for i, rows in enumerate(self._minibatches(total, bs)):
+                self.loss_grad(data, rows, rows.numel(), stats[i], control=control, target_kl=self.target_kl or 0.0)
+                self.adam_step(control)
         self._hand_over()
         if not gated:
             if ev is None:
@@ -514,7 +662,7 @@ class PPOLearner:
 
     def learn(self, collector, iterations: int, callback=None, episode_stats: bool = False, eval_collector=None,
               eval_freq: int = 0, n_eval_episodes: int = 10, explained_variance: bool = False, first_iteration: int = 0,
-              checkpoint_path=None, checkpoint_freq: int = 0, history: Optional[list] = None) -> list:
+              checkpoint_path=None, checkpoint_freq: int = 0, history: Optional[list] = None, check_sync: bool = False) -> list:
         """Alternates `collector.collect()` and `update()`; returns the per-iteration mean stats, each with the rollout's
         mean reward per env-step under "reward" (and, with `target_kl`, the update's "stopped" and "minibatches_run").
         episode_stats=True: each record gains `episodes`, `ep_rew_mean`, `ep_len_mean` over the episodes that ended in
@@ -537,7 +685,15 @@ class PPOLearner:
         `sort_policy` if it has one (under policies["sort_policy"]), iteration = it + 1, `iterations` and the history so
         far; an `{iteration}` field in checkpoint_path is filled in, so earlier files can be kept.  `eval_collector`'s
         env is not saved and needs no state: `evaluate_policy` resets it every time.  With the defaults nothing is
-        written and the loop is what it was."""
+        written and the loop is what it was.
+        With an `exchange` every rank calls `learn` with its own collector; a checkpoint is per rank (give each rank its own
+        checkpoint_path), explained_variance=True is refused, and check_sync=True adds `in_sync` to each record:
+        `exchange.same_on_all_ranks(weights)`, off by default because it reads back."""
+        if self.exchange is not None and explained_variance:
+            raise ValueError("learn(explained_variance=True) cannot be combined with an exchange: it would cover this rank's "
+                             "rows only")
+        if check_sync and self.exchange is None:
+            raise ValueError("check_sync needs an exchange")
         evaluate = self._evaluator(eval_collector, eval_freq, n_eval_episodes, keep_best=True)
 
         def step(data, progress_remaining):
@@ -554,6 +710,8 @@ class PPOLearner:
                 rec.update(bc_coef=self.bc_coef)
             if explained_variance:
                 rec.update(explained_variance=out["explained_variance"])
+            if check_sync:
+                rec.update(in_sync=self.exchange.same_on_all_ranks(self.weights))
             return rec
 
         def checkpoint(iteration, history):

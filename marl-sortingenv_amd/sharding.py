@@ -15,6 +15,10 @@ every rank contributes its step-major [K, n_local, ...] buffer as it stands, so 
 (xGMI is point-to-point: ~38.5 MB per rank per step at 262 144 envs) and never transposes.  Global env
 g = r * n_local + j sits at [r, :, j]; `step_major()` gives the [K, R, n_local, ...] view (no copy) and
 `to_step_major()` the contiguous [K, N, ...] copy for consumers that insist on it.
+
+A learner that wants every row of every rank is link-bound, so the data-parallel learner exchanges no rows:
+`GradientExchange` carries the two small all-reduces of a minibatch (`PPOLearner(exchange=...)`), and
+`shard_minibatch_plan` says which rows of its own rollout every rank contributes to which minibatch.
 """
 from __future__ import annotations
 
@@ -204,6 +208,76 @@ class RolloutExchange:
         if t is self._pending:
             self._pending = None
         return t.result
+
+
+def shard_minibatch_plan(totals, batch_size: int) -> list:
+    """The minibatches of one epoch of a data-parallel update, with no device and no collective in it.  totals[r]: the
+    rollout rows of rank r; batch_size: rows per minibatch PER RANK.  There are M = ceil(max(totals) / batch_size)
+    minibatches; rank r's j-th is rows [j * bs, min((j + 1) * bs, totals[r])) of its own permutation, so it may be short
+    or EMPTY (a rank with fewer rows still makes every collective call).  -> M lists of the R local sizes; a minibatch's
+    global_batch is their sum.  Totals 50 and 45 at batch_size 16: [[16, 16], [16, 16], [16, 13], [2, 0]]."""
+    totals, bs = [int(t) for t in totals], int(batch_size)
+    if not totals or min(totals) < 0 or max(totals) < 1:
+        raise ValueError(f"totals must be non-negative row counts, one per rank, at least one of them positive, not {totals!r}")
+    if bs < 1:
+        raise ValueError(f"batch_size must be >= 1, not {batch_size!r}")
+    m = (max(totals) + bs - 1) // bs
+    return [[max(0, min((j + 1) * bs, t) - j * bs) for t in totals] for j in range(m)]
+
+
+class GradientExchange:
+    """The collectives of a data-parallel learner (`PPOLearner(exchange=...)`): what crosses between ranks per minibatch
+    is four doubles and then the policy's gradient sums, never rollout rows.  Works on any backend (nccl = RCCL on ROCm;
+    gloo on CPU tensors in the host tests).  At world size 1 without `force_collective` every call is a no-op, as in
+    RolloutExchange.
+
+    `all_reduce_sum` and `broadcast` are enqueued on the current stream's ordering by the nccl backend and do not
+    synchronise the host; `same_on_all_ranks` is the one call that reads back."""
+
+    def __init__(self, group=None, device: Optional[torch.device] = None, force_collective: bool = False):
+        self.group = group
+        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        self.device = device
+        self.collective = self.world > 1 or (force_collective and dist.is_initialized())
+
+    def _global(self, rank: int) -> int:
+        return int(rank) if self.group is None else dist.get_global_rank(self.group, int(rank))
+
+    def all_reduce_sum(self, t: torch.Tensor) -> torch.Tensor:
+        """In place: t = the sum of every rank's t (f64 or f32, contiguous).  Every rank gets the same bits."""
+        if t.dtype not in (torch.float64, torch.float32):
+            raise ValueError(f"all_reduce_sum takes f64 or f32 tensors, not {t.dtype}")
+        if self.collective:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def broadcast(self, t: torch.Tensor, src: int = 0) -> torch.Tensor:
+        """In place: t = rank `src`'s t."""
+        if self.collective:
+            dist.broadcast(t, src=self._global(src), group=self.group)
+        return t
+
+    def all_gather_ints(self, value: int) -> list:
+        """-> [rank 0's value, rank 1's, ...] as host integers (reads back: once per rollout size, not per update)."""
+        if not self.collective:
+            return [int(value)]
+        dev = self.device if self.device is not None else torch.device("cpu")
+        mine = torch.tensor([int(value)], dtype=torch.int64, device=dev)
+        allv = torch.empty(self.world, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(allv, mine, group=self.group)
+        return [int(v) for v in allv.tolist()]
+
+    def same_on_all_ranks(self, t: torch.Tensor) -> bool:
+        """Do all ranks hold the same BITS in t (a tensor of 4-byte elements)?  MIN and MAX of the int32 view agree.
+        Reads back."""
+        if not self.collective:
+            return True
+        lo = t.contiguous().view(torch.int32).clone()
+        hi = lo.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=self.group)
+        dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=self.group)
+        return bool(torch.equal(lo, hi))
 
 
 class ShardedSortingEnv:

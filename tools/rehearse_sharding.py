@@ -8,6 +8,11 @@ the rollout buffers are all-gathered (the hand-off that is one RCCL all_gather_i
 multi-GPU node; here gloo on host copies), and rank 0 compares the gathered rollout with a single-handle run of the
 whole batch: bit for bit, over several rollouts.  On a multi-GPU node the same script runs with one GPU per rank over
 nccl (it picks the backend from the device count).
+
+Over nccl - one GPU per rank, or ONE rank on a one-GPU box (--nproc-per-node 1, where the collectives are forced on although
+the world is one) - it then rehearses the learner's leg: every rank collects a policy rollout of its own envs and runs one
+`PPOLearner(exchange=GradientExchange(force_collective=True)).update()` (per minibatch three phases with an all-reduce of four
+doubles and one of the gradient sums between them), and the ranks check that they ended with the same weights, bit for bit.
 """
 import os
 import sys
@@ -18,7 +23,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 import marl_sortingenv_amd as M  # noqa: E402
-from marl_sortingenv_amd.sharding import RolloutExchange, shard_range  # noqa: E402
+from marl_sortingenv_amd.sharding import GradientExchange, RolloutExchange, shard_range  # noqa: E402
 
 world, rank = int(os.environ["WORLD_SIZE"]), int(os.environ["RANK"])
 local_rank = int(os.environ.get("LOCAL_RANK", rank))
@@ -51,6 +56,23 @@ if rank == 0:
     print(f"sharding rehearsal {'OK' if ok else 'FAILED'}: {world} ranks x ~{G // world} envs on {n_dev} GPU(s), "
           f"{'gloo (shared device)' if shared else 'nccl'}, 3 rollouts of {K} steps identical to one handle of {G} envs",
           flush=True)
+if not shared:  # the learner's leg: the gradient all-reduce needs device tensors in the collective
+    D, A = M.OBS_DIM["mono"], M.NUM_ACTIONS["mono"]
+    pol = M.MlpPolicy.random_init(D, A, seed=1 + rank, device=dev)  # ranks start apart: the constructor's broadcast aligns them
+    lenv = M.BatchedSortingEnv(num_envs=n_local, device=dev, index_offset=start, auto_reset=True, **kw)
+    gx = GradientExchange(device=dev, force_collective=True)
+    learner = M.PPOLearner(pol, n_epochs=2, batch_size=4096, ent_coef=0.05, shuffle="device", weight_sync="device", target_kl=0.05,
+                           exchange=gx)
+    started_alike = gx.same_on_all_ranks(learner.weights)
+    out = learner.update(M.FusedPolicyRollout(lenv, pol, 16, seed=7).collect())
+    torch.cuda.synchronize()
+    in_sync = started_alike and gx.same_on_all_ranks(learner.weights) and gx.same_on_all_ranks(out["stats"])
+    ok = ok and in_sync
+    if rank == 0:
+        print(f"learner rehearsal {'OK' if in_sync else 'FAILED'}: {world} rank(s), collectives "
+              f"{'forced on' if world == 1 else 'on'}, one update of {out['stats'].shape[0]} minibatches "
+              f"({out['minibatches_run']} run), loss {out['mean']['loss']:+.4f}; weights and statistics identical on all ranks",
+              flush=True)
 dist.barrier()
 dist.destroy_process_group()
 sys.exit(0 if ok else 1)

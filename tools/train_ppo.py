@@ -58,6 +58,12 @@
                                                           # evaluation all on that view)
     python tools/train_ppo.py --time --time-section preview  # the preview launch (plain, with labels, with the mixture) beside
                                                           # the plain policy kernel at 65 536 and 262 144 envs; only when named
+    python -m torch.distributed.run --nproc-per-node 8 tools/train_ppo.py --kind mono --envs 262144 --data-parallel
+                                                          # one process per GPU: every rank steps its block of the global
+                                                          # envs and trains on its own rows; per minibatch the ranks
+                                                          # all-reduce four doubles and the gradient sums (RCCL); rank 0 prints
+    python tools/train_ppo.py --time --time-section exchange  # update() with a one-rank exchange, collectives forced on, beside
+                                                          # the plain update(): the fixed overhead of the phase split
 
 Prints the mean reward per env-step and the learner's mean statistics per iteration (a record that learning happens).
 """
@@ -162,6 +168,47 @@ def time_loss_grad(args):
         print(f"{args.kind} rows={rows}: " + ", ".join(f"{k} {v * 1e6:.1f} us ({rows / v / 1e6:.1f} M rows/s)" for k, v in res.items())
               + f"; collect {t_col * 1e6:.0f} us, update (10 epochs x 4 minibatches) "
               + ", ".join(f"shuffle={mode} " + " / ".join(f"{t * 1e3:.2f}" for t in ts) + " ms" for mode, ts in t_upd.items()))
+
+
+def time_exchange(args):
+    """The fixed overhead of the phase split: update() with a GradientExchange at world size 1, the collectives forced on
+    over RCCL (three phases and two all-reduces per minibatch), beside the plain update() (one mse_ppo_loss_grad per
+    minibatch) on the same rollout, at time_loss_grad's sizes.  One warm-up each, then three timed updates each,
+    alternating; every timed region ends in a device synchronise.  What the two collectives cost between GPUs is not in it."""
+    import torch.distributed as dist
+
+    from marl_sortingenv_amd.sharding import GradientExchange
+
+    D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    own_group = not dist.is_initialized()
+    if own_group:
+        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:29547", rank=0, world_size=1, device_id=dev)
+    try:
+        ex = GradientExchange(device=dev, force_collective=True)
+        for n in (256, 4096, 65536):
+            K = 16
+            pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
+            env = M.BatchedSortingEnv(kind=args.kind, num_envs=n, device=0, base_seed=args.seed, max_steps=50, auto_reset=True)
+            data = M.FusedPolicyRollout(env, pol, K, seed=args.seed).collect()
+            kw = dict(ent_coef=0.05, shuffle="device", weight_sync="device", arithmetic=args.arithmetic)
+            learners = {"plain": M.PPOLearner(pol, **kw), "exchange": M.PPOLearner(pol, exchange=ex, **kw)}
+            times = {name: [] for name in learners}
+            for rep in range(4):
+                for name, lrn in learners.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    lrn.update(data)
+                    torch.cuda.synchronize()
+                    if rep > 0:
+                        times[name].append(time.perf_counter() - t0)
+            print(f"{args.kind} rows={K * n}: update (10 epochs x 4 minibatches, shuffle=device, weight_sync=device, "
+                  f"arithmetic={args.arithmetic}) " + ", ".join(f"{name} " + " / ".join(f"{t * 1e3:.2f}" for t in ts) + " ms"
+                                                              for name, ts in times.items()))
+    finally:
+        if own_group:
+            dist.destroy_process_group()
 
 
 def time_weight_sync(args):
@@ -549,10 +596,16 @@ def main():
     ap.add_argument("--bc-schedule", choices=("const", "linear"), default="const",
                     help="with --bc-coef: linear is X times progress_remaining, which reaches 0 in the last iteration")
     ap.add_argument("--time", action="store_true")
-    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo", "modular_demo", "preview"),
+    ap.add_argument("--time-section", choices=("all", "loss_grad", "weight_sync", "arithmetic", "bc", "demo", "modular_demo", "preview",
+                                               "exchange"),
                     default="all",
                     help="with --time: run one block of the timings only; 'all' is every block but modular_demo (four collectors "
-                         "at 262 144 envs, the multi-launch twin among them) and preview, which run only when named, with any --kind")
+                         "at 262 144 envs, the multi-launch twin among them), preview and exchange (it brings up a process "
+                         "group), which run only when named, with any --kind")
+    ap.add_argument("--data-parallel", action="store_true",
+                    help="run under `python -m torch.distributed.run --nproc-per-node R`: every rank steps its block of the "
+                         "--envs global envs on its own GPU and keeps its rows; the update exchanges moments and gradient sums "
+                         "(PPOLearner(exchange=GradientExchange())); rank 0 prints.  --batch-size counts rows per rank")
     ap.add_argument("--checkpoint", default=None, metavar="PATH",
                     help="write the whole run state here (save_checkpoint); an {iteration} field keeps one file per checkpoint")
     ap.add_argument("--checkpoint-every", type=int, default=0, metavar="N",
@@ -575,11 +628,39 @@ def main():
             time_modular_demo(args)
         if args.time_section == "preview":
             time_preview(args)
+        if args.time_section == "exchange":
+            time_exchange(args)
         return
     D, A = M.OBS_DIM[args.kind], M.NUM_ACTIONS[args.kind]
     pol = M.MlpPolicy.random_init(D, A, seed=args.seed)
-    env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
-                              auto_reset=True)
+    exchange, rank, device = None, 0, 0
+    if args.data_parallel:
+        import torch.distributed as dist
+
+        from marl_sortingenv_amd.sharding import GradientExchange, shard_range
+
+        for flag, name in ((args.bc_coef is not None, "--bc-coef"), (args.explained_variance, "--explained-variance"),
+                           (args.pretrain, "--pretrain"), (args.resume or args.checkpoint, "--checkpoint / --resume")):
+            if flag:
+                raise SystemExit(f"--data-parallel does not go with {name}")
+        if "RANK" not in os.environ:
+            raise SystemExit("--data-parallel runs under `python -m torch.distributed.run --nproc-per-node R tools/train_ppo.py ...`")
+        device = int(os.environ.get("LOCAL_RANK", 0)) % torch.cuda.device_count()
+        torch.cuda.set_device(device)
+        dist.init_process_group("nccl", device_id=torch.device("cuda", device))  # RCCL: one GPU per rank
+        rank, world = dist.get_rank(), dist.get_world_size()
+        exchange = GradientExchange(device=torch.device("cuda", device))
+        # this rank's contiguous block of the global env indices (ShardedSortingEnv's rule): env g is seeded with seed + g
+        # and its policy stream keyed by g, so the rollouts of all ranks together are those of one handle of --envs envs
+        start, n_local = shard_range(args.envs, world, rank)
+        pol = M.MlpPolicy.random_init(D, A, seed=args.seed, device=device) if device != 0 else pol
+        env = M.BatchedSortingEnv(kind=args.kind, num_envs=n_local, device=device, base_seed=args.seed, max_steps=args.max_steps,
+                                  auto_reset=True, index_offset=start)
+        if rank == 0:
+            print(f"data-parallel: {world} ranks, {args.envs} global envs, rank 0 steps envs [{start}, {start + n_local})")
+    else:
+        env = M.BatchedSortingEnv(kind=args.kind, num_envs=args.envs, device=0, base_seed=args.seed, max_steps=args.max_steps,
+                                  auto_reset=True)
     # --bc-coef: the rollout PPO trains on, with the rule's label of every state it visits, in one launch
     col = M.FusedPolicyRollout(env, pol, args.steps, seed=args.seed, expert_labels=args.bc_coef is not None, view=args.view)
     lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
@@ -587,20 +668,24 @@ def main():
     bc_coef = (lambda p: args.bc_coef * p) if args.bc_coef is not None and args.bc_schedule == "linear" else args.bc_coef
     eval_col = None
     if args.eval_every > 0:
-        eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
+        eval_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=device, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
                                        auto_reset=True)
         eval_col = M.FusedPolicyRollout(eval_env, pol, min(args.max_steps, 50), seed=args.seed + 1, view=args.view)
     if args.pretrain and not args.resume:  # a resumed run's weights come from its checkpoint
         pretrain(args, pol, args.kind, args.view, "the policy", eval_col if args.dagger else None)
     learner = M.PPOLearner(pol, learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch_size, ent_coef=args.ent_coef,
                            seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, target_kl=args.target_kl,
-                           arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf, bc_coef=bc_coef)
-    print(f"{KINDS[args.kind]} ({D} -> {A}{', view=preview' if args.view == 'preview' else ''}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
-          f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}, "
-          f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}"
-          + (f", bc_coef {args.bc_coef:g} {args.bc_schedule}" if args.bc_coef is not None else ""))
+                           arithmetic=args.arithmetic, clip_range=clip, clip_range_vf=args.clip_range_vf, bc_coef=bc_coef,
+                           exchange=exchange)
+    if rank == 0:
+        print(f"{KINDS[args.kind]} ({D} -> {A}{', view=preview' if args.view == 'preview' else ''}), {args.envs} envs x {args.steps} steps per iteration, shuffle={args.shuffle}, "
+              f"weight_sync={args.weight_sync}, target_kl={args.target_kl}, arithmetic={args.arithmetic}, "
+              f"clip_range_vf={args.clip_range_vf}, lr {args.lr_schedule}, clip range {args.clip_schedule}"
+              + (f", bc_coef {args.bc_coef:g} {args.bc_schedule}" if args.bc_coef is not None else ""))
 
     def show(it, rec):
+        if rank != 0:  # the statistics are the global ones, identical on every rank; the reward is this rank's envs'
+            return
         print(f"it {it:3d} reward/step {rec['reward']:+.4f} loss {rec['loss']:+.4f} pg {rec['policy_loss']:+.4f} "
               f"vf {rec['value_loss']:.4f} ent {-rec['entropy_loss']:.3f} kl {rec['approx_kl']:.4f} clip {rec['clip_fraction']:.3f}")
 
@@ -611,6 +696,8 @@ def main():
             print(f"       learning_rate {rec['learning_rate']:.3e} clip_range {rec['clip_range']:.4f}")
         if "explained_variance" in rec:
             print(f"       explained_variance {rec['explained_variance']:+.4f}")
+        if "in_sync" in rec:
+            print(f"       weights identical on all ranks: {rec['in_sync']}")
         if "stopped" in rec:
             print(f"       minibatches run {rec['minibatches_run']}" + (" (stopped on target_kl)" if rec["stopped"] else ""))
         if "episodes" in rec:
@@ -635,11 +722,13 @@ def main():
     every = args.checkpoint_every if args.checkpoint_every > 0 else args.iterations
     learner.learn(col, args.iterations, callback=show, episode_stats=args.episode_stats, eval_collector=eval_col,
                   eval_freq=args.eval_every, explained_variance=args.explained_variance, first_iteration=first, history=history,
-                  checkpoint_path=args.checkpoint, checkpoint_freq=every if args.checkpoint else 0)
+                  checkpoint_path=args.checkpoint, checkpoint_freq=every if args.checkpoint else 0, check_sync=args.data_parallel)
     if eval_col is not None:
         learner.restore_best()
-    if args.save:
+    if args.save and rank == 0:
         torch.save(pol.state_dict(), args.save)
+    if args.data_parallel:
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":
