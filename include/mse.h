@@ -280,6 +280,14 @@ int mse_rollout_model(mse_env *env, struct mse_policy *sort_agent, struct mse_po
 int mse_trace_begin(mse_env *env, int64_t env_index, double *records_dev, int64_t capacity);
 int mse_trace_end(mse_env *env, int64_t *n_records_out);
 
+/* The same trace for EVERY env: records_dev is f64[capacity, MSE_TRACE_COLS, N], one plane of N doubles per column per
+ * step, so the store of one column by a wave is 64 consecutive doubles.  From the call on every mse_step stores the
+ * record of every env into step slot n_records (the values and their moment are those of the one-env trace; columns 38
+ * and 39 are not written), until mse_trace_end, which ends either kind of trace.  A step beyond `capacity` and any
+ * mse_rollout* while the trace is attached are refused exactly as with mse_trace_begin; beginning either kind of
+ * trace replaces the one attached.  The records are what mse_plant_scan (below) folds into per-episode rows. */
+int mse_trace_begin_all(mse_env *env, double *records_dev, int64_t capacity);
+
 /* The step counter t of the on-device policy stream (word = f(policy seed, global env index, t); every mse_step
  * advances it by 1, every mse_rollout by k_steps).  It is host-side handle state, not part of the state record:
  * a checkpoint that must reproduce an on-device-policy rollout saves it with mse_get_state's record and restores
@@ -951,6 +959,54 @@ int mse_episode_summary(int64_t n, int32_t slots, const int32_t *ep_count, const
                         double *summary, void *stream);
 int mse_episode_summary_host(int64_t n, int32_t slots, const int32_t *ep_count, const double *ledger_return,
                              const int32_t *ledger_length, double *summary);
+
+/* ---- Plant ledger: per-episode plant quantities of every env, out of the all-env trace ------------------------------------
+ * What the reference's dashboard reads off ONE env - reward_data's (r_sort, r_press) pairs, press_actions_per_timestep,
+ * the bale_count lists and _calculate_avg_bale_deviation (env_super.py:235-241, 661-687, 928-946; utils/plotting.py:32-48)
+ * - as one row of MSE_PLANT_COLS doubles per episode, for all N envs.  csrc/mse_plant_math.h specifies the arithmetic
+ * completely; the kernel and the host form run that one header.
+ *
+ * mse_plant_scan walks records f64[K, MSE_TRACE_COLS, N] (mse_trace_begin_all), one env per lane, steps k = 0 .. K - 1 in
+ * order.  Per step: first the N_BALE press_bale calls in order (n / S full bales; a remainder > remainder_units opens a
+ * bale; else it merges into the last bale of that material if the episode has one; else it opens one), then the N_LOG
+ * press-log codes, then the reward parts.  An episode closes at DONE != 0; its row is
+ *    0        length
+ *    1 2 3    sum REWARD, sum R_SORT, sum R_PRESS (float64 sums in step order)
+ *    4 5      presses started on press 1 / press 2 (codes 1, 2)
+ *    6        busy or invalid attempts (codes 111, 222)        7   no-ops (code 0)
+ *    8        OVERFLOW of the closing step                     9   material left in the containers at the closing step
+ *    10-14    bales of A..E after the merge rule               15-19  their mass
+ *    20-24    sum over bales of the stored quality in hundredths (a merge keeps the last bale's quality)
+ *    25-29    sum over bales of |size - S|, an integer (a merge replaces the last bale's term)
+ *    30 31    zero
+ * The reference's average bale deviation is (sum of 25-29) / (S x sum of 10-14), formed once outside the sums.
+ *   bale_standard_size S, remainder_units = floor(S x bale_remainder_threshold): mse_plant_params gives both
+ *   run        f64[MSE_PLANT_RUN_COLS, N]  the carry, read and written: rows 0-29 are the open episode's columns (8 and 9
+ *              stay 0), rows 30-34 the size of the last bale of A..E, row 35 is not touched.  Zero it once.
+ *   ep_count, targets, slots   as in mse_episode_scan; ledger f64[slots, MSE_PLANT_COLS, N] or NULL with slots 0: a counted
+ *              episode is stored at slot ep_count[i] while that is < slots; the carry is cleared at every episode end
+ *   totals     f64[1 + MSE_PLANT_COLS] or NULL, ADDED TO: [0] counted episodes, [1 + c] the sum of column c (column 8 as
+ *              overflow != 0).  Every column but 1-3 is integer-valued, so exact in any order.
+ *   workspace  mse_plant_workspace_bytes() bytes, 8-byte aligned, needed with totals
+ * Totals are reduced per wave, then over the workgroup's waves in LDS, one slab per workgroup goes to the workspace, a
+ * one-workgroup launch folds the slabs in index order: no atomics, equal inputs give bit-equal outputs.
+ * Refusals, all before any device call, in this order: k_steps < 1 or n < 1; records, run or ep_count NULL; slots < 0,
+ * or a ledger without slots, or slots without a ledger; bale_standard_size < 1 or remainder_units outside
+ * [0, bale_standard_size) (all MSE_ERR_INVALID_ARGUMENT); device form only: totals without a workspace
+ * (MSE_ERR_INVALID_ARGUMENT); records, run, ledger, totals or workspace not 8-byte aligned (MSE_ERR_ALIGNMENT); device
+ * form only: no HIP device (MSE_ERR_NO_DEVICE).  Nothing is written on a refusal.
+ * mse_plant_scan_host is the same on host arrays, envs in ascending order; it and mse_plant_params need no device.
+ * Per-env outputs (carry, ledger, ep_count) and the integer totals equal the device's bit for bit, totals 1-3 to rounding. */
+#define MSE_PLANT_COLS 32
+#define MSE_PLANT_RUN_COLS 36
+int64_t mse_plant_workspace_bytes(void);
+int mse_plant_scan(int32_t k_steps, int64_t n, const double *records, int32_t bale_standard_size, int32_t remainder_units,
+                   double *run, int32_t *ep_count, const int32_t *targets, int32_t slots, double *ledger, double *totals,
+                   void *workspace, void *stream);
+int mse_plant_scan_host(int32_t k_steps, int64_t n, const double *records, int32_t bale_standard_size, int32_t remainder_units,
+                        double *run, int32_t *ep_count, const int32_t *targets, int32_t slots, double *ledger, double *totals);
+/* out = {bale_standard_size, floor(bale_standard_size x bale_remainder_threshold)} as the handle's compiled config holds them */
+int mse_plant_params(const mse_env *env, int32_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@ MSE_PREVIEW_DETERMINISTIC = 1024
 MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
+MSE_PLANT_COLS, MSE_PLANT_RUN_COLS = 32, 36
 
 EXPORTS = [
     "mse_version", "mse_last_error", "mse_status_string", "mse_config_default", "mse_create",
@@ -37,6 +38,7 @@ EXPORTS = [
     "mse_rollout_policy_labelled", "mse_rollout_policy_labelled_check",
     "mse_rollout_modular_labelled", "mse_rollout_modular_labelled_check",
     "mse_mono_agent_obs", "mse_rollout_policy_preview", "mse_rollout_policy_preview_check",
+    "mse_trace_begin_all", "mse_plant_workspace_bytes", "mse_plant_scan", "mse_plant_scan_host", "mse_plant_params",
     "mse_ppo_shard_partial_len", "mse_ppo_shard_moments", "mse_ppo_shard_loss_grad", "mse_ppo_shard_finish",
 ]
 
@@ -172,6 +174,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_model_actions.argtypes = [vp, u32, vp, vp]
     L.mse_trace_begin.argtypes = [vp, i64, vp, i64]
     L.mse_trace_end.argtypes = [vp, C.POINTER(i64)]
+    L.mse_trace_begin_all.argtypes = [vp, vp, i64]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError if the library does not export what include/mse.h declares
     L.mse_tie_window.restype = u32
@@ -234,6 +237,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_episode_scan_host.argtypes = [i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.mse_episode_summary.argtypes = [i64, i32, vp, vp, vp, vp, vp]
     L.mse_episode_summary_host.argtypes = [i64, i32, vp, vp, vp, vp]
+    L.mse_plant_workspace_bytes.argtypes = []
+    L.mse_plant_workspace_bytes.restype = i64
+    L.mse_plant_scan.argtypes = [i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.mse_plant_scan_host.argtypes = [i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp]
+    L.mse_plant_params.argtypes = [vp, C.POINTER(i32 * 2)]
     if path is None:
         _lib = L
     else:

@@ -177,12 +177,24 @@ class BatchedSortingEnv:
             check(self.L.mse_model_actions(self._h, flags, _ptr(out), self._stream()))
         return out
 
-    # ---- opt-in trace of one env (the reference's dashboard ledgers) ---------------------------------
+    # ---- opt-in trace of one env, or of all (the reference's dashboard ledgers) ------------------------
     def trace_begin(self, env_index: int = 0, capacity: int = 4096) -> None:
         """From now on every step() appends one record f64[MSE_TRACE_COLS] for env `env_index` (mse_trace_begin)."""
         self._trace_buf = torch.zeros((int(capacity), MSE_TRACE_COLS), dtype=torch.float64, device=self.device)
         self._trace_n = 0
         check(self.L.mse_trace_begin(self._h, int(env_index), _ptr(self._trace_buf), int(capacity)))
+
+    def trace_begin_all(self, capacity: int) -> None:
+        """From now on every step() stores the record of EVERY env (mse_trace_begin_all): `trace_records()` is then
+        f64[n, MSE_TRACE_COLS, N], one plane of N doubles per column per step - what `PlantStats.update` scans and
+        `EnvTrace.from_records` reads.  capacity x 320 x N bytes of device memory; a buffer of the same capacity is
+        used again by the next call (records handed out earlier are views of it)."""
+        shape = (int(capacity), MSE_TRACE_COLS, self.num_envs)
+        buf = getattr(self, "_trace_all_buf", None)
+        if buf is None or tuple(buf.shape) != shape:
+            buf = self._trace_all_buf = torch.zeros(shape, dtype=torch.float64, device=self.device)
+        check(self.L.mse_trace_begin_all(self._h, _ptr(buf), int(capacity)))
+        self._trace_buf, self._trace_n = buf, 0
 
     def trace_records(self) -> torch.Tensor:
         """The records written so far (synchronises the stream); the trace stays attached."""
@@ -192,7 +204,7 @@ class BatchedSortingEnv:
         return self._trace_buf[: self._trace_n]
 
     def trace_end(self) -> torch.Tensor:
-        """Detaches the trace and returns its records f64[n, MSE_TRACE_COLS]."""
+        """Detaches the trace (of either kind) and returns its records, f64[n, MSE_TRACE_COLS] or f64[n, MSE_TRACE_COLS, N]."""
         rec = self.trace_records().clone()
         check(self.L.mse_trace_end(self._h, None))
         self._trace_buf = None

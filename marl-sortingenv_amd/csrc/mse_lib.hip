@@ -313,7 +313,9 @@ __device__ __forceinline__ int policy_action(const Env &e, uint32_t cur, const T
 // kernels
 // ==========================================================================================
 // TRACE: the launch also appends one record (include/mse.h MSE_TRACE_*) for env `trace_env` to trace_rec - the
-// opt-in single-env trace behind the reference's dashboard ledgers (mse_trace_begin).
+// opt-in single-env trace behind the reference's dashboard ledgers (mse_trace_begin) - or, with trace_env == kTraceAll,
+// the record of every env into the column planes f64[MSE_TRACE_COLS][n] at trace_rec (mse_trace_begin_all).
+constexpr long long kTraceAll = -2;
 template <int KIND, bool NOISE, bool LITERAL, bool TRACE = false, bool GEN = false>
 __global__ __launch_bounds__(kBlock) void k_step(Params P, uint4 *__restrict__ planes,
                                                  const uint32_t *__restrict__ table_image,
@@ -361,34 +363,36 @@ __global__ __launch_bounds__(kBlock) void k_step(Params P, uint4 *__restrict__ p
             for (int q = 0; q < 2; ++q) lg.code[q] = lg.mat[q] = lg.bmat[q] = lg.bn[q] = lg.bq[q] = -1;
         }
         StepResult r = env_step<KIND, NOISE, LITERAL, TRACE, GEN>(e, P, tb, a, sm, flags, bales, k, o, &lg);
-        if (TRACE && i == trace_env) {
-            // the state _log_step_data sees: after the step, before any auto-reset
-            double *t = trace_rec;
+        if (TRACE && (trace_env == kTraceAll || i == trace_env)) {
+            // the state _log_step_data sees: after the step, before any auto-reset.  One env: the record's columns lie
+            // side by side.  All envs: one plane of n doubles per column, a wave stores 64 neighbouring cells.
+            const long long ts = trace_env == kTraceAll ? P.n : 1;
+            double *t = trace_env == kTraceAll ? trace_rec + i : trace_rec;
             const uint32_t bw = stage_word(e.st_belt, P);
-            t[MSE_TRACE_ACTION] = (double)a;
-            t[MSE_TRACE_R_SORT] = r.r_sort;
-            t[MSE_TRACE_R_PRESS] = r.r_press;
-            t[MSE_TRACE_SETTING] = (double)e.mode;
+            t[MSE_TRACE_ACTION * ts] = (double)a;
+            t[MSE_TRACE_R_SORT * ts] = r.r_sort;
+            t[MSE_TRACE_R_PRESS * ts] = r.r_press;
+            t[MSE_TRACE_SETTING * ts] = (double)e.mode;
             for (int m = 0; m < 4; ++m) {
-                t[MSE_TRACE_BELT + m] = (double)((bw >> (8 * m)) & 0xFFu);
-                t[MSE_TRACE_CONT_TRUE + m] = (double)e.ct[m];
-                t[MSE_TRACE_CONT_FALSE + m] = (double)e.cf[m];
+                t[(MSE_TRACE_BELT + m) * ts] = (double)((bw >> (8 * m)) & 0xFFu);
+                t[(MSE_TRACE_CONT_TRUE + m) * ts] = (double)e.ct[m];
+                t[(MSE_TRACE_CONT_FALSE + m) * ts] = (double)e.cf[m];
             }
-            t[MSE_TRACE_CONT_E] = (double)e.ce;
-            t[MSE_TRACE_N_LOG] = (double)lg.n_log;
-            t[MSE_TRACE_N_BALE] = (double)lg.n_bale;
+            t[MSE_TRACE_CONT_E * ts] = (double)e.ce;
+            t[MSE_TRACE_N_LOG * ts] = (double)lg.n_log;
+            t[MSE_TRACE_N_BALE * ts] = (double)lg.n_bale;
             for (int q = 0; q < 2; ++q) {
-                t[MSE_TRACE_LOG + 2 * q] = (double)lg.code[q];
-                t[MSE_TRACE_LOG + 2 * q + 1] = (double)lg.mat[q];
-                t[MSE_TRACE_BALE + 3 * q] = (double)lg.bmat[q];
-                t[MSE_TRACE_BALE + 3 * q + 1] = (double)lg.bn[q];
-                t[MSE_TRACE_BALE + 3 * q + 2] = (double)lg.bq[q];
+                t[(MSE_TRACE_LOG + 2 * q) * ts] = (double)lg.code[q];
+                t[(MSE_TRACE_LOG + 2 * q + 1) * ts] = (double)lg.mat[q];
+                t[(MSE_TRACE_BALE + 3 * q) * ts] = (double)lg.bmat[q];
+                t[(MSE_TRACE_BALE + 3 * q + 1) * ts] = (double)lg.bn[q];
+                t[(MSE_TRACE_BALE + 3 * q + 2) * ts] = (double)lg.bq[q];
             }
-            t[MSE_TRACE_DONE] = (double)r.done;
-            t[MSE_TRACE_STEP] = (double)e.step;
-            t[MSE_TRACE_INTERNAL] = (double)lg.internal;
-            t[MSE_TRACE_REWARD] = r.reward;
-            for (int m = 0; m < 4; ++m) t[MSE_TRACE_ACC_BELT + m] = e.acc[m];
+            t[MSE_TRACE_DONE * ts] = (double)r.done;
+            t[MSE_TRACE_STEP * ts] = (double)e.step;
+            t[MSE_TRACE_INTERNAL * ts] = (double)lg.internal;
+            t[MSE_TRACE_REWARD * ts] = r.reward;
+            for (int m = 0; m < 4; ++m) t[(MSE_TRACE_ACC_BELT + m) * ts] = e.acc[m];
             int ovf = 0; // env_super.py:900-905 detect_overflow: the first material above capacity
             if ((flags & MSE_STEP_CHECK_OVERFLOW) && r.done) {
                 for (int m = 4; m >= 0; --m) {
@@ -396,7 +400,7 @@ __global__ __launch_bounds__(kBlock) void k_step(Params P, uint4 *__restrict__ p
                     if (lvl > P.capacity) ovf = m + 1;
                 }
             }
-            t[MSE_TRACE_OVERFLOW] = (double)ovf;
+            t[MSE_TRACE_OVERFLOW * ts] = (double)ovf;
         }
         if (r.done && P.auto_reset) {
             if (terminal_obs_out != nullptr) {
@@ -2316,7 +2320,8 @@ struct mse_env {
     bool literal;                // evaluate every Generator.choice draw in literal fp64
     RolloutKernel rollout;       // mse_rollout's kernel (plan_rollout, at create)
     uint64_t policy_t;
-    // opt-in trace of one env (mse_trace_begin): records_dev f64[capacity][MSE_TRACE_COLS], caller-owned
+    // opt-in trace (caller-owned records_dev): of one env (mse_trace_begin), f64[capacity][MSE_TRACE_COLS], or of all
+    // (mse_trace_begin_all, trace_env == kTraceAll), f64[capacity][MSE_TRACE_COLS][n]
     double *trace_rec;
     int64_t trace_env, trace_capacity, trace_count;
     int cus;                     // compute units of the device
@@ -2392,8 +2397,9 @@ template <int KIND>
 static void launch_step(mse_env *h, hipStream_t s, const int32_t *action, const int32_t *sort_mode, uint32_t flags,
                         float *obs, float *rew, double *rew64, uint8_t *done, uint8_t *mask, float *tobs)
 {
-    const bool traced = h->trace_rec != nullptr; // the traced variant: one more record for env trace_env
-    double *rec = traced ? h->trace_rec + h->trace_count * MSE_TRACE_COLS : nullptr;
+    const bool traced = h->trace_rec != nullptr; // the traced variant: one more record for env trace_env, or for all
+    const long long rec_stride = h->trace_env == kTraceAll ? (long long)MSE_TRACE_COLS * h->P.n : MSE_TRACE_COLS;
+    double *rec = traced ? h->trace_rec + h->trace_count * rec_stride : nullptr;
     with_flags([&](auto NOISE, auto LIT, auto TRACE, auto GEN) {
         hipLaunchKernelGGL((k_step<KIND, NOISE, LIT, TRACE, GEN>), grid_of(h), dim3(kBlock), lds_bytes_step<KIND>(h), s,
                            h->P, h->planes, h->tables, action, sort_mode, flags, obs, rew, rew64, done, mask, tobs,
@@ -3226,6 +3232,25 @@ int mse_trace_begin(mse_env *h, int64_t env_index, double *records_dev, int64_t 
     h->trace_env = env_index;
     h->trace_capacity = capacity;
     h->trace_count = 0;
+    return MSE_OK;
+}
+
+int mse_trace_begin_all(mse_env *h, double *records_dev, int64_t capacity)
+{
+    if (!h || !records_dev) return fail(MSE_ERR_INVALID_ARGUMENT, "env/records_dev is NULL");
+    if (capacity < 1) return fail(MSE_ERR_INVALID_ARGUMENT, "capacity must be >= 1");
+    h->trace_rec = records_dev;
+    h->trace_env = kTraceAll;
+    h->trace_capacity = capacity;
+    h->trace_count = 0;
+    return MSE_OK;
+}
+
+int mse_plant_params(const mse_env *h, int32_t out[2])
+{
+    if (!h || !out) return fail(MSE_ERR_INVALID_ARGUMENT, "env/out is NULL");
+    out[0] = h->P.balesize;
+    out[1] = h->P.rem_thr_units;
     return MSE_OK;
 }
 

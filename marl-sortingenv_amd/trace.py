@@ -3,9 +3,10 @@
 The reference appends to three ledgers every step - `reward_data` (src/envs_train/env_super.py:402-408, 928-946),
 `press_actions_per_timestep` (:631-637, 730-736; env_monolith.py:136; env_2_press.py:131) and the `bale_count`
 lists (:661-687) - and its dashboard reads them off the env (utils/plotting.py:32-48).  Unbounded lists cannot live
-per GPU lane, so the engine keeps O(1) summaries for all envs and offers this opt-in trace for ONE env index:
-`mse_trace_begin` makes every `mse_step` write one fixed-size record (include/mse.h MSE_TRACE_*); `EnvTrace` turns
-records into the reference's ledger objects, in the reference's formats.  Pure NumPy: no torch, no device code.
+per GPU lane, so the engine keeps O(1) summaries for all envs and offers an opt-in trace: `mse_trace_begin` makes every
+`mse_step` write one fixed-size record (include/mse.h MSE_TRACE_*) for ONE env index, `mse_trace_begin_all` for every env
+(column planes [n, 40, N]; plant.py folds those into per-episode rows on the device).  `EnvTrace` turns the records of one
+env into the reference's ledger objects, in the reference's formats.  Pure NumPy: no torch, no device code.
 """
 from __future__ import annotations
 
@@ -84,6 +85,31 @@ class EnvTrace:
         for r in np.asarray(records, dtype=np.float64).reshape(-1, len(records[0]) if len(records) else 40):
             self.append(r)
         return self
+
+    @classmethod
+    def from_records(cls, records, env_index: int, bale_standard_size: int = 200, bale_remainder_threshold: float = 0.5,
+                     episode: int | None = None):
+        """The ledgers of env `env_index` out of an all-env trace, records [n, 40, N] (`trace_begin_all`; a tensor or an
+        array).  episode=None feeds every record; episode=j only those of the j-th episode that begins in the records
+        (episodes are split after each record with DONE != 0), as the reference's ledgers are cleared by reset()."""
+        if hasattr(records, "detach"):
+            records = records.detach().cpu().numpy()
+        records = np.asarray(records, dtype=np.float64)
+        if records.ndim != 3 or records.shape[1] != 40 or not 0 <= int(env_index) < records.shape[2]:
+            raise ValueError("records must be [n, 40, N] with 0 <= env_index < N")
+        rows = records[:, :, int(env_index)]
+        if episode is not None:
+            ends = np.flatnonzero(rows[:, DONE] != 0)
+            starts = np.concatenate(([0], ends + 1))
+            if not 0 <= int(episode) < len(starts) or starts[int(episode)] >= len(rows):
+                raise IndexError("no such episode in the records")
+            lo = starts[int(episode)]
+            later = ends[ends >= lo]
+            rows = rows[lo:(later[0] + 1 if len(later) else len(rows))]
+        tr = cls(bale_standard_size, bale_remainder_threshold)
+        for r in rows:
+            tr.append(r)
+        return tr
 
     def as_arrays(self):
         """The ledgers as plain arrays, keys as the fixtures' `ledger_*` (oracle/ref_harness.py ledgers)."""

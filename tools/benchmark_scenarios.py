@@ -18,6 +18,7 @@ launches per step) for each agent combination at --envs envs and K = --k steps.
 
     python tools/benchmark_scenarios.py [--envs 65536] [--sort-weights F] [--press-weights F] [--mono-weights F]
     python tools/benchmark_scenarios.py --time [--envs 65536] [--k 200]
+    python tools/benchmark_scenarios.py --plant [--envs 4096]      the plant ledger beside the reward (multi-launch stepping)
 """
 import argparse
 import os
@@ -36,6 +37,9 @@ ap.add_argument("--press-weights", default=None, help="... of the pressing agent
 ap.add_argument("--mono-weights", default=None, help="... of the monolithic agent (29 -> 22)")
 ap.add_argument("--time", action="store_true", help="env-steps/s of the fused model rollout vs ModelRolloutCollector")
 ap.add_argument("--k", type=int, default=200, help="steps per rollout for --time")
+ap.add_argument("--plant", action="store_true",
+                help="also print the plant ledger of the scenarios (evaluate_plant: one episode per seed through the all-env "
+                     "trace, 50 x 320 B x envs of device memory): the return's parts, press log, overflow, bales, deviation")
 args = ap.parse_args()
 n, T = args.envs, 200
 
@@ -142,3 +146,17 @@ for label, run, note in (
         ("PPO Monolith, masking", lambda: mono_reward(make(), mono_ag, True), mono_note)):
     r = run()
     print(f"{label:24s} {n} seeds: cumulative reward {float(r.mean()):8.2f} +- {float(r.std()):6.2f}{note}")
+
+if args.plant:
+    from marl_sortingenv_amd.plant import evaluate_plant, format_summary
+
+    for label, source in (
+            ("Random, masking", lambda e: (e, "random")),
+            ("Rule-Based, masking", lambda e: (e, "rule_based")),
+            ("mode=model, no agents", lambda e: M.ModelRolloutCollector(e)),
+            ("PPO Modular, masking" + (sort_note or press_note), lambda e: M.ModelRolloutCollector(e, sort_ag, press_ag))):
+        env = make()
+        s = evaluate_plant(source(env), n_eval_episodes=n, k_steps=50)
+        print(f"{label}: {n} seeds: cumulative reward {s['mean_reward']:8.2f} +- {s['std_reward']:6.2f}")
+        print(format_summary(s))
+        env.close()

@@ -536,6 +536,15 @@ def train_modular(args):
             print(f"cloned pair, before PPO: eval (mode='model', both agents) {mean:+.3f} +- {std:.3f}")
     M.ModularTrainer(col, learners[0], learners[1], reward=args.reward).learn(
         args.iterations, callback=show, episode_stats=args.episode_stats, eval_env=eval_env, eval_freq=args.eval_every)
+    if args.eval_plant:  # why the pair scores what it scores: the plant ledger of 10 episodes in mode='model'
+        from marl_sortingenv_amd.plant import evaluate_plant, format_summary
+
+        plant_env = M.BatchedSortingEnv(kind="mono", num_envs=10, device=0, base_seed=args.seed + 10 ** 6, max_steps=args.max_steps,
+                                        auto_reset=True)
+        s = evaluate_plant(M.ModelRolloutCollector(plant_env, sort_ag, press_ag, press_agent_maskable=col.press_masked),
+                           k_steps=min(args.max_steps, 50))
+        print(f"plant ledger (mode='model', both agents): eval {s['mean_reward']:+.3f} +- {s['std_reward']:.3f}")
+        print(format_summary(s))
     if args.save:
         torch.save({"sort_agent": sort_ag.state_dict(), "press_agent": press_ag.state_dict()}, args.save)
 
@@ -565,6 +574,9 @@ def main():
                     help="SB3's target_kl: stop an update after the minibatch whose approx_kl exceeds 1.5 times this")
     ap.add_argument("--episode-stats", action="store_true",
                     help="print the episodes that ended in each rollout with their mean return and length (SB3's ep_rew_mean)")
+    ap.add_argument("--eval-plant", action="store_true",
+                    help="after training print the plant ledger of 10 evaluation episodes (evaluate_plant): the return's sort "
+                         "and press parts, press log counts, overflow rate, bales per material, average bale deviation")
     ap.add_argument("--eval-every", type=int, default=0,
                     help="every this many iterations evaluate_policy (10 deterministic episodes) and keep the best weights")
     ap.add_argument("--arithmetic", choices=("fma", "matrix"), default="fma",
@@ -725,6 +737,15 @@ def main():
                   checkpoint_path=args.checkpoint, checkpoint_freq=every if args.checkpoint else 0, check_sync=args.data_parallel)
     if eval_col is not None:
         learner.restore_best()
+    if args.eval_plant and rank == 0:  # why the policy scores what it scores: the plant ledger of 10 deterministic episodes
+        from marl_sortingenv_amd.plant import evaluate_plant, format_summary
+
+        plant_env = M.BatchedSortingEnv(kind=args.kind, num_envs=10, device=device, base_seed=args.seed + 10 ** 6,
+                                        max_steps=args.max_steps, auto_reset=True)
+        plant_col = M.PolicyRolloutCollector(plant_env, pol, min(args.max_steps, 50), seed=args.seed + 1, view=args.view)
+        s = evaluate_plant(plant_col, collect_kwargs={"deterministic": True})
+        print(f"plant ledger: eval {s['mean_reward']:+.3f} +- {s['std_reward']:.3f}")
+        print(format_summary(s))
     if args.save and rank == 0:
         torch.save(pol.state_dict(), args.save)
     if args.data_parallel:
