@@ -1008,6 +1008,56 @@ int mse_plant_scan_host(int32_t k_steps, int64_t n, const double *records, int32
 /* out = {bale_standard_size, floor(bale_standard_size x bale_remainder_threshold)} as the handle's compiled config holds them */
 int mse_plant_params(const mse_env *env, int32_t out[2]);
 
+/* ---- Lookahead: fork every env and score each candidate action in ONE launch (the rollout algorithm's inner loop) ----------
+ * Per env i, candidate action a < A (A = mse_num_actions) and sample m < n_samples, the fork is a copy of env i's current
+ * state held in registers, stepped with masking on (use_action_masking=True; MSE_STEP_CHECK_OVERFLOW honoured):
+ *   - a candidate that the current action_masks() forbids runs no step and gets q = -inf;
+ *   - step 0 is mse_step's transition under action a; steps s = 1 .. horizon - 1 take the base policy's action for the
+ *     fork's state: base_policy = 1 what mse_rule_actions returns for it, base_policy = 0 the masked-uniform action
+ *     mse_sample_actions draws with the policy stream's word of (base_seed, index_offset + i, s) (csrc/mse_policy_stream.h:
+ *     the word at s under the key of base_seed and the index) - it depends on neither a nor m: common random numbers; Env_2's sorting decision
+ *     is sort_mode_dev[i] at every step of the fork (NULL: sorting_rules());
+ *   - the fork ends with its episode (max_steps, or an overflow under MSE_STEP_CHECK_OVERFLOW): there is no auto-reset
+ *     inside a fork, and steps after `done` add nothing;
+ *   - ret = sum over the steps taken of disc_s * reward64_s in double, formed in step order as acc += disc * r;
+ *     disc *= gamma, every operation rounded on its own (no fused multiply-add), acc = 0 and disc = 1 at the start;
+ *   - q_out[a][i] = (ret_0 + ... + ret_{M-1}) / M, added in sample order, in double (every fork writes its return to the
+ *     workspace, f64[M][A][N]; a second small kernel forms the mean and the argmax);
+ *   - action_out[i] = the legal candidate of largest q, ties to the lowest index; value_out[i] = that q;
+ *   - streams = 0 ("own"): every PCG64 stream of the fork continues the env's own: the fork sees the draws the env itself
+ *     is going to see (clairvoyant: an upper bound, and the form that can be held against real stepping);
+ *   - streams = 1 ("fresh"): every stream column of the fork's state record (the rng block of mse_get_state) is the one
+ *     mse_reset gives an env seeded with mse_lookahead_stream_seed(lookahead_seed, index_offset + i, m); everything else,
+ *     the seasonal generator's position included, stays the env's.  The candidate is not part of the key: the candidates of
+ *     one env and sample share their draws.  With streams = 0 the samples are copies of one another;
+ *   - nothing of the handle is written: state planes, policy step counter, bale ledger, trace and error count stay; a
+ *     fork's press_bale bookings go to a ledger that discards them (nothing a step computes reads the ledger).
+ * mse_lookahead_stream_seed (host, pure; csrc/mse_lookahead_seed.h is the one definition, for host and device): with
+ * mix(z) { z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31); }
+ * and arithmetic modulo 2^64:  a = mix(lookahead_seed + 0x9E3779B97F4A7C15);  b = mix(a ^ global_env_index);
+ * c = mix(b + (sample + 1) * 0x9E3779B97F4A7C15);  the seed is c >> 1 (below 2^63).
+ * Shape: one lane per (env, candidate, sample), grid (ceil(N / 256), A, M) x 256 threads, the lookup tables in LDS; one
+ * launch of it and one of the reduction, both on `stream`; no allocation, no synchronisation.  Works on a handle with or
+ * without auto_reset, with or without an attached trace, and with literal_choice.
+ *   q_out f64[A][N]; action_out i32[N] or NULL; value_out f64[N] or NULL; workspace: mse_lookahead_workspace_bytes(env,
+ *   n_samples) bytes of device memory (8 N A M; a negative mse_status for a NULL env or n_samples out of range).
+ * Refusals, all before any device call, in this order: MSE_ERR_INVALID_ARGUMENT - a NULL env, q_out or workspace;
+ * horizon < 1 or > MSE_LOOKAHEAD_MAX_HORIZON; n_samples < 1 or > MSE_LOOKAHEAD_MAX_SAMPLES; gamma not a number in [0, 1];
+ * base_policy or streams outside {0, 1}; a flag other than MSE_STEP_CHECK_OVERFLOW; sort_mode_dev on a kind other than
+ * Env_2.  MSE_ERR_UNSUPPORTED_CONFIG - general generator mode (the fork does not carry the input generator's private
+ * stream).  MSE_ERR_NOT_RESET - a handle not yet reset.  MSE_ERR_ALIGNMENT - q_out, value_out or workspace not 8-byte
+ * aligned.  A handle exists only on a device (mse_create's MSE_ERR_NO_DEVICE), so there is no such refusal here.  A refused
+ * call writes nothing. */
+#define MSE_LOOKAHEAD_MAX_HORIZON 65535 /* = the largest max_steps: no fork runs longer */
+#define MSE_LOOKAHEAD_MAX_SAMPLES 256
+int64_t  mse_lookahead_workspace_bytes(const mse_env *env, int32_t n_samples);
+uint64_t mse_lookahead_stream_seed(uint64_t lookahead_seed, uint64_t global_env_index, uint32_t sample);
+int mse_lookahead(mse_env *env, int32_t horizon, double gamma, int32_t base_policy /* 0 random, 1 rule_based */,
+                  uint64_t base_seed, int32_t streams /* 0 own, 1 fresh */, uint64_t lookahead_seed, int32_t n_samples,
+                  const int32_t *sort_mode_dev /* Env_2, or NULL */, uint32_t flags /* MSE_STEP_CHECK_OVERFLOW or 0 */,
+                  double *q_out /* f64[A][N] */, int32_t *action_out /* i32[N] or NULL */, double *value_out /* f64[N] or NULL */,
+                  void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .config import KIND_BY_NAME, NUM_ACTIONS, OBS_DIM, SortingEnvConfig
 
 __all__ = [
     "BatchedSortingEnv", "Env_1_Sorting", "Env_2_Pressing", "Env_3_Monolith", "SortingVecEnv",
-    "ShardedSortingEnv", "GradientExchange", "shard_minibatch_plan", "MlpPolicy", "PolicyRolloutCollector", "FusedPolicyRollout", "ModelRolloutCollector", "FusedModularRollout", "ModularRolloutCollector", "ModularTrainer", "PPOLearner", "PPO_BC_STAT_NAMES", "DemonstrationCollector", "FusedDemonstrationRollout", "expert_threshold", "ImitationLearner", "compute_gae", "resolve_schedule", "EpisodeStats", "evaluate_policy", "evaluate_rollout", "PlantStats", "evaluate_plant", "EnvTrace", "save_checkpoint", "load_checkpoint", "SortingEnvConfig", "MseError", "build_library", "load_library", "library_path",
+    "ShardedSortingEnv", "GradientExchange", "shard_minibatch_plan", "MlpPolicy", "PolicyRolloutCollector", "FusedPolicyRollout", "ModelRolloutCollector", "FusedModularRollout", "ModularRolloutCollector", "ModularTrainer", "PPOLearner", "PPO_BC_STAT_NAMES", "DemonstrationCollector", "FusedDemonstrationRollout", "expert_threshold", "ImitationLearner", "compute_gae", "resolve_schedule", "EpisodeStats", "evaluate_policy", "evaluate_rollout", "PlantStats", "evaluate_plant", "lookahead_reference", "LookaheadCollector", "evaluate_lookahead", "EnvTrace", "save_checkpoint", "load_checkpoint", "SortingEnvConfig", "MseError", "build_library", "load_library", "library_path",
     "KIND_BY_NAME", "OBS_DIM", "NUM_ACTIONS", "MSE_ENV_SORT", "MSE_ENV_PRESS", "MSE_ENV_MONO",
     "MSE_STEP_UNMASKED", "MSE_STEP_CHECK_OVERFLOW", "MSE_SNAP_INTS",
 ]
@@ -46,6 +46,9 @@ def __getattr__(name):  # torch-dependent front-ends are imported on first use
     if name in ("PlantStats", "evaluate_plant"):
         from . import plant
         return getattr(plant, name)
+    if name in ("lookahead_reference", "LookaheadCollector", "evaluate_lookahead"):
+        from . import lookahead
+        return getattr(lookahead, name)
     if name == "EnvTrace":
         from .trace import EnvTrace
         return EnvTrace

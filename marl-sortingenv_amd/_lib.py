@@ -17,6 +17,7 @@ MSE_SNAP_INTS = 71
 MSE_SNAP_RNG_WORDS = 30  # rng, rng_noise, rng_pressing, rng_sorting, input generator x {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}
 MSE_TRACE_COLS = 40
 MSE_PLANT_COLS, MSE_PLANT_RUN_COLS = 32, 36
+MSE_LOOKAHEAD_MAX_HORIZON, MSE_LOOKAHEAD_MAX_SAMPLES = 65535, 256
 
 EXPORTS = [
     "mse_version", "mse_last_error", "mse_status_string", "mse_config_default", "mse_create",
@@ -40,6 +41,7 @@ EXPORTS = [
     "mse_mono_agent_obs", "mse_rollout_policy_preview", "mse_rollout_policy_preview_check",
     "mse_trace_begin_all", "mse_plant_workspace_bytes", "mse_plant_scan", "mse_plant_scan_host", "mse_plant_params",
     "mse_ppo_shard_partial_len", "mse_ppo_shard_moments", "mse_ppo_shard_loss_grad", "mse_ppo_shard_finish",
+    "mse_lookahead_workspace_bytes", "mse_lookahead_stream_seed", "mse_lookahead",
 ]
 
 _other_libs: dict = {}
@@ -242,6 +244,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_plant_scan.argtypes = [i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.mse_plant_scan_host.argtypes = [i32, i64, vp, i32, i32, vp, vp, vp, i32, vp, vp]
     L.mse_plant_params.argtypes = [vp, C.POINTER(i32 * 2)]
+    L.mse_lookahead_workspace_bytes.argtypes = [vp, i32]
+    L.mse_lookahead_workspace_bytes.restype = i64
+    L.mse_lookahead_stream_seed.argtypes = [u64, u64, u32]
+    L.mse_lookahead_stream_seed.restype = u64
+    L.mse_lookahead.argtypes = [vp, i32, C.c_double, i32, u64, i32, u64, i32, vp, u32, vp, vp, vp, vp, vp]
     if path is None:
         _lib = L
     else:

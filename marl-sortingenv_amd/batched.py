@@ -291,6 +291,52 @@ class BatchedSortingEnv:
                                            _ptr(buffers.get("press_obs")), self._stream()))
         return buffers
 
+    # ---- lookahead: every env forked once per candidate action and sample, in one launch (mse_lookahead) ---------------
+    def lookahead(self, horizon: int, gamma: float = 1.0, base_policy: str = "rule_based", streams: str = "fresh", seed: int = 0,
+                  base_seed: int = 2024, n_samples: int = 1, sort_mode: Optional[torch.Tensor] = None,
+                  check_overflow: bool = False, out: Optional[dict] = None) -> dict:
+        """The rollout algorithm's inner loop in one `mse_lookahead` call, no host copy: per env, every action is tried on a
+        copy of the env's current state and followed by horizon - 1 steps of `base_policy` ("rule_based" | "random", the
+        latter drawn with `base_seed`); q[a, i] is the mean discounted return over `n_samples` forks, -inf where
+        `action_masks()` forbids a; `action` the legal candidate of largest q (ties: the lowest), `value` its q.
+        streams="fresh": sample m of env i draws from the streams of `reset(seed=mse_lookahead_stream_seed(seed,
+        index_offset + i, m))`; streams="own": the fork continues the env's own streams (clairvoyant).  The env is not
+        touched.  Returns {"q": f64[A, N], "action": i32[N], "value": f64[N]}; out: the dict of an earlier call, written again
+        and returned (the workspace is kept by the env and grows with n_samples).  include/mse.h has the full contract;
+        `lookahead.lookahead_reference` is the multi-launch twin."""
+        if base_policy not in ("rule_based", "random"):
+            raise ValueError(f"base_policy must be 'rule_based' or 'random', not {base_policy!r}")
+        if streams not in ("fresh", "own"):
+            raise ValueError(f"streams must be 'fresh' or 'own', not {streams!r}")
+        if int(horizon) < 1:
+            raise ValueError("horizon must be >= 1")
+        if int(n_samples) < 1:
+            raise ValueError("n_samples must be >= 1")
+        if sort_mode is not None:
+            sort_mode = sort_mode.to(device=self.device, dtype=torch.int32).contiguous()
+            if sort_mode.numel() != self.num_envs:
+                raise ValueError("sort_mode must have one entry per env")
+        n, A, dev = self.num_envs, self.num_actions, self.device
+        need = int(self.L.mse_lookahead_workspace_bytes(self._h, int(n_samples)))
+        if need < 0:
+            check(need)
+        ws = getattr(self, "_lookahead_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._lookahead_ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        if out is None:
+            out = {"q": torch.empty((A, n), dtype=torch.float64, device=dev), "action": torch.empty((n,), dtype=torch.int32, device=dev),
+                   "value": torch.empty((n,), dtype=torch.float64, device=dev)}
+        for key, shape, dt in (("q", (A, n), torch.float64), ("action", (n,), torch.int32), ("value", (n,), torch.float64)):
+            t = out.get(key)
+            if t is None or t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"out[{key!r}] must be a contiguous {dt} device tensor of shape {shape}")
+        with torch.cuda.device(self.device):
+            check(self.L.mse_lookahead(self._h, int(horizon), float(gamma), 1 if base_policy == "rule_based" else 0, int(base_seed),
+                                       1 if streams == "fresh" else 0, int(seed), int(n_samples), _ptr(sort_mode),
+                                       MSE_STEP_CHECK_OVERFLOW if check_overflow else 0, _ptr(out["q"]), _ptr(out["action"]),
+                                       _ptr(out["value"]), _ptr(ws), self._stream()))
+        return out
+
     # ---- state export / import (tests, checkpoint, dashboard trace) ---------------------------
     def get_state(self):
         n, dev = self.num_envs, self.device

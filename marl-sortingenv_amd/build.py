@@ -10,7 +10,7 @@ REPO_ROOT = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", "mse_lib.hip"), os.path.join(PKG_DIR, "csrc", "mse_policy.hip"),
            os.path.join(PKG_DIR, "csrc", "mse_ppo.hip"), os.path.join(PKG_DIR, "csrc", "mse_ppo_matrix.hip"),
            os.path.join(PKG_DIR, "csrc", "mse_episode.hip"), os.path.join(PKG_DIR, "csrc", "mse_plant.hip")]
-HEADERS = [os.path.join(PKG_DIR, "csrc", h) for h in ("mse_device.h", "mse_exact.h", "mse_host.h", "mse_params.h", "mse_plan.h", "mse_tables.h", "mse_policy_device.h", "mse_policy_pack.h", "mse_policy_stream.h", "mse_demo_mix.h", "mse_ppo_math.h", "mse_ppo_grad.h", "mse_ppo_grad_body.inc", "mse_ppo_matrix_body.inc", "mse_rollout_policy_body.inc", "mse_rollout_modular_body.inc", "mse_plain_frame.inc", "mse_episode_math.h", "mse_plant_math.h")] + \
+HEADERS = [os.path.join(PKG_DIR, "csrc", h) for h in ("mse_device.h", "mse_exact.h", "mse_host.h", "mse_params.h", "mse_plan.h", "mse_tables.h", "mse_policy_device.h", "mse_policy_pack.h", "mse_policy_stream.h", "mse_demo_mix.h", "mse_lookahead_seed.h", "mse_ppo_math.h", "mse_ppo_grad.h", "mse_ppo_grad_body.inc", "mse_ppo_matrix_body.inc", "mse_rollout_policy_body.inc", "mse_rollout_modular_body.inc", "mse_plain_frame.inc", "mse_episode_math.h", "mse_plant_math.h")] + \
           [os.path.join(REPO_ROOT, "include", "mse.h")]
 LIB_PATH = os.environ.get("MSE_LIB_PATH") or os.path.join(PKG_DIR, "libmse_hip.so")  # override: experiments only
 

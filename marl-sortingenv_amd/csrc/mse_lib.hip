@@ -6,6 +6,7 @@
 #include "mse_device.h"
 #include "mse_demo_mix.h" // after mse_device.h: MSE_HD needs the HIP runtime header
 #include "mse_host.h"
+#include "mse_lookahead_seed.h"
 #include "mse_plan.h"
 #include "mse_policy_device.h"
 #include "mse_tables.h"
@@ -506,6 +507,100 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
 #pragma unroll
         for (int m = 0; m < 5; ++m) planes[(long long)(PL_BALE0 + m) * P.n_pad + i] = bales.load(m);
     }
+}
+
+// ==========================================================================================
+// Lookahead (mse_lookahead): one lane per (env, candidate action, sample).  The lane forks the env - a copy
+// of its state in registers -, steps the candidate, follows it with horizon - 1 steps of the base policy and leaves the
+// discounted return in the workspace; nothing of the handle is written.  The candidate and the sample are the grid's y and
+// z, so a wave's 64 lanes are 64 neighbouring envs under one candidate: the state loads are k_rollout's coalesced loads
+// and a wave never diverges on the candidate (only on what the envs' masks forbid and on where their episodes end).
+// ==========================================================================================
+// The ledger of a fork: a fork's bale bookings are discarded.  press_bale only ever writes the ledger - no transition,
+// reward, observation or mask reads it -, so a fork that kept one would compute the same returns and throw it away.
+struct BaleDiscard {
+    __device__ __forceinline__ uint4 load(int) const { return make_uint4(0, 0, 0, 0); }
+    __device__ __forceinline__ void store(int, const uint4 &) const {}
+};
+
+// LDS: the table image up to the jump tables, nothing else (no output row is staged: the one output is a double per lane)
+template <int KIND, bool NOISE, bool LITERAL>
+__global__ __launch_bounds__(kBlock) void k_lookahead(Params P, const uint4 *__restrict__ planes,
+                                                      const uint32_t *__restrict__ table_image, int horizon, double gamma,
+                                                      uint32_t flags, uint64_t base_seed, int fresh, uint64_t lookahead_seed,
+                                                      const int *__restrict__ sort_mode, double *__restrict__ returns)
+{
+    constexpr int D = Dims<KIND>::D, A = Dims<KIND>::A;
+    uint32_t *ltab = reinterpret_cast<uint32_t *>(mse_dyn_lds);
+    const int tid = threadIdx.x;
+    const long long i = (long long)blockIdx.x * kBlock + tid; // i < n_pad always: the planes are padded to whole workgroups
+    const int cand = (int)blockIdx.y;
+    const uint32_t sample = blockIdx.z;
+
+    Env e;
+    load_env<KIND, NOISE>(e, planes, P, i); // in flight while the tables are copied
+    load_tables_to_lds(ltab, table_image, P.off_jump, tid); // off_jump is a multiple of 4 words
+    const Tables tb = tables_at(ltab, P);
+    if (i >= P.n) return;
+    const int sm = (KIND == 2 && sort_mode != nullptr) ? sort_mode[i] : -1;
+
+    uint32_t cur_mask = action_mask_bits<KIND>(e, P);
+    double ret = -__builtin_inf(); // a candidate the current action_masks() forbids: no step is run
+    if ((cur_mask >> cand) & 1u) {
+        const uint64_t g = (uint64_t)(P.index_offset + i);
+        if (fresh) { // the streams mse_reset gives an env seeded with the fork's seed (k_reset); the generator's position stays
+            const uint64_t seed = mse_lookahead_seed_of(lookahead_seed, g, sample);
+            e.rng = pcg_seed(seed + 99);
+            if (NOISE) e.noise = pcg_seed(seed + 4);
+            if (KIND == 1) {
+                e.press = pcg_seed(seed + 3);
+                e.press_has = 0;
+                e.press_uint = 0;
+            }
+        }
+        const uint32_t pkey = mse_policy_key(base_seed, g);
+        const BaleDiscard bales{};
+        double disc = 1.0;
+        int a = cand;
+        ret = 0.0;
+        for (int s = 0;;) {
+            float o[D];
+            int k[4];
+            const StepResult r = env_step<KIND, NOISE, LITERAL, false, false, BaleDiscard>(e, P, tb, a, sm, flags, bales, k, o);
+            ret = __dadd_rn(ret, __dmul_rn(disc, r.reward)); // acc += disc * r, two roundings
+            disc = __dmul_rn(disc, gamma);
+            if (r.done || ++s >= horizon) break; // the fork ends with its episode: no auto-reset
+            cur_mask = action_mask_bits<KIND>(e, P);
+            a = policy_action<KIND, false>(e, cur_mask, tb, flags, pkey, (uint64_t)s);
+        }
+    }
+    returns[((long long)sample * A + cand) * P.n + i] = ret;
+}
+
+// q[a][i] = (ret_0 + ... + ret_{M-1}) / M in sample order; the legal candidate of largest q, ties to the lowest index
+// (a forbidden candidate's returns are all -inf, so is its mean, and no legal one's is)
+template <int A>
+__global__ __launch_bounds__(kBlock) void k_lookahead_reduce(long long n, int n_samples, const double *__restrict__ returns,
+                                                             double *__restrict__ q_out, int *__restrict__ action_out,
+                                                             double *__restrict__ value_out)
+{
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double best = -__builtin_inf();
+    int best_a = 0;
+    const double count = (double)n_samples;
+    for (int a = 0; a < A; ++a) {
+        double sum = returns[(long long)a * n + i];
+        for (int m = 1; m < n_samples; ++m) sum = __dadd_rn(sum, returns[((long long)m * A + a) * n + i]);
+        const double q = sum / count;
+        q_out[(long long)a * n + i] = q;
+        if (q > best) {
+            best = q;
+            best_a = a;
+        }
+    }
+    if (action_out != nullptr) action_out[i] = best_a;
+    if (value_out != nullptr) value_out[i] = best;
 }
 
 // ==========================================================================================
@@ -2874,6 +2969,60 @@ int mse_rollout(mse_env *h, int32_t k_steps, uint64_t policy_seed, const int32_t
     });
     MSE_CHECK_LAUNCH();
     h->policy_t += (uint64_t)k_steps;
+    return MSE_OK;
+}
+
+// ---- lookahead: the fork kernel and its reduction (include/mse.h) ----
+int64_t mse_lookahead_workspace_bytes(const mse_env *h, int32_t n_samples)
+{
+    if (!h) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_workspace_bytes: env is NULL");
+    if (n_samples < 1 || n_samples > MSE_LOOKAHEAD_MAX_SAMPLES)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_workspace_bytes: n_samples must be in [1, MSE_LOOKAHEAD_MAX_SAMPLES]");
+    return (int64_t)sizeof(double) * n_samples * mse_num_actions(h) * h->P.n; // f64[M][A][N]: one return per fork
+}
+
+uint64_t mse_lookahead_stream_seed(uint64_t lookahead_seed, uint64_t global_env_index, uint32_t sample)
+{
+    return mse_lookahead_seed_of(lookahead_seed, global_env_index, sample);
+}
+
+int mse_lookahead(mse_env *h, int32_t horizon, double gamma, int32_t base_policy, uint64_t base_seed, int32_t streams,
+                  uint64_t lookahead_seed, int32_t n_samples, const int32_t *sort_mode, uint32_t flags, double *q_out,
+                  int32_t *action_out, double *value_out, void *workspace, void *stream)
+{
+    const auto aligned8 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; };
+    if (!h || !q_out || !workspace) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: env / q_out / workspace is NULL");
+    if (horizon < 1 || horizon > MSE_LOOKAHEAD_MAX_HORIZON)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: horizon must be in [1, MSE_LOOKAHEAD_MAX_HORIZON]");
+    if (n_samples < 1 || n_samples > MSE_LOOKAHEAD_MAX_SAMPLES)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: n_samples must be in [1, MSE_LOOKAHEAD_MAX_SAMPLES]");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: gamma must be a number in [0, 1]");
+    if (base_policy < 0 || base_policy > 1 || streams < 0 || streams > 1)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: base_policy is 0 (random) | 1 (rule_based), streams 0 (own) | 1 (fresh)");
+    if (flags & ~MSE_STEP_CHECK_OVERFLOW)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: the only flag is MSE_STEP_CHECK_OVERFLOW (a fork steps with masking on)");
+    if (sort_mode && h->P.env_kind != MSE_ENV_PRESS)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead: sort_mode_dev is Env_2's sorting decision; this kind has none");
+    if (h->P.gen_mode)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_lookahead: general generator mode is not served (the fork does not carry the "
+                                                "input generator's private stream): fork with mse_get_state / mse_set_state");
+    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_lookahead before mse_reset(seeds)");
+    if (!aligned8(q_out) || !aligned8(value_out) || !aligned8(workspace))
+        return fail(MSE_ERR_ALIGNMENT, "mse_lookahead: q_out / value_out / workspace must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *returns = static_cast<double *>(workspace);
+    const uint32_t kflags = flags | (base_policy == 1 ? MSE_ROLLOUT_RULE_BASED : 0u);
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        constexpr int A = Dims<KIND>::A;
+        const dim3 grid((unsigned)(h->P.n_pad / kBlock), (unsigned)A, (unsigned)n_samples);
+        with_flags([&](auto NOISE, auto LIT) {
+            hipLaunchKernelGGL((k_lookahead<KIND, NOISE, LIT>), grid, dim3(kBlock), (size_t)h->P.off_jump * 4u, s, h->P, h->planes,
+                               h->tables, horizon, gamma, kflags, base_seed, streams, lookahead_seed, sort_mode, returns);
+        }, h->noise_on, h->literal);
+        hipLaunchKernelGGL(k_lookahead_reduce<A>, grid_of(h), dim3(kBlock), 0, s, (long long)h->P.n, n_samples, returns, q_out,
+                           action_out, value_out);
+    });
+    MSE_CHECK_LAUNCH();
     return MSE_OK;
 }
 

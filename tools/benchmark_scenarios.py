@@ -19,6 +19,8 @@ launches per step) for each agent combination at --envs envs and K = --k steps.
     python tools/benchmark_scenarios.py [--envs 65536] [--sort-weights F] [--press-weights F] [--mono-weights F]
     python tools/benchmark_scenarios.py --time [--envs 65536] [--k 200]
     python tools/benchmark_scenarios.py --plant [--envs 4096]      the plant ledger beside the reward (multi-launch stepping)
+    python tools/benchmark_scenarios.py --planner 1 4 16 [--envs 10] [--planner-streams fresh] [--planner-samples 1]
+                                                                   the lookahead planner (mse_lookahead) at these horizons
 """
 import argparse
 import os
@@ -40,6 +42,12 @@ ap.add_argument("--k", type=int, default=200, help="steps per rollout for --time
 ap.add_argument("--plant", action="store_true",
                 help="also print the plant ledger of the scenarios (evaluate_plant: one episode per seed through the all-env "
                      "trace, 50 x 320 B x envs of device memory): the return's parts, press log, overflow, bales, deviation")
+ap.add_argument("--planner", type=int, nargs="+", default=None, metavar="H",
+                help="only the planner scenario: at every step each env takes the action BatchedSortingEnv.lookahead(H) ranks "
+                     "first (every action tried on a fork, followed by H - 1 rule-based steps), one row per horizon")
+ap.add_argument("--planner-streams", default="fresh", choices=("fresh", "own"), help="the forks' streams ('own' is clairvoyant)")
+ap.add_argument("--planner-samples", type=int, default=1, help="forks per candidate action")
+ap.add_argument("--planner-base", default="rule_based", choices=("rule_based", "random"), help="the forks' base policy")
 args = ap.parse_args()
 n, T = args.envs, 200
 
@@ -103,6 +111,21 @@ def timed(fn):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e-3
 
+
+if args.planner:
+    from marl_sortingenv_amd.plant import evaluate_plant, format_summary
+
+    kw = dict(streams=args.planner_streams, n_samples=args.planner_samples, base_policy=args.planner_base)
+    r = total_reward(make(), "rule_based")
+    print(f"{'Rule-Based, masking':24s} {n} seeds: cumulative reward {float(r.mean()):8.2f} +- {float(r.std(unbiased=False)):6.2f}")
+    for H in args.planner:
+        env = make()
+        mean, std = M.evaluate_lookahead(env, n, H, **kw)
+        print(f"{'Planner H=' + str(H):24s} {n} seeds: cumulative reward {mean:8.2f} +- {std:6.2f}   ({kw})", flush=True)
+        if args.plant:
+            print(format_summary(evaluate_plant(M.LookaheadCollector(env, 50, H, gamma=1.0, seed=0, **kw), n_eval_episodes=n)))
+        env.close()
+    sys.exit(0)
 
 if args.time:
     K = args.k

@@ -56,6 +56,10 @@
                                                           # after the step's flow update, as the modular agents are
                                                           # (mse_rollout_policy_preview: cloning, DAgger, --bc-coef and the
                                                           # evaluation all on that view)
+    python tools/train_ppo.py --kind mono --pretrain lookahead --horizon 8 --eval-every 10
+                                                          # the teacher is the lookahead planner (LookaheadCollector: every
+                                                          # action tried on a fork of the env and followed by H - 1 rule-based
+                                                          # steps, one mse_lookahead launch per step); --dagger: the clone steps
     python tools/train_ppo.py --time --time-section preview  # the preview launch (plain, with labels, with the mixture) beside
                                                           # the plain policy kernel at 65 536 and 262 144 envs; only when named
     python -m torch.distributed.run --nproc-per-node 8 tools/train_ppo.py --kind mono --envs 262144 --data-parallel
@@ -438,16 +442,21 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
     of its own, ImitationLearner); the PPO learner constructed afterwards starts from the cloned weights."""
     env = M.BatchedSortingEnv(kind=env_kind, num_envs=args.envs, device=0, base_seed=args.seed + 2 * 10 ** 6,
                               max_steps=args.max_steps, auto_reset=True)
-    if args.dagger:
+    planner = args.pretrain == "lookahead"
+    if planner:  # the planner labels the env's own observation; with --dagger the student steps, without it the planner
+        col = M.LookaheadCollector(env, args.steps, args.horizon, actor=pol if args.dagger else None, seed=args.seed + 7,
+                                   n_samples=args.lookahead_samples)
+    elif args.dagger:
         col = M.FusedDemonstrationRollout(env, args.steps, actor=pol, beta=1.0, seed=args.seed + 7, mix_seed=args.seed + 8,
                                           agent="preview" if agent == "preview" else "own")
     else:
         col = M.DemonstrationCollector(env, args.steps, agent=agent)
     il = M.ImitationLearner(pol, learning_rate=args.pretrain_lr, n_epochs=args.pretrain_epochs, batch_size=args.batch_size,
                             seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, arithmetic=args.arithmetic)
-    print(f"cloning the rule-based controller into {name} ({pol.obs_dim} -> {pol.n_actions}): {args.pretrain_iterations} "
+    print(f"cloning {f'the lookahead planner (H = {args.horizon})' if planner else 'the rule-based controller'} into {name} ({pol.obs_dim} -> {pol.n_actions}): {args.pretrain_iterations} "
           f"iterations of {args.envs} envs x {args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}"
-          + (f", DAgger with beta schedule '{args.beta_schedule}'" if args.dagger else ""))
+          + (", the student steps" if planner and args.dagger else
+             f", DAgger with beta schedule '{args.beta_schedule}'" if args.dagger else ""))
 
     def show(it, rec):
         print(f"bc {it:3d} reward/step of the {'mixture' if args.dagger else 'expert'} {rec['reward']:+.4f} loss {rec['loss']:+.4f} "
@@ -457,7 +466,7 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
 
     return il.learn(col, args.pretrain_iterations, callback=show, eval_collector=eval_col,
                     eval_freq=args.eval_every if eval_col is not None else 0,
-                    beta=BETA_SCHEDULES[args.beta_schedule] if args.dagger else None)
+                    beta=BETA_SCHEDULES[args.beta_schedule] if args.dagger and not planner else None)
 
 
 def pretrain_modular_dagger(args, sort_ag, press_ag):
@@ -589,9 +598,13 @@ def main():
                     help="linear: the clip range 0.2 times progress_remaining")
     ap.add_argument("--explained-variance", action="store_true",
                     help="print SB3's train/explained_variance of each rollout's values against its returns")
-    ap.add_argument("--pretrain", choices=("rule_based",), default=None,
+    ap.add_argument("--pretrain", choices=("rule_based", "lookahead"), default=None,
                     help="clone the env's rule-based controller into the policy first (ImitationLearner), then run PPO from there; "
-                         "--kind modular clones the sorting and the pressing agent from their own views of Env_3")
+                         "--kind modular clones the sorting and the pressing agent from their own views of Env_3.  lookahead: the "
+                         "teacher is the planner instead (LookaheadCollector: every action tried on a fork and followed by "
+                         "--horizon - 1 rule-based steps); with --dagger the policy being cloned steps the envs")
+    ap.add_argument("--horizon", type=int, default=8, metavar="H", help="with --pretrain lookahead: the planner's horizon")
+    ap.add_argument("--lookahead-samples", type=int, default=1, metavar="M", help="with --pretrain lookahead: forks per candidate")
     ap.add_argument("--pretrain-iterations", type=int, default=20, metavar="N",
                     help="with --pretrain: collections of --envs x --steps demonstrations, each followed by one update")
     ap.add_argument("--pretrain-epochs", type=int, default=4, help="with --pretrain: epochs per update")
@@ -629,6 +642,10 @@ def main():
     args = ap.parse_args()
     if args.view == "preview" and args.kind != "mono":
         raise SystemExit("--view preview is the mono policy's in-step view: it goes with --kind mono")
+    if args.pretrain == "lookahead" and (args.kind == "modular" or args.view != "own"):
+        raise SystemExit("--pretrain lookahead labels the env's own observation: it goes with --kind sort | press | mono and --view own")
+    if args.pretrain == "lookahead" and args.horizon < 1:
+        raise SystemExit("--horizon must be >= 1")
     if args.kind == "modular" and not (args.time and args.time_section in ("modular_demo", "preview")):
         return train_modular(args)
     if args.time:
