@@ -1058,6 +1058,46 @@ int mse_lookahead(mse_env *env, int32_t horizon, double gamma, int32_t base_poli
                   double *q_out /* f64[A][N] */, int32_t *action_out /* i32[N] or NULL */, double *value_out /* f64[N] or NULL */,
                   void *workspace, void *stream);
 
+/* ---- Lookahead with a learned network inside the fork: the policy as base, the critic as leaf value -------
+ * mse_lookahead's sentence - forks, candidates, samples, step 0, the end of a fork with its episode, ret, q_out, action_out,
+ * value_out, both stream modes, sort_mode_dev, MSE_STEP_CHECK_OVERFLOW, the workspace (mse_lookahead_workspace_bytes), the
+ * reduction, "nothing of the handle is written" and the fork's discarded bale ledger - with two changes:
+ *   - the base policy: base_policy = 0 and 1 are mse_lookahead's (base_deterministic is ignored for them); with base_policy = 2
+ *     steps s = 1 .. horizon - 1 take the action mse_policy_forward(policy, ...) returns for the fork's current state: its
+ *     arguments are the fork's observation and action_masks() (masking always on), seed = base_seed, t = s, index_offset + i
+ *     as the global env index and deterministic = base_deterministic.  base_deterministic != 0: the argmax of the masked
+ *     logits, ties to the lowest index.  base_deterministic == 0: inverse-cdf sampling with the policy stream's word of
+ *     (base_seed, index_offset + i, s) - the same word for every candidate and sample of an env (common random numbers),
+ *     the rule base_policy = 0 follows;
+ *   - the leaf value: with leaf_value = 1 a fork that has taken `horizon` steps and whose last step did not end its episode
+ *     adds the critic's value of the state it stands in: ret = ret + disc * (double)v, the product and the sum rounded on
+ *     their own, disc as the step loop left it (gamma multiplied in `horizon` times), v the f32 `value` mse_policy_forward
+ *     returns for that state's observation.  A fork that ended with its episode adds nothing.  horizon = 1 with the leaf
+ *     is the TD-greedy policy of the critic.
+ * The policy's precision form (f32 or f16x3) is the handle's current one, as in mse_rollout_policy; its weights are read
+ * when the launch runs (a learner that updates the handle in place is seen by the next call).  Neither handle is written.
+ * Shape: mse_lookahead's grid, (ceil(N / 256), A, M) x 256 threads; a wave is 64 neighbouring envs under one candidate and
+ * sample and runs the network on the matrix cores for its own 64 forks (two 32-env tiles), observations from registers;
+ * LDS holds one policy weight image and the lookup tables.  The matrix work is done for whole waves, whatever share of
+ * their lanes are legal forks.  One launch of it and one of the reduction, both on `stream`; no allocation, no
+ * synchronisation.  Works with or without auto_reset and with or without an attached trace.
+ * Refusals, all before any device call, in this order: mse_lookahead's MSE_ERR_INVALID_ARGUMENT refusals in its order - a NULL
+ * env, q_out or workspace; horizon < 1 or > MSE_LOOKAHEAD_MAX_HORIZON; n_samples < 1 or > MSE_LOOKAHEAD_MAX_SAMPLES; gamma
+ * not a number in [0, 1]; base_policy outside {0, 1, 2} or streams outside {0, 1}; a flag other than
+ * MSE_STEP_CHECK_OVERFLOW; sort_mode_dev on a kind other than Env_2 -; then MSE_ERR_INVALID_ARGUMENT - a NULL policy; a policy
+ * whose dimensions are not the env's obs_dim -> num_actions, or that lives on another device; leaf_value outside {0, 1};
+ * base_policy != 2 with leaf_value == 0 (the network has nothing to do: mse_lookahead is the call).
+ * MSE_ERR_UNSUPPORTED_CONFIG - general generator mode; a literal_choice handle; a config whose tables do not fit the LDS
+ * beside the weight image.  MSE_ERR_NOT_RESET - a handle not yet reset.  MSE_ERR_ALIGNMENT - q_out, value_out or workspace not
+ * 8-byte aligned.  A refused call writes nothing. */
+int mse_lookahead_net(mse_env *env, mse_policy *policy, int32_t horizon, double gamma,
+                      int32_t base_policy /* 0 random, 1 rule_based, 2 network */, int32_t base_deterministic,
+                      uint64_t base_seed, int32_t leaf_value /* 0 or 1 */, int32_t streams /* 0 own, 1 fresh */,
+                      uint64_t lookahead_seed, int32_t n_samples, const int32_t *sort_mode_dev /* Env_2, or NULL */,
+                      uint32_t flags /* MSE_STEP_CHECK_OVERFLOW or 0 */, double *q_out /* f64[A][N] */,
+                      int32_t *action_out /* i32[N] or NULL */, double *value_out /* f64[N] or NULL */, void *workspace,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

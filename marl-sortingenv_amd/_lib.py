@@ -42,6 +42,7 @@ EXPORTS = [
     "mse_trace_begin_all", "mse_plant_workspace_bytes", "mse_plant_scan", "mse_plant_scan_host", "mse_plant_params",
     "mse_ppo_shard_partial_len", "mse_ppo_shard_moments", "mse_ppo_shard_loss_grad", "mse_ppo_shard_finish",
     "mse_lookahead_workspace_bytes", "mse_lookahead_stream_seed", "mse_lookahead",
+    "mse_lookahead_net",
 ]
 
 _other_libs: dict = {}
@@ -249,6 +250,7 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.mse_lookahead_stream_seed.argtypes = [u64, u64, u32]
     L.mse_lookahead_stream_seed.restype = u64
     L.mse_lookahead.argtypes = [vp, i32, C.c_double, i32, u64, i32, u64, i32, vp, u32, vp, vp, vp, vp, vp]
+    L.mse_lookahead_net.argtypes = [vp, vp, i32, C.c_double, i32, i32, u64, i32, i32, u64, i32, vp, u32, vp, vp, vp, vp, vp]
     if path is None:
         _lib = L
     else:

@@ -22,6 +22,33 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+LOOKAHEAD_BASES = ("random", "rule_based")  # mse_lookahead's base_policy codes 0 and 1; 2 is the network (mse_lookahead_net)
+
+
+def lookahead_network(base_policy, leaf_value):
+    """(network or None, base_policy code) of a lookahead call.  base_policy: one of the two strings or a policy object
+    (`MlpPolicy`); leaf_value: None or a policy object.  The kernel holds one weight image, so two different objects for
+    base and leaf are a ValueError."""
+    if isinstance(base_policy, str):
+        if base_policy not in LOOKAHEAD_BASES:
+            raise ValueError(f"base_policy must be 'rule_based' or 'random', not {base_policy!r}")
+        base_net, code = None, LOOKAHEAD_BASES.index(base_policy)
+    elif base_policy is None or not all(hasattr(base_policy, k) for k in ("obs_dim", "n_actions")):
+        raise ValueError(f"base_policy must be 'rule_based', 'random' or an MlpPolicy, not {base_policy!r}")
+    else:
+        base_net, code = base_policy, 2
+    if leaf_value is not None and not all(hasattr(leaf_value, k) for k in ("obs_dim", "n_actions")):
+        raise ValueError(f"leaf_value must be None or an MlpPolicy, not {leaf_value!r}")
+    if base_net is not None and leaf_value is not None and base_net is not leaf_value:
+        raise ValueError("base_policy and leaf_value must be the same MlpPolicy object: the lookahead kernel holds one weight image")
+    return (base_net if base_net is not None else leaf_value), code
+
+
+def _other_device(a, b) -> bool:
+    a, b = torch.device(a), torch.device(b)
+    return a.type != b.type or (a.index is not None and b.index is not None and a.index != b.index)
+
+
 class BatchedSortingEnv:
     """N independent Env_1_Sorting / Env_2_Pressing / Env_3_Monolith instances on one MI355X.
 
@@ -292,9 +319,10 @@ class BatchedSortingEnv:
         return buffers
 
     # ---- lookahead: every env forked once per candidate action and sample, in one launch (mse_lookahead) ---------------
-    def lookahead(self, horizon: int, gamma: float = 1.0, base_policy: str = "rule_based", streams: str = "fresh", seed: int = 0,
+    def lookahead(self, horizon: int, gamma: float = 1.0, base_policy="rule_based", streams: str = "fresh", seed: int = 0,
                   base_seed: int = 2024, n_samples: int = 1, sort_mode: Optional[torch.Tensor] = None,
-                  check_overflow: bool = False, out: Optional[dict] = None) -> dict:
+                  check_overflow: bool = False, out: Optional[dict] = None, leaf_value=None,
+                  base_deterministic: bool = True) -> dict:
         """The rollout algorithm's inner loop in one `mse_lookahead` call, no host copy: per env, every action is tried on a
         copy of the env's current state and followed by horizon - 1 steps of `base_policy` ("rule_based" | "random", the
         latter drawn with `base_seed`); q[a, i] is the mean discounted return over `n_samples` forks, -inf where
@@ -303,9 +331,16 @@ class BatchedSortingEnv:
         index_offset + i, m))`; streams="own": the fork continues the env's own streams (clairvoyant).  The env is not
         touched.  Returns {"q": f64[A, N], "action": i32[N], "value": f64[N]}; out: the dict of an earlier call, written again
         and returned (the workspace is kept by the env and grows with n_samples).  include/mse.h has the full contract;
-        `lookahead.lookahead_reference` is the multi-launch twin."""
-        if base_policy not in ("rule_based", "random"):
-            raise ValueError(f"base_policy must be 'rule_based' or 'random', not {base_policy!r}")
+        `lookahead.lookahead_reference` is the multi-launch twin.
+        With a network (`mse_lookahead_net`): base_policy may be an `MlpPolicy` - steps 1 .. horizon - 1 take its
+        `forward(obs, mask, seed=base_seed, t=s)` action, the argmax with base_deterministic (the default), a sample
+        otherwise -, and leaf_value an `MlpPolicy` whose critic's value of the state a fork stands in after `horizon` steps
+        is added with the running discount unless the fork's episode ended.  The kernel holds one weight image: base and
+        leaf must be the same object.  The handle is live: every call plans with the policy's current weights."""
+        net, base_code = lookahead_network(base_policy, leaf_value)
+        if net is not None and (net.obs_dim != self.obs_dim or net.n_actions != self.num_actions or
+                                _other_device(net.device, self.device)):
+            raise ValueError(f"the lookahead's network must be a {self.obs_dim} -> {self.num_actions} policy on {self.device}")
         if streams not in ("fresh", "own"):
             raise ValueError(f"streams must be 'fresh' or 'own', not {streams!r}")
         if int(horizon) < 1:
@@ -330,11 +365,17 @@ class BatchedSortingEnv:
             t = out.get(key)
             if t is None or t.dtype != dt or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
                 raise ValueError(f"out[{key!r}] must be a contiguous {dt} device tensor of shape {shape}")
+        flags = MSE_STEP_CHECK_OVERFLOW if check_overflow else 0
         with torch.cuda.device(self.device):
-            check(self.L.mse_lookahead(self._h, int(horizon), float(gamma), 1 if base_policy == "rule_based" else 0, int(base_seed),
-                                       1 if streams == "fresh" else 0, int(seed), int(n_samples), _ptr(sort_mode),
-                                       MSE_STEP_CHECK_OVERFLOW if check_overflow else 0, _ptr(out["q"]), _ptr(out["action"]),
-                                       _ptr(out["value"]), _ptr(ws), self._stream()))
+            if net is None:
+                check(self.L.mse_lookahead(self._h, int(horizon), float(gamma), base_code, int(base_seed),
+                                           1 if streams == "fresh" else 0, int(seed), int(n_samples), _ptr(sort_mode), flags,
+                                           _ptr(out["q"]), _ptr(out["action"]), _ptr(out["value"]), _ptr(ws), self._stream()))
+            else:
+                check(self.L.mse_lookahead_net(self._h, net._h, int(horizon), float(gamma), base_code,
+                                               1 if base_deterministic else 0, int(base_seed), 0 if leaf_value is None else 1,
+                                               1 if streams == "fresh" else 0, int(seed), int(n_samples), _ptr(sort_mode), flags,
+                                               _ptr(out["q"]), _ptr(out["action"]), _ptr(out["value"]), _ptr(ws), self._stream()))
         return out
 
     # ---- state export / import (tests, checkpoint, dashboard trace) ---------------------------

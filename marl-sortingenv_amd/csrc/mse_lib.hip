@@ -1304,6 +1304,118 @@ __global__ __launch_bounds__(512) void k_rollout_policy_labelled(Params P, uint4
 #include "mse_rollout_policy_body.inc"
 }
 
+// ==========================================================================================
+// Lookahead with a network inside the fork (mse_lookahead_net).  k_lookahead's grid and lane assignment -
+// one lane per (env, candidate, sample), a wave = 64 neighbouring envs under one candidate and sample -, which is exactly
+// a TILES = 2 pair of MFMA tiles: the wave runs actor_tiles (base_mode 2: the base policy of steps 1 .. H - 1) and
+// value_tiles (leaf: the critic's value of the state a fork stands in after H steps) on its own 64 forks, observations
+// from registers through operands_of.  LDS: [one policy weight image][the table image up to the jump tables].
+// The tile functions need all 64 lanes, so the fork loop is the wave's, not the lane's: it runs while any lane's fork is
+// alive, and a dead lane (forbidden candidate, ended episode, past the batch's end) holds its state - env_step sits under
+// the lane's `alive`, nothing else touches `e` - and feeds the tiles the last observation it formed (zeros if it never
+// stepped).  A network's row does not depend on its neighbours (mse_policy_device.h), so that changes no live lane's bits.
+// The base policy (0 random, 1 rule_based, 2 network), base_deterministic, the leaf flag and the stream mode are wave-uniform
+// arguments in one word (kLookNet*), not template parameters: twelve instantiations, none with scratch or a spill (DESIGN.md
+// 4.23 has the resource report, and what a compile-time network base gave when it was tried).
+// ==========================================================================================
+enum : uint32_t { kLookNetBaseMask = 3u, kLookNetDeterministic = 4u, kLookNetLeaf = 8u, kLookNetFresh = 16u };
+template <int KIND, bool NOISE, bool F16X3>
+__global__ __launch_bounds__(kBlock) void k_lookahead_net(Params P, const uint4 *__restrict__ planes,
+                                                          const uint32_t *__restrict__ table_image,
+                                                          const float *__restrict__ weight_blob, int horizon, double gamma,
+                                                          uint32_t flags, uint32_t mode, uint64_t base_seed,
+                                                          uint64_t lookahead_seed,
+                                                          const int *__restrict__ sort_mode, double *__restrict__ returns)
+{
+    constexpr int A = Dims<KIND>::A, NR = msep::regs_for_actions(A);
+    float *lw = reinterpret_cast<float *>(mse_dyn_lds);
+    uint32_t *ltab = reinterpret_cast<uint32_t *>(lw + msep::kLdsFloats);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const long long wave_row0 = (long long)blockIdx.x * kBlock + (tid & ~63);
+    const long long i_own = wave_row0 + lane;
+    const bool live = i_own < P.n;
+    const long long i = live ? i_own : P.n - 1; // lanes past the batch's end mirror its last env and store nothing
+    const int cand = (int)blockIdx.y;
+    const uint32_t sample = blockIdx.z;
+
+    Env e;
+    load_env<KIND, NOISE>(e, planes, P, i); // in flight while the image and the tables are copied
+    msep_copy_image(lw, weight_blob, F16X3, tid, kBlock);
+    load_tables_to_lds(ltab, table_image, P.off_jump, tid); // off_jump is a multiple of 4 words; ends with the barrier
+    const Tables tb = tables_at(ltab, P);
+    if (wave_row0 >= P.n) return; // a wave without an env; after the workgroup's one barrier
+    const msep::lds_f4 wl = (msep::lds_f4)(__attribute__((address_space(3))) float *)lw;
+    const int sm = (KIND == 2 && sort_mode != nullptr) ? sort_mode[i] : -1;
+
+    uint32_t cur_mask = action_mask_bits<KIND>(e, P);
+    const bool legal_cand = ((cur_mask >> cand) & 1u) != 0;
+    bool alive = live && legal_cand;
+    const uint64_t g = (uint64_t)(P.index_offset + i);
+    if (mode & kLookNetFresh) { // k_lookahead's: the streams mse_reset gives an env seeded with the fork's seed
+        const uint64_t seed = mse_lookahead_seed_of(lookahead_seed, g, sample);
+        e.rng = pcg_seed(seed + 99);
+        if (NOISE) e.noise = pcg_seed(seed + 4);
+        if (KIND == 1) {
+            e.press = pcg_seed(seed + 3);
+            e.press_has = 0;
+            e.press_uint = 0;
+        }
+    }
+    const uint32_t pkey = mse_policy_key(base_seed, g);
+    // policy stream keys of the envs this lane serves as an MFMA column (tile t = lanes 32 t .. 32 t + 31 of the wave)
+    const int h = lane >> 5, col = lane & 31;
+    const uint32_t key0 = mse_policy_key(base_seed, (uint64_t)(P.index_offset + wave_row0 + col));
+    const uint32_t key1 = mse_policy_key(base_seed, (uint64_t)(P.index_offset + wave_row0 + 32 + col));
+    const bool net_base = (mode & kLookNetBaseMask) == 2u;
+    const uint32_t pflags = flags | ((mode & kLookNetBaseMask) == 1u ? MSE_ROLLOUT_RULE_BASED : 0u);
+    const BaleDiscard bales{};
+    float o[32]; // the observation of the state the fork stands in: live here (the network reads it)
+#pragma unroll
+    for (int j = 0; j < 32; ++j) o[j] = 0.0f;
+    // Env_3's step keeps the scalar file full, so what only the end needs is put into vector registers here, of which there
+    // are plenty: the lane's output slot (else its scalar parts - returns, sample, candidate, n - stay live to the end), what
+    // the lane will store (else `live` and `legal_cand` are two lane masks of two SGPRs each), and gamma
+    double *slot = returns + (((long long)sample * A + cand) * P.n + i);
+    int store_what = live ? (legal_cand ? 2 : 1) : 0; // nothing | -inf | ret
+    double gamma_v = gamma;
+    asm volatile("" : "+v"(slot), "+v"(store_what), "+v"(gamma_v));
+    double disc = 1.0; // the same in every lane: multiplied once per step of the wave's loop
+    double ret = 0.0;
+    int a = cand;
+    for (int s = 0;;) {
+        if (alive) {
+            int k[4];
+            const StepResult r = env_step<KIND, NOISE, false, false, false, BaleDiscard>(e, P, tb, a, sm, flags, bales, k, o);
+            ret = __dadd_rn(ret, __dmul_rn(disc, r.reward)); // acc += disc * r, two roundings
+            alive = r.done == 0;                             // the fork ends with its episode: no auto-reset
+        }
+        disc = __dmul_rn(disc, gamma_v);
+        if (++s >= horizon || __ballot(alive) == 0ull) break; // wave-uniform
+        cur_mask = action_mask_bits<KIND>(e, P);
+        if (net_base) { // wave-uniform: all 64 lanes in the tiles
+            float x[2][16];
+            operands_of(o, x);
+            uint32_t mb0, mb1;
+            msep::both_halves_u32(cur_mask, mb0, mb1);
+            const uint32_t legal[2] = {legal_of(mb0, h), legal_of(mb1, h)};
+            const uint32_t words[2] = {mse_policy_word(key0, (uint64_t)s), mse_policy_word(key1, (uint64_t)s)};
+            msep::TileOut p[2];
+            msep::actor_tiles<NR, F16X3, 2>(wl, lane, x, A, legal, (mode & kLookNetDeterministic) != 0, words, p);
+            a = tile_pick<2>(h, p[0].action, p[1].action);
+        } else {
+            a = policy_action<KIND, false>(e, cur_mask, tb, pflags, pkey, (uint64_t)s);
+        }
+    }
+    if ((mode & kLookNetLeaf) && __ballot(alive) != 0ull) { // a live lane here took `horizon` steps and none ended its episode
+        float x[2][16], v[2];
+        operands_of(o, x);
+        msep::value_tiles<F16X3, 2>(wl, lane, x, v);
+        const float value = tile_pick<2>(h, v[0], v[1]);
+        if (alive) ret = __dadd_rn(ret, __dmul_rn(disc, (double)value));
+    }
+    if (store_what != 0) *slot = store_what == 2 ? ret : -__builtin_inf();
+}
+
 // ---- the learned-policy rollout in roles (batches that leave a SIMD 64 envs: n <= 256 envs x CUs) --------------------
 // k_rollout_policy at that size has to choose between one 64-env wave per SIMD, alone with its own latencies, and two
 // 32-env waves that issue the env transition twice with half their lanes mirroring.  Here a SIMD's 64 envs are one full
@@ -3019,6 +3131,62 @@ int mse_lookahead(mse_env *h, int32_t horizon, double gamma, int32_t base_policy
             hipLaunchKernelGGL((k_lookahead<KIND, NOISE, LIT>), grid, dim3(kBlock), (size_t)h->P.off_jump * 4u, s, h->P, h->planes,
                                h->tables, horizon, gamma, kflags, base_seed, streams, lookahead_seed, sort_mode, returns);
         }, h->noise_on, h->literal);
+        hipLaunchKernelGGL(k_lookahead_reduce<A>, grid_of(h), dim3(kBlock), 0, s, (long long)h->P.n, n_samples, returns, q_out,
+                           action_out, value_out);
+    });
+    MSE_CHECK_LAUNCH();
+    return MSE_OK;
+}
+
+// mse_lookahead with a network inside the fork: k_lookahead_net, then k_lookahead_reduce unchanged (include/mse.h)
+int mse_lookahead_net(mse_env *h, mse_policy *pol, int32_t horizon, double gamma, int32_t base_policy, int32_t base_deterministic,
+                      uint64_t base_seed, int32_t leaf_value, int32_t streams, uint64_t lookahead_seed, int32_t n_samples,
+                      const int32_t *sort_mode, uint32_t flags, double *q_out, int32_t *action_out, double *value_out,
+                      void *workspace, void *stream)
+{
+    const auto aligned8 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; };
+    if (!h || !q_out || !workspace) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: env / q_out / workspace is NULL");
+    if (horizon < 1 || horizon > MSE_LOOKAHEAD_MAX_HORIZON)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: horizon must be in [1, MSE_LOOKAHEAD_MAX_HORIZON]");
+    if (n_samples < 1 || n_samples > MSE_LOOKAHEAD_MAX_SAMPLES)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: n_samples must be in [1, MSE_LOOKAHEAD_MAX_SAMPLES]");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: gamma must be a number in [0, 1]");
+    if (base_policy < 0 || base_policy > 2 || streams < 0 || streams > 1)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: base_policy is 0 (random) | 1 (rule_based) | 2 (network), streams 0 (own) | 1 (fresh)");
+    if (flags & ~MSE_STEP_CHECK_OVERFLOW)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: the only flag is MSE_STEP_CHECK_OVERFLOW (a fork steps with masking on)");
+    if (sort_mode && h->P.env_kind != MSE_ENV_PRESS)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: sort_mode_dev is Env_2's sorting decision; this kind has none");
+    if (!pol) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: policy is NULL");
+    if (pol->d_in != mse_obs_dim(h) || pol->n_act != mse_num_actions(h) || pol->device != h->device)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: the policy must be an obs_dim -> num_actions one on the env's device");
+    if (leaf_value < 0 || leaf_value > 1) return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: leaf_value is 0 | 1");
+    if (base_policy != 2 && leaf_value == 0)
+        return fail(MSE_ERR_INVALID_ARGUMENT, "mse_lookahead_net: neither the base policy nor the leaf value is the network's: "
+                                              "mse_lookahead is the call");
+    if (h->P.gen_mode)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_lookahead_net: general generator mode is not served (the fork does not carry the "
+                                                "input generator's private stream): fork with mse_get_state / mse_set_state");
+    if (h->literal)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_lookahead_net: a literal_choice handle is not served: alternate "
+                                                "mse_policy_forward and mse_step on forks made with mse_get_state / mse_set_state");
+    const size_t lds_bytes = (size_t)msep::kLdsFloats * 4u + (size_t)h->P.off_jump * 4u;
+    if (lds_bytes > kLdsLimitBytes)
+        return fail(MSE_ERR_UNSUPPORTED_CONFIG, "mse_lookahead_net: the weight image and this config's tables do not fit the LDS");
+    if (!h->seeded) return fail(MSE_ERR_NOT_RESET, "mse_lookahead_net before mse_reset(seeds)");
+    if (!aligned8(q_out) || !aligned8(value_out) || !aligned8(workspace))
+        return fail(MSE_ERR_ALIGNMENT, "mse_lookahead_net: q_out / value_out / workspace must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double *returns = static_cast<double *>(workspace);
+    const uint32_t mode = (uint32_t)base_policy | (base_deterministic != 0 ? kLookNetDeterministic : 0u) |
+                          (leaf_value ? kLookNetLeaf : 0u) | (streams ? kLookNetFresh : 0u);
+    with_kind(h->P.env_kind, [&](auto KIND) {
+        constexpr int A = Dims<KIND>::A;
+        const dim3 grid((unsigned)(h->P.n_pad / kBlock), (unsigned)A, (unsigned)n_samples);
+        with_flags([&](auto NOISE, auto F16) {
+            hipLaunchKernelGGL((k_lookahead_net<KIND, NOISE, F16>), grid, dim3(kBlock), lds_bytes, s, h->P, h->planes, h->tables,
+                               pol->blob, horizon, gamma, flags, mode, base_seed, lookahead_seed, sort_mode, returns);
+        }, h->noise_on, pol->use_f16());
         hipLaunchKernelGGL(k_lookahead_reduce<A>, grid_of(h), dim3(kBlock), 0, s, (long long)h->P.n, n_samples, returns, q_out,
                            action_out, value_out);
     });

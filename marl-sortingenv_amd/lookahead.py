@@ -2,7 +2,8 @@
 
 From the current state of every env, try every action, follow each with horizon - 1 steps of a base policy, and take the
 action with the best return.  `BatchedSortingEnv.lookahead` is that in one launch (`mse_lookahead`: every env's state is
-read once, the A x M forks run in registers, nothing is written back).  On top of it:
+read once, the A x M forks run in registers, nothing is written back).  With an `MlpPolicy` as `base_policy` and / or
+`leaf_value` it is `mse_lookahead_net`: the learned actor inside the fork, the learned critic at its end.  On top of it:
 
 - `lookahead_reference`: the multi-launch twin, written from include/mse.h's sentence with calls that exist without the
   kernel - a scratch env of N x A x M forks filled by `get_state` / `set_state`, stepped with `step`, `rule_actions` and
@@ -20,13 +21,14 @@ from typing import Optional
 import torch
 
 from ._lib import check
-from .batched import BatchedSortingEnv
+from .batched import BatchedSortingEnv, lookahead_network
 from .collector import rollout_buffers
 from .episodes import _begin, _finish
 from .learner import _ptr, _stream
 from .policy import MlpPolicy
 
-LOOKAHEAD_KW = ("gamma", "base_policy", "streams", "seed", "base_seed", "n_samples", "sort_mode", "check_overflow")
+LOOKAHEAD_KW = ("gamma", "base_policy", "streams", "seed", "base_seed", "n_samples", "sort_mode", "check_overflow", "leaf_value",
+                "base_deterministic")
 LOOKAHEAD_ROWS = ("observations", "action_masks", "actions", "stepped_actions", "rewards", "episode_starts", "returns")
 
 
@@ -37,8 +39,7 @@ def check_lookahead_args(horizon: int, kw: dict, allowed=LOOKAHEAD_KW) -> None:
         raise TypeError(f"unknown lookahead argument(s) {unknown}: the choices are {list(allowed)}")
     if int(horizon) < 1:
         raise ValueError("horizon must be >= 1")
-    if kw.get("base_policy", "rule_based") not in ("rule_based", "random"):
-        raise ValueError(f"base_policy must be 'rule_based' or 'random', not {kw['base_policy']!r}")
+    lookahead_network(kw.get("base_policy", "rule_based"), kw.get("leaf_value"))  # a bad string, two different policies
     if kw.get("streams", "fresh") not in ("fresh", "own"):
         raise ValueError(f"streams must be 'fresh' or 'own', not {kw['streams']!r}")
     if int(kw.get("n_samples", 1)) < 1:
@@ -61,12 +62,17 @@ def stream_seeds(env: BatchedSortingEnv, seed: int, n_samples: int) -> torch.Ten
                         dtype=torch.int64)
 
 
-def lookahead_reference(env: BatchedSortingEnv, horizon: int, gamma: float = 1.0, base_policy: str = "rule_based",
+def lookahead_reference(env: BatchedSortingEnv, horizon: int, gamma: float = 1.0, base_policy="rule_based",
                         streams: str = "fresh", seed: int = 0, base_seed: int = 2024, n_samples: int = 1,
-                        sort_mode: Optional[torch.Tensor] = None, check_overflow: bool = False) -> dict:
+                        sort_mode: Optional[torch.Tensor] = None, check_overflow: bool = False,
+                        leaf_value: Optional[MlpPolicy] = None, base_deterministic: bool = True) -> dict:
     """`env.lookahead(...)` in many launches; the same dict.  Fork j = (m * A + a) * N + i is env i under candidate a in
-    sample m.  `env` is only read (`get_state`, `action_masks`)."""
-    check_lookahead_args(horizon, dict(base_policy=base_policy, streams=streams, n_samples=n_samples))
+    sample m.  `env` is only read (`get_state`, `action_masks`).  A network base policy is `policy.forward` on the scratch
+    env's observation and mask, block by block over the A x M blocks of N forks (a block's rows are envs 0 .. N - 1, so
+    `index_offset=env.index_offset` gives fork j the word of env i); the leaf is `forward(...)["value"]` of the state the
+    forks stand in after `horizon` steps, added where no step ended the fork's episode."""
+    check_lookahead_args(horizon, dict(base_policy=base_policy, streams=streams, n_samples=n_samples, leaf_value=leaf_value))
+    net, base_code = lookahead_network(base_policy, leaf_value)
     N, A, M, dev = env.num_envs, env.num_actions, int(n_samples), env.device
     F = N * A * M
     ints, dbls, rng = env.get_state()
@@ -80,7 +86,8 @@ def lookahead_reference(env: BatchedSortingEnv, horizon: int, gamma: float = 1.0
     scratch = _scratch_like(env, F)
     scratch.set_state(rep(ints), rep(dbls), fork_rng)
     sm = None if sort_mode is None else sort_mode.to(device=dev, dtype=torch.int32).repeat(A * M)
-    sampler = _scratch_like(env, N, index_offset=env.index_offset) if base_policy == "random" and horizon > 1 else None
+    sampler = _scratch_like(env, N, index_offset=env.index_offset) if base_code == 0 and horizon > 1 else None
+    fwd = None  # the network's output dict of one block, written again by every forward
 
     # step 0: the candidate; a forbidden candidate's fork steps the env's first legal action instead and is discarded below
     cand = torch.arange(A, dtype=torch.int32, device=dev).view(A, 1).expand(A, N)
@@ -91,8 +98,15 @@ def lookahead_reference(env: BatchedSortingEnv, horizon: int, gamma: float = 1.0
     disc = 1.0
     for s in range(int(horizon)):
         if s > 0:
-            if base_policy == "rule_based":
+            if base_code == 1:
                 actions = scratch.rule_actions()
+            elif base_code == 2:  # mse_policy_forward on the fork's observation and action_masks(), t = s
+                actions = torch.empty(F, dtype=torch.int32, device=dev)
+                for b in range(A * M):
+                    cut = slice(b * N, (b + 1) * N)
+                    fwd = net.forward(scratch.obs[cut], scratch.mask[cut], seed=base_seed, t=s, deterministic=bool(base_deterministic),
+                                      index_offset=env.index_offset, out=fwd)
+                    actions[cut] = fwd["action"]
             else:  # the word of (base_seed, global index of env i, s): the same for every fork of env i
                 si, sd, sr = scratch.get_state()
                 sampler.policy_step = s
@@ -107,6 +121,14 @@ def lookahead_reference(env: BatchedSortingEnv, horizon: int, gamma: float = 1.0
         disc = disc * float(gamma)
         if not bool(alive.any()):
             break
+    if leaf_value is not None and bool(alive.any()):  # `alive` forks took `horizon` steps; disc = gamma^horizon, rounded per step
+        leaf = torch.empty(F, dtype=torch.float64, device=dev)
+        for b in range(A * M):
+            cut = slice(b * N, (b + 1) * N)
+            fwd = net.forward(scratch.obs[cut], scratch.mask[cut], seed=base_seed, t=int(horizon), deterministic=True,
+                              index_offset=env.index_offset, out=fwd)
+            leaf[cut] = fwd["value"].double()
+        acc = torch.where(alive, acc + disc * leaf, acc)  # ret + disc * (double)v: two roundings
     scratch.close()
     if sampler is not None:
         sampler.close()
@@ -138,7 +160,11 @@ class LookaheadCollector:
     `returns`, `stepped_actions` - plus `rule_actions` i32[K, N] and `values` f64[K, N]; `ImitationLearner.learn` consumes
     it unchanged, and since it steps through `mse_step`, `evaluate_plant`'s trace and `EpisodeStats` see it as any stepping.
     gamma discounts both the planner's returns and `returns`.  lookahead_kw: base_policy, streams, base_seed, n_samples,
-    sort_mode, check_overflow."""
+    sort_mode, check_overflow, leaf_value, base_deterministic.  base_policy and leaf_value may be an `MlpPolicy`
+    (`mse_lookahead_net`): the handle is live, so every `env.lookahead` of the loop above plans with the weights the policy
+    holds at that moment.  `LookaheadCollector(env, ..., actor=student, base_policy=student, leaf_value=student)` followed by
+    `ImitationLearner(student).learn` is expert iteration: the student steps the env, is the base policy and the leaf value
+    of the planner that labels it, and each `collect()` plans with what the last update left."""
 
     def __init__(self, env: BatchedSortingEnv, n_steps: int, horizon: int, actor: Optional[MlpPolicy] = None,
                  deterministic_actor: bool = False, gamma: float = 0.99, seed: int = 2024, **lookahead_kw):

@@ -21,6 +21,9 @@ launches per step) for each agent combination at --envs envs and K = --k steps.
     python tools/benchmark_scenarios.py --plant [--envs 4096]      the plant ledger beside the reward (multi-launch stepping)
     python tools/benchmark_scenarios.py --planner 1 4 16 [--envs 10] [--planner-streams fresh] [--planner-samples 1]
                                                                    the lookahead planner (mse_lookahead) at these horizons
+    python tools/benchmark_scenarios.py --planner 1 2 4 8 --envs 10 --planner-policy F [--planner-base network] [--planner-leaf]
+                                                                   a learned network inside the forks (mse_lookahead_net): its
+                                                                   actor as the base policy, its critic as the leaf value
 """
 import argparse
 import os
@@ -47,8 +50,15 @@ ap.add_argument("--planner", type=int, nargs="+", default=None, metavar="H",
                      "first (every action tried on a fork, followed by H - 1 rule-based steps), one row per horizon")
 ap.add_argument("--planner-streams", default="fresh", choices=("fresh", "own"), help="the forks' streams ('own' is clairvoyant)")
 ap.add_argument("--planner-samples", type=int, default=1, help="forks per candidate action")
-ap.add_argument("--planner-base", default="rule_based", choices=("rule_based", "random"), help="the forks' base policy")
+ap.add_argument("--planner-base", default="rule_based", choices=("rule_based", "random", "network"),
+                help="the forks' base policy; 'network': the argmax of the --planner-policy actor (mse_lookahead_net)")
+ap.add_argument("--planner-policy", default=None, metavar="FILE",
+                help="the network inside the planner's forks (29 -> 22): a state_dict as tools/train_ppo.py --save writes it")
+ap.add_argument("--planner-leaf", action="store_true",
+                help="add the --planner-policy critic's value of the state a fork stands in after H steps (bootstrapped lookahead)")
 args = ap.parse_args()
+if (args.planner_leaf or args.planner_base == "network") and not args.planner_policy:
+    ap.error("--planner-leaf and --planner-base network need --planner-policy FILE")
 n, T = args.envs, 200
 
 
@@ -116,12 +126,20 @@ if args.planner:
     from marl_sortingenv_amd.plant import evaluate_plant, format_summary
 
     kw = dict(streams=args.planner_streams, n_samples=args.planner_samples, base_policy=args.planner_base)
+    shown = dict(kw)
+    if args.planner_policy:
+        net = M.MlpPolicy.from_state_dict(torch.load(args.planner_policy, map_location="cpu"), device=0)
+        if args.planner_base == "network":
+            kw["base_policy"] = net
+        if args.planner_leaf:
+            kw["leaf_value"] = net
+        shown = dict(shown, leaf_value=args.planner_leaf, policy=os.path.basename(args.planner_policy))
     r = total_reward(make(), "rule_based")
     print(f"{'Rule-Based, masking':24s} {n} seeds: cumulative reward {float(r.mean()):8.2f} +- {float(r.std(unbiased=False)):6.2f}")
     for H in args.planner:
         env = make()
         mean, std = M.evaluate_lookahead(env, n, H, **kw)
-        print(f"{'Planner H=' + str(H):24s} {n} seeds: cumulative reward {mean:8.2f} +- {std:6.2f}   ({kw})", flush=True)
+        print(f"{'Planner H=' + str(H):24s} {n} seeds: cumulative reward {mean:8.2f} +- {std:6.2f}   ({shown})", flush=True)
         if args.plant:
             print(format_summary(evaluate_plant(M.LookaheadCollector(env, 50, H, gamma=1.0, seed=0, **kw), n_eval_episodes=n)))
         env.close()

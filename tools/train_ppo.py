@@ -60,6 +60,9 @@
                                                           # the teacher is the lookahead planner (LookaheadCollector: every
                                                           # action tried on a fork of the env and followed by H - 1 rule-based
                                                           # steps, one mse_lookahead launch per step); --dagger: the clone steps
+    python tools/train_ppo.py --kind mono --pretrain lookahead --horizon 8 --dagger --planner-self --eval-every 10
+                                                          # expert iteration: the policy being cloned is the planner's base
+                                                          # policy and leaf value (mse_lookahead_net, the current weights)
     python tools/train_ppo.py --time --time-section preview  # the preview launch (plain, with labels, with the mixture) beside
                                                           # the plain policy kernel at 65 536 and 262 144 envs; only when named
     python -m torch.distributed.run --nproc-per-node 8 tools/train_ppo.py --kind mono --envs 262144 --data-parallel
@@ -444,8 +447,11 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
                               max_steps=args.max_steps, auto_reset=True)
     planner = args.pretrain == "lookahead"
     if planner:  # the planner labels the env's own observation; with --dagger the student steps, without it the planner
+        # --planner-self: expert iteration - the student is the base policy and the leaf value of the planner that labels
+        # it (mse_lookahead_net reads the handle's weights at every launch, so each collect() plans with the last update's)
+        self_kw = dict(base_policy=pol, leaf_value=pol) if args.planner_self else {}
         col = M.LookaheadCollector(env, args.steps, args.horizon, actor=pol if args.dagger else None, seed=args.seed + 7,
-                                   n_samples=args.lookahead_samples)
+                                   n_samples=args.lookahead_samples, **self_kw)
     elif args.dagger:
         col = M.FusedDemonstrationRollout(env, args.steps, actor=pol, beta=1.0, seed=args.seed + 7, mix_seed=args.seed + 8,
                                           agent="preview" if agent == "preview" else "own")
@@ -455,6 +461,7 @@ def pretrain(args, pol, env_kind, agent, name, eval_col=None):
                             seed=args.seed, shuffle=args.shuffle, weight_sync=args.weight_sync, arithmetic=args.arithmetic)
     print(f"cloning {f'the lookahead planner (H = {args.horizon})' if planner else 'the rule-based controller'} into {name} ({pol.obs_dim} -> {pol.n_actions}): {args.pretrain_iterations} "
           f"iterations of {args.envs} envs x {args.steps} steps, {args.pretrain_epochs} epochs each, lr {args.pretrain_lr:g}"
+          + (", the student is the planner's base policy and leaf value" if planner and args.planner_self else "")
           + (", the student steps" if planner and args.dagger else
              f", DAgger with beta schedule '{args.beta_schedule}'" if args.dagger else ""))
 
@@ -605,6 +612,9 @@ def main():
                          "--horizon - 1 rule-based steps); with --dagger the policy being cloned steps the envs")
     ap.add_argument("--horizon", type=int, default=8, metavar="H", help="with --pretrain lookahead: the planner's horizon")
     ap.add_argument("--lookahead-samples", type=int, default=1, metavar="M", help="with --pretrain lookahead: forks per candidate")
+    ap.add_argument("--planner-self", action="store_true",
+                    help="with --pretrain lookahead: expert iteration - the policy being cloned is the planner's base policy (argmax) "
+                         "and its critic the leaf value (mse_lookahead_net), so every collection plans with the current weights")
     ap.add_argument("--pretrain-iterations", type=int, default=20, metavar="N",
                     help="with --pretrain: collections of --envs x --steps demonstrations, each followed by one update")
     ap.add_argument("--pretrain-epochs", type=int, default=4, help="with --pretrain: epochs per update")
@@ -646,6 +656,8 @@ def main():
         raise SystemExit("--pretrain lookahead labels the env's own observation: it goes with --kind sort | press | mono and --view own")
     if args.pretrain == "lookahead" and args.horizon < 1:
         raise SystemExit("--horizon must be >= 1")
+    if args.planner_self and args.pretrain != "lookahead":
+        raise SystemExit("--planner-self goes with --pretrain lookahead")
     if args.kind == "modular" and not (args.time and args.time_section in ("modular_demo", "preview")):
         return train_modular(args)
     if args.time:
